@@ -8,6 +8,14 @@ stage 3 fused into the contraction, finalize), evaluate the derivative table on 
 (txm_eval_poly) and copy the (order+1, nrep, N_obs) derivatives to the host.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config north|c2|c4|c3|c5] [--mode states|replicas]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W untimed and K timed steps and prints the headline line (value, ms_per_step, the per-step
+breakdown from the events inside the timed steps).  `--full` adds what takes runs of its own after the timed region: the
+sampler, cold-call, reduce and forced-FP64 timings, the parity check against the FP64 kernel, the roofline blocks, the
+generator split and the CPU baseline (configs 3 and 5: the kernel roofline and the serial loop over the states).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB in all): the inputs
+and the sampler seeds depend on the arguments only, so two builds can be compared output for output.
 
 Multi-GPU (one process per GPU, RCCL): `--gpus N` with N > 1 starts the N ranks itself when it is not
 already running under torch.distributed.run (child process, before anything touches the GPU) and
@@ -59,13 +67,46 @@ def parse():
     p.add_argument("--n-obs", type=int, default=None)
     p.add_argument("--order", type=int, default=None)
     p.add_argument("--nrep", type=int, default=None)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-fp64-leg", action="store_true", help="skip timing the same shape with the FP64 kernel")
+    p.add_argument("--full", action="store_true",
+                   help="also the measurements that take runs of their own: roofline, FP64 leg, parity, cold call, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the arrays the last timed step returned as DIR/<name>.npy (float64, at most 64 MB in all)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-fp64-leg", action="store_true", help="with --full: skip timing the same shape with the FP64 kernel")
     p.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU baseline duration")
     p.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0: min(host cores, N_obs) -- the reference threads over observables only)")
     p.add_argument("--dry-run", action="store_true",
                    help="no GPU: ranks rendezvous over gloo and run the sharded step with a stand-in compute (tests the launcher)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000  # all .npy files of one --dump-outputs together, headers included
+
+
+def dump_outputs(dirname, arrays: dict) -> None:
+    """DIR/<name>.npy for every array (torch tensors, labelled arrays, numpy): float32 stays float32, the rest is written as
+    float64.  When the arrays hold more than DUMP_LIMIT_BYTES together, each is replaced by the same fixed, seeded sample
+    of its flattened elements (a share proportional to its size, in index order), so two runs still compare element for
+    element."""
+    import numpy as np
+
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        host[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+    budget = DUMP_LIMIT_BYTES - 256 * len(host)                 # (an .npy header is at most a few hundred bytes)
+    total = sum(a.nbytes for a in host.values())
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in host.items():
+        if total > budget:
+            flat = a.reshape(-1)
+            n = max(1, int(flat.size * (budget / total)))
+            a = flat[np.sort(np.random.default_rng(0).choice(flat.size, n, replace=False))]
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
 
 
 def dry_run(args):
@@ -489,6 +530,13 @@ def main():
     ms_per_step = 1e3 * dt / args.steps
     value = (1 if replicas else world) * N / (dt / args.steps)
     nrep_rank = len(txd.shard_range(nrep, rank, world)) if replicas else nrep
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: this rank's host derivatives (order+1, nrep, N_obs), the gathered
+        # replicate states (rows, N_obs, 2, order+1) and, for config 4, the per-replicate <dx/dq> of the same call
+        outs = {"derivs": results["derivs"], "replicate_states": results["slabs"]}
+        if dxdq is not None:
+            outs["dxdq"] = results["dxdq"]
+        dump_outputs(args.dump_outputs, outs)
     main_calls = [a.elapsed_time(b) for a, b in boot_events]
     t_boot = sum(main_calls) / max(len(main_calls), 1)
     info = engine.resample_info()
@@ -504,184 +552,186 @@ def main():
         "how": "HIP events on the launch stream inside the timed steps; host_and_gather = wall clock per step minus the events",
     }
 
-    # ---- separate event timings of the other kernels of a step (same stream) -------
-    def timed(fn, reps):
-        evs = []
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            evs.append((e0, e1))
-        torch.cuda.synchronize()
-        ts = [a.elapsed_time(b) for a, b in evs]
-        return sum(ts) / len(ts)  # mean ms
-
-    sampler = engine.DeviceSampler(seed=0, nrep=nrep_rank, ndat=N)
-    out = torch.empty((nrep_rank, C, 2, K), dtype=torch.float64, device="cuda")
-    t_samp = timed(lambda: sampler.draw(seed=777), 3)
-    # the FIRST bootstrap of a data object also runs the int8 path's pre-pass (one more read of the samples: pivot, window
-    # table, guard flags); the timed steps reuse the block the data object keeps -- `prepass_reused` -- so this is the
-    # one-time cost per data object that `value` does not contain
-    def cold():
-        engine.resample_vals(x, u, order, sampler=sampler, out=out, prep=engine.ResamplePrep(), y=dxdq)
-    cold()
-    step_breakdown["cold_call_ms"] = timed(cold, 2)
-    step_breakdown["cold_call_note"] = ("one txm_resample_vals call on a data object without a pre-pass block (pivot estimate + pre-pass + "
-                                        "contraction + finalize); bootstrap_call above is the same call with the block reused")
-    t_red = timed(lambda: engine.reduce_vals(x, u, order), 10)
     path = info["path"]
-    t_fp64 = None
-    parity = None
-    if path == "int8" and not args.no_fp64_leg:
-        with engine.forced_path("fp64"):
-            engine.resample_vals(x, u, order, sampler=sampler, pivot=pivot, out=out)
-            t_fp64 = timed(lambda: engine.resample_vals(x, u, order, sampler=sampler, pivot=pivot, out=out), 2)
-        # parity of what was timed (outside the timed region): the default dispatch against the FP64 kernel on the same
-        # sampler draw, every replicate and column, relative to each comoment's natural scale sigma_x^a sigma_u^b
-        got = engine.resample_vals(x, u, order, sampler=sampler, pivot=pivot)
-        sx, su = x[: 1 << 20].std(dim=0), u[: 1 << 20].std()
-        sc = torch.empty((C, 2, K), dtype=torch.float64, device="cuda")
-        for b in range(K):
-            sc[:, 0, b] = su**b
-            sc[:, 1, b] = sx * su**b
-        parity = {"max_scaled_abs_diff_vs_fp64_kernel": float(((got - out).abs() / (out.abs() + sc[None])).max()),
-                  "over": f"{nrep_rank} replicates x {C} columns x 2 x {K} comoments, same sampler draw",
-                  "tolerance_in_tests": 1e-12}
-        del got
+    roofline = roofline_reduce = roofline_fp64 = parity = t_samp = None
+    if args.full:
+        # ---- separate event timings of the other kernels of a step (same stream) -------
+        def timed(fn, reps):
+            evs = []
+            for _ in range(reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                evs.append((e0, e1))
+            torch.cuda.synchronize()
+            ts = [a.elapsed_time(b) for a, b in evs]
+            return sum(ts) / len(ts)  # mean ms
 
-    shape = (N, C, order, nrep_rank)
-    alg_bytes = 8.0 * N * (C + 1)                         # samples read once
-    alg_flops = 2.0 * N * nrep_rank * K * (C + 1)         # dense contraction F.M
+        sampler = engine.DeviceSampler(seed=0, nrep=nrep_rank, ndat=N)
+        out = torch.empty((nrep_rank, C, 2, K), dtype=torch.float64, device="cuda")
+        t_samp = timed(lambda: sampler.draw(seed=777), 3)
+        # the FIRST bootstrap of a data object also runs the int8 path's pre-pass (one more read of the samples: pivot, window
+        # table, guard flags); the timed steps reuse the block the data object keeps -- `prepass_reused` -- so this is the
+        # one-time cost per data object that `value` does not contain
+        def cold():
+            engine.resample_vals(x, u, order, sampler=sampler, out=out, prep=engine.ResamplePrep(), y=dxdq)
+        cold()
+        step_breakdown["cold_call_ms"] = timed(cold, 2)
+        step_breakdown["cold_call_note"] = ("one txm_resample_vals call on a data object without a pre-pass block (pivot estimate + pre-pass + "
+                                            "contraction + finalize); bootstrap_call above is the same call with the block reused")
+        t_red = timed(lambda: engine.reduce_vals(x, u, order), 10)
+        t_fp64 = None
+        parity = None
+        if path == "int8" and not args.no_fp64_leg:
+            with engine.forced_path("fp64"):
+                engine.resample_vals(x, u, order, sampler=sampler, pivot=pivot, out=out)
+                t_fp64 = timed(lambda: engine.resample_vals(x, u, order, sampler=sampler, pivot=pivot, out=out), 2)
+            # parity of what was timed (outside the timed region): the default dispatch against the FP64 kernel on the same
+            # sampler draw, every replicate and column, relative to each comoment's natural scale sigma_x^a sigma_u^b
+            got = engine.resample_vals(x, u, order, sampler=sampler, pivot=pivot)
+            sx, su = x[: 1 << 20].std(dim=0), u[: 1 << 20].std()
+            sc = torch.empty((C, 2, K), dtype=torch.float64, device="cuda")
+            for b in range(K):
+                sc[:, 0, b] = su**b
+                sc[:, 1, b] = sx * su**b
+            parity = {"max_scaled_abs_diff_vs_fp64_kernel": float(((got - out).abs() / (out.abs() + sc[None])).max()),
+                      "over": f"{nrep_rank} replicates x {C} columns x 2 x {K} comoments, same sampler draw",
+                      "tolerance_in_tests": 1e-12}
+            del got
 
-    def fp64_block(ms, kernel, measured):
-        tf = alg_flops / (ms * 1e-3) / 1e12
-        tr, src = pmc_traffic("txm::resample_kernel", shape)
-        return {
-            "kernel": kernel, "bound": "mfma", "pipe": "fp64", "achieved": tf, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-            "frac": tf / FP64_PEAK_TFLOPS, "traffic": tr, "traffic_source": src, "ms": ms, "measured": measured,
-            "algorithmic_flops": alg_flops, "algorithmic_bytes": alg_bytes,
-            "hbm_achieved_GBs": alg_bytes / (ms * 1e-3) / 1e9, "hbm_frac": alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "note": "flops = 2*N*nrep*K*(N_obs+1) executed on v_mfma_f64_16x16x4_f64 (dense F.M, SURVEY 8(d)); fp64 "
-                    "peak 78.6 TF (vector = matrix); max attainable HBM fraction of this workload is ~1 %",
-        }
+        shape = (N, C, order, nrep_rank)
+        alg_bytes = 8.0 * N * (C + 1)                         # samples read once
+        alg_flops = 2.0 * N * nrep_rank * K * (C + 1)         # dense contraction F.M
 
-    live = "HIP events around every txm_resample_vals call of the timed steps (window pre-pass + guard list + memset + contraction + finalize)"
-    roofline_fp64 = None
-    if path == "int8":
-        # executed int8 operations (txm_resample_i8t.hip): per workgroup (8 waves x 64 replicates) and k-step of 32
-        # samples, every (column quad, power) fragment is contracted for both replicate halves (2 MFMAs) and every u-row
-        # fragment (4 monomials) for both halves.  C > 16: 8 quads per 32-column group, orders 5..7 in two passes over the
-        # sampler stream; narrow states (C <= 16): 1, 2 or 4 quads whose waves split the powers, one pass (four quads:
-        # orders 6, 7 in two)
-        if C <= 16 and K >= 2:
-            nq = 1 if C <= 4 else 2 if C <= 8 else 4
-            passes = [4, K - 4] if (nq == 4 and K >= 7) else [K]
-            what = f"narrow state, {nq} column quad(s) whose waves split the powers; "
+        def fp64_block(ms, kernel, measured):
+            tf = alg_flops / (ms * 1e-3) / 1e12
+            tr, src = pmc_traffic("txm::resample_kernel", shape)
+            return {
+                "kernel": kernel, "bound": "mfma", "pipe": "fp64", "achieved": tf, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": tf / FP64_PEAK_TFLOPS, "traffic": tr, "traffic_source": src, "ms": ms, "measured": measured,
+                "algorithmic_flops": alg_flops, "algorithmic_bytes": alg_bytes,
+                "hbm_achieved_GBs": alg_bytes / (ms * 1e-3) / 1e9, "hbm_frac": alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "note": "flops = 2*N*nrep*K*(N_obs+1) executed on v_mfma_f64_16x16x4_f64 (dense F.M, SURVEY 8(d)); fp64 "
+                        "peak 78.6 TF (vector = matrix); max attainable HBM fraction of this workload is ~1 %",
+            }
+
+        live = "HIP events around every txm_resample_vals call of the timed steps (window pre-pass + guard list + memset + contraction + finalize)"
+        roofline_fp64 = None
+        if path == "int8":
+            # executed int8 operations (txm_resample_i8t.hip): per workgroup (8 waves x 64 replicates) and k-step of 32
+            # samples, every (column quad, power) fragment is contracted for both replicate halves (2 MFMAs) and every u-row
+            # fragment (4 monomials) for both halves.  C > 16: 8 quads per 32-column group, orders 5..7 in two passes over the
+            # sampler stream; narrow states (C <= 16): 1, 2 or 4 quads whose waves split the powers, one pass (four quads:
+            # orders 6, 7 in two)
+            if C <= 16 and K >= 2:
+                nq = 1 if C <= 4 else 2 if C <= 8 else 4
+                passes = [4, K - 4] if (nq == 4 and K >= 7) else [K]
+                what = f"narrow state, {nq} column quad(s) whose waves split the powers; "
+            else:
+                nq = 8
+                passes = {1: [1], 2: [2], 3: [3], 4: [4], 5: [5], 6: [3, 3], 7: [4, 3], 8: [4, 4]}[K]
+                what = ""
+            n_mfma = sum(2 * nq * jn + 2 * -(-jn // 4) for jn in passes)
+            kname = "txm::resample_i8t_kernel"
+            kdesc = (what + "bootstrap contraction on the int8 matrix pipe: 51-bit fixed-point words sliced once per sample, "
+                     "byte-transposed by the LDS transposing read (ds_read_b64_tr_b8: 8 digit slots per word, 7 used), "
+                     "exact int32 accumulation, Philox stage 3 fused")
+            ksteps = -(-nrep_rank // 64) * (-(-N // 1024) * 32) * -(-C // 32)   # replicate groups x k-steps x column groups
+            if info.get("kernel") == "int8_table" and C <= 16:
+                # txm_resample_i8gn.hip: workgroup = 128 replicates x the state's 1, 2 or 4 column quads; per k-step 4 replicate
+                # quarters x (quads x powers + u-row fragments of four monomials) MFMAs; four quads take orders >= 4 in two passes
+                passes = [4, K - 4] if (nq == 4 and K >= 5) else [K]
+                n_mfma = sum(4 * (nq * jn + -(-jn // 4)) for jn in passes)
+                kname = "txm::resample_i8gn_kernel"
+                kdesc = (what + "bootstrap contraction on the int8 matrix pipe over a count table in HBM (txm::count_table_kernel, part of "
+                         f"the timed call): 128 replicates per workgroup, {len(passes)} pass(es), operands by LDS-DMA, two k-steps per LDS round trip")
+                ksteps = -(-nrep_rank // 128) * (-(-N // 1024) * 32)
+            elif info.get("kernel") == "int8_table":
+                # txm_resample_i8g.hip: workgroup = 128 replicates x 32 columns; per k-step 4 replicate quarters x 8 column quads
+                # per row set, the u-row in the words' dead byte (no extra MFMAs); K power row sets (+ the second matrix's) over
+                # the fewest passes of <= 3; the count table of the call generated once (txm::count_table_kernel, inside the call)
+                rows = K + (1 if dxdq is not None else 0)
+                n_mfma = 32 * rows
+                kname = "txm::resample_i8g_kernel"
+                kdesc = ("bootstrap contraction on the int8 matrix pipe over a count table in HBM (txm::count_table_kernel, part of the "
+                         f"timed call): {rows} row sets in {-(-rows // 3)} passes of <= 3, 128 replicates per workgroup, u-row in the dead "
+                         "eighth byte, operands by LDS-DMA")
+                ksteps = -(-nrep_rank // 128) * (-(-N // 1024) * 32) * -(-C // 32)
+            i8_ops = 2.0 * 32 * 32 * 32 * n_mfma * ksteps
+            tops = i8_ops / (t_boot * 1e-3) / 1e12
+            table_split = None
+            if info.get("kernel") == "int8_table":
+                # the call = count-table generator (Philox-bound: 87 vector instructions per 12 draws) + contraction passes (int8 pipe) + finalize: the generator alone,
+                # timed live on the same stream outside the timed region (txm_sampler_count_table: the launch the call makes)
+                import ctypes as _ct
+                from thermoextrap_amd import _lib as _tl
+                _L = _tl.load()
+                _tb = torch.empty(_L.txm_sampler_count_table_bytes(N, nrep_rank), dtype=torch.uint8, device="cuda")
+                def _gen():
+                    _tl.check(_L.txm_sampler_count_table(_ct.byref(sampler.spec), engine._ptr(sampler.counts), 0, nrep_rank,
+                                                         engine._ptr(_tb), engine._stream()), "count_table")
+                _gen()
+                t_gen = timed(_gen, 3)
+                del _tb
+                t_con = max(t_boot - t_gen, 1e-6)
+                table_split = {"count_table_kernel_ms": t_gen, "count_table_written_GBs": N * (-(-nrep_rank // 128) * 128) / (t_gen * 1e-3) / 1e9,
+                               "contraction_and_finalize_ms": t_con,
+                               "contraction_frac_of_int8_peak": i8_ops / (t_con * 1e-3) / 1e12 / INT8_PEAK_TOPS,
+                               "how": "generator timed alone with HIP events after the timed region; contraction = the call minus it "
+                                      "(finalize and memsets included); profiles/*_kernel_stats.csv has the rocprofv3 per-kernel durations"}
+            # HBM bytes of the timed CALL: the sum over its kernels (generator + every contraction pass + finalize ...), not one launch
+            tr, tr_kernels, src = pmc_call_traffic(shape, info.get("kernel") or "int8_fused", prepass=not info.get("prep_reused"),
+                                                   has_y=dxdq is not None)
+            if tr is None and C <= 16:  # narrow states: the counters of tools/narrow_pmc.sh (config 2's shape)
+                tr, tr_kernels, src2 = pmc_narrow_call_traffic("c2", {"states": 1, "n_samp": N, "n_obs": C, "order": order, "nrep": nrep_rank},
+                                                               info.get("kernel") or "int8_fused")
+                src = src2 or src
+            roofline = {
+                "kernel": f"{kname} ({kdesc}) + pre-pass (unless reused) and finalize kernels",
+                "bound": "mfma-i8", "pipe": "int8",
+                "achieved": tops, "peak": INT8_PEAK_TOPS, "unit": "TOP/s", "frac": tops / INT8_PEAK_TOPS,
+                "traffic": tr, "traffic_source": src,
+                "traffic_ratio": (tr / alg_bytes) if tr else None,
+                "hbm_executed_GBs": (tr / (t_boot * 1e-3) / 1e9) if tr else None,
+                "hbm_executed_frac": (tr / (t_boot * 1e-3) / 1e9 / HBM_PEAK_GBS) if tr else None,
+                "kernels": tr_kernels,
+                "traffic_note": "traffic = HBM bytes of ONE timed bootstrap call = the sum over the kernels it launches (count-table "
+                                "generator, every contraction pass, finalize, info; the pre-pass when not reused) of the per-launch "
+                                "FETCH_SIZE x2 + WRITE_SIZE figures of the committed rocprofv3 --pmc summary; kernels = the addends; "
+                                "traffic_ratio = traffic / algorithmic_bytes",
+                "ms": t_boot, "measured": live,
+                "executed_int8_ops": i8_ops,
+                "algorithmic_flops": alg_flops, "algorithmic_bytes": alg_bytes,
+                "fp64_equiv_tflops": alg_flops / (t_boot * 1e-3) / 1e12,
+                "hbm_achieved_GBs": alg_bytes / (t_boot * 1e-3) / 1e9,
+                "hbm_frac": alg_bytes / (t_boot * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "guard_windows": info["windows"], "guard_windows_fp64": info["windows_fp64"],
+                "table_call_split": table_split,
+                "note": "achieved = EXECUTED v_mfma_i32_32x32x32_i8 operations per second against the dense int8 peak "
+                        "(2x bf16 = 5 POP/s); fp64_equiv_tflops = the algorithmic FP64 flops 2*N*nrep*K*(N_obs+1) per "
+                        "second -- a speed, not a fraction of any roof.  12.5 % of the executed MFMA columns are the dead "
+                        "eighth digit slot of the 8-byte word (DESIGN.md 4.2b)",
+            }
+            if t_fp64 is not None:
+                roofline_fp64 = fp64_block(t_fp64, "txm::resample_kernel (the same shape forced onto the FP64 MFMA kernel, "
+                                           "Philox stage 3 fused)", "HIP events around 2 forced-FP64 txm_resample_vals calls after the timed region")
         else:
-            nq = 8
-            passes = {1: [1], 2: [2], 3: [3], 4: [4], 5: [5], 6: [3, 3], 7: [4, 3], 8: [4, 4]}[K]
-            what = ""
-        n_mfma = sum(2 * nq * jn + 2 * -(-jn // 4) for jn in passes)
-        kname = "txm::resample_i8t_kernel"
-        kdesc = (what + "bootstrap contraction on the int8 matrix pipe: 51-bit fixed-point words sliced once per sample, "
-                 "byte-transposed by the LDS transposing read (ds_read_b64_tr_b8: 8 digit slots per word, 7 used), "
-                 "exact int32 accumulation, Philox stage 3 fused")
-        ksteps = -(-nrep_rank // 64) * (-(-N // 1024) * 32) * -(-C // 32)   # replicate groups x k-steps x column groups
-        if info.get("kernel") == "int8_table" and C <= 16:
-            # txm_resample_i8gn.hip: workgroup = 128 replicates x the state's 1, 2 or 4 column quads; per k-step 4 replicate
-            # quarters x (quads x powers + u-row fragments of four monomials) MFMAs; four quads take orders >= 4 in two passes
-            passes = [4, K - 4] if (nq == 4 and K >= 5) else [K]
-            n_mfma = sum(4 * (nq * jn + -(-jn // 4)) for jn in passes)
-            kname = "txm::resample_i8gn_kernel"
-            kdesc = (what + "bootstrap contraction on the int8 matrix pipe over a count table in HBM (txm::count_table_kernel, part of "
-                     f"the timed call): 128 replicates per workgroup, {len(passes)} pass(es), operands by LDS-DMA, two k-steps per LDS round trip")
-            ksteps = -(-nrep_rank // 128) * (-(-N // 1024) * 32)
-        elif info.get("kernel") == "int8_table":
-            # txm_resample_i8g.hip: workgroup = 128 replicates x 32 columns; per k-step 4 replicate quarters x 8 column quads
-            # per row set, the u-row in the words' dead byte (no extra MFMAs); K power row sets (+ the second matrix's) over
-            # the fewest passes of <= 3; the count table of the call generated once (txm::count_table_kernel, inside the call)
-            rows = K + (1 if dxdq is not None else 0)
-            n_mfma = 32 * rows
-            kname = "txm::resample_i8g_kernel"
-            kdesc = ("bootstrap contraction on the int8 matrix pipe over a count table in HBM (txm::count_table_kernel, part of the "
-                     f"timed call): {rows} row sets in {-(-rows // 3)} passes of <= 3, 128 replicates per workgroup, u-row in the dead "
-                     "eighth byte, operands by LDS-DMA")
-            ksteps = -(-nrep_rank // 128) * (-(-N // 1024) * 32) * -(-C // 32)
-        i8_ops = 2.0 * 32 * 32 * 32 * n_mfma * ksteps
-        tops = i8_ops / (t_boot * 1e-3) / 1e12
-        table_split = None
-        if info.get("kernel") == "int8_table":
-            # the call = count-table generator (Philox-bound: 87 vector instructions per 12 draws) + contraction passes (int8 pipe) + finalize: the generator alone,
-            # timed live on the same stream outside the timed region (txm_sampler_count_table: the launch the call makes)
-            import ctypes as _ct
-            from thermoextrap_amd import _lib as _tl
-            _L = _tl.load()
-            _tb = torch.empty(_L.txm_sampler_count_table_bytes(N, nrep_rank), dtype=torch.uint8, device="cuda")
-            def _gen():
-                _tl.check(_L.txm_sampler_count_table(_ct.byref(sampler.spec), engine._ptr(sampler.counts), 0, nrep_rank,
-                                                     engine._ptr(_tb), engine._stream()), "count_table")
-            _gen()
-            t_gen = timed(_gen, 3)
-            del _tb
-            t_con = max(t_boot - t_gen, 1e-6)
-            table_split = {"count_table_kernel_ms": t_gen, "count_table_written_GBs": N * (-(-nrep_rank // 128) * 128) / (t_gen * 1e-3) / 1e9,
-                           "contraction_and_finalize_ms": t_con,
-                           "contraction_frac_of_int8_peak": i8_ops / (t_con * 1e-3) / 1e12 / INT8_PEAK_TOPS,
-                           "how": "generator timed alone with HIP events after the timed region; contraction = the call minus it "
-                                  "(finalize and memsets included); profiles/*_kernel_stats.csv has the rocprofv3 per-kernel durations"}
-        # HBM bytes of the timed CALL: the sum over its kernels (generator + every contraction pass + finalize ...), not one launch
-        tr, tr_kernels, src = pmc_call_traffic(shape, info.get("kernel") or "int8_fused", prepass=not info.get("prep_reused"),
-                                               has_y=dxdq is not None)
-        if tr is None and C <= 16:  # narrow states: the counters of tools/narrow_pmc.sh (config 2's shape)
-            tr, tr_kernels, src2 = pmc_narrow_call_traffic("c2", {"states": 1, "n_samp": N, "n_obs": C, "order": order, "nrep": nrep_rank},
-                                                           info.get("kernel") or "int8_fused")
-            src = src2 or src
-        roofline = {
-            "kernel": f"{kname} ({kdesc}) + pre-pass (unless reused) and finalize kernels",
-            "bound": "mfma-i8", "pipe": "int8",
-            "achieved": tops, "peak": INT8_PEAK_TOPS, "unit": "TOP/s", "frac": tops / INT8_PEAK_TOPS,
+            roofline = fp64_block(t_boot, "txm::resample_kernel (FP64 MFMA bootstrap contraction, Philox stage 3 fused)", live)
+        roofline["path"] = path
+        tr, src = pmc_traffic("txm::reduce_rowmajor_kernel", shape)
+        roofline_reduce = {
+            "kernel": "txm::reduce_rowmajor_kernel (one-pass power-sum reduction, the HBM-bound leg of the path)",
+            "bound": "hbm",
+            "achieved": alg_bytes / (t_red * 1e-3) / 1e9,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": alg_bytes / (t_red * 1e-3) / 1e9 / HBM_PEAK_GBS,
             "traffic": tr, "traffic_source": src,
-            "traffic_ratio": (tr / alg_bytes) if tr else None,
-            "hbm_executed_GBs": (tr / (t_boot * 1e-3) / 1e9) if tr else None,
-            "hbm_executed_frac": (tr / (t_boot * 1e-3) / 1e9 / HBM_PEAK_GBS) if tr else None,
-            "kernels": tr_kernels,
-            "traffic_note": "traffic = HBM bytes of ONE timed bootstrap call = the sum over the kernels it launches (count-table "
-                            "generator, every contraction pass, finalize, info; the pre-pass when not reused) of the per-launch "
-                            "FETCH_SIZE x2 + WRITE_SIZE figures of the committed rocprofv3 --pmc summary; kernels = the addends; "
-                            "traffic_ratio = traffic / algorithmic_bytes",
-            "ms": t_boot, "measured": live,
-            "executed_int8_ops": i8_ops,
-            "algorithmic_flops": alg_flops, "algorithmic_bytes": alg_bytes,
-            "fp64_equiv_tflops": alg_flops / (t_boot * 1e-3) / 1e12,
-            "hbm_achieved_GBs": alg_bytes / (t_boot * 1e-3) / 1e9,
-            "hbm_frac": alg_bytes / (t_boot * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "guard_windows": info["windows"], "guard_windows_fp64": info["windows_fp64"],
-            "table_call_split": table_split,
-            "note": "achieved = EXECUTED v_mfma_i32_32x32x32_i8 operations per second against the dense int8 peak "
-                    "(2x bf16 = 5 POP/s); fp64_equiv_tflops = the algorithmic FP64 flops 2*N*nrep*K*(N_obs+1) per "
-                    "second -- a speed, not a fraction of any roof.  12.5 % of the executed MFMA columns are the dead "
-                    "eighth digit slot of the 8-byte word (DESIGN.md 4.2b)",
+            "algorithmic_bytes": alg_bytes,
+            "ms": t_red,
+            "samples_per_s": N / (t_red * 1e-3),
         }
-        if t_fp64 is not None:
-            roofline_fp64 = fp64_block(t_fp64, "txm::resample_kernel (the same shape forced onto the FP64 MFMA kernel, "
-                                       "Philox stage 3 fused)", "HIP events around 2 forced-FP64 txm_resample_vals calls after the timed region")
-    else:
-        roofline = fp64_block(t_boot, "txm::resample_kernel (FP64 MFMA bootstrap contraction, Philox stage 3 fused)", live)
-    roofline["path"] = path
-    tr, src = pmc_traffic("txm::reduce_rowmajor_kernel", shape)
-    roofline_reduce = {
-        "kernel": "txm::reduce_rowmajor_kernel (one-pass power-sum reduction, the HBM-bound leg of the path)",
-        "bound": "hbm",
-        "achieved": alg_bytes / (t_red * 1e-3) / 1e9,
-        "peak": HBM_PEAK_GBS,
-        "unit": "GB/s",
-        "frac": alg_bytes / (t_red * 1e-3) / 1e9 / HBM_PEAK_GBS,
-        "traffic": tr, "traffic_source": src,
-        "algorithmic_bytes": alg_bytes,
-        "ms": t_red,
-        "samples_per_s": N / (t_red * 1e-3),
-    }
 
     ranks_seen = ranks_identity(torch, dist, world)
     # what every rank ran (the first SCALE record can be held against DESIGN 6's prediction rank by rank): its replicate slab
@@ -721,16 +771,17 @@ def main():
             "replicate_samples_per_s": value * nrep,
             "ranks_seen": ranks_seen,
             "per_rank": per_rank,
-            "sampler_ms": t_samp,
-            "roofline": roofline,
-            "roofline_reduce": roofline_reduce,
         }
+        if args.full:
+            rec["sampler_ms"] = t_samp
+            rec["roofline"] = roofline
+            rec["roofline_reduce"] = roofline_reduce
         if roofline_fp64 is not None:
             rec["roofline_fp64_path"] = roofline_fp64
         if parity is not None:
             rec["parity_check"] = parity
         rec["step_breakdown_ms"] = step_breakdown
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the reference's parallelism is over observables only (cmomy's numba threads span broadcast dims, never the sample
             # axis: SURVEY 8(d)) -- effective cores = min(N_obs, host cores)
             nthr = args.cpu_threads or min(os.cpu_count() or 1, C)

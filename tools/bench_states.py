@@ -10,7 +10,8 @@ c5  64 state points (N = 1e6 samples x 4 observables each), order 3, nrep = 100:
 Under torch.distributed.run (bench.py --config c3|c5 --gpus N) the STATE POINTS shard over the ranks: rank r builds and
 bootstraps only its contiguous share, one all-gather of the per-state blocks ends a step
 (input_GP_from_states(sharded="local")).  Prints one JSON line in bench.py's format (samples/s = states x N_samp /
-step time, max over ranks) and exits non-zero when two nccl ranks report the same device."""
+step time, max over ranks) and exits non-zero when two nccl ranks report the same device.  The kernel roofline (c3, c5) and
+the serial loop over the states (c5) take runs of their own after the timed steps: bench.py --full only."""
 from __future__ import annotations
 
 import json
@@ -109,8 +110,11 @@ def main(args):
 
         dt = _timed_steps(torch, dist, world, step, args.warmup, args.steps)
         assert out["v"].shape[0] == S, out["v"].shape
-        t_k = _timed_events(torch, lambda: engine.reduce_vals_1d(u, order + 1), 10)
-        alg = 8.0 * len(mine) * N
+        if args.dump_outputs and rank == 0:
+            bench.dump_outputs(args.dump_outputs, {"moments": out["v"]})     # (state, xmom, umom) of the last timed step
+        if args.full:
+            t_k = _timed_events(torch, lambda: engine.reduce_vals_1d(u, order + 1), 10)
+            alg = 8.0 * len(mine) * N
         if rank == 0:
             rec = {
                 "metric": "samples/s for order-4 central moments of 16 state points (x_is_u reduction)",
@@ -120,11 +124,12 @@ def main(args):
                 "config": {"workload": f"c3: {S} states x N_samp={N:.0e} potential-energy series, x_is_u, order {order}, one batched launch per rank",
                            "states": S, "n_samp": N, "order": order, "parallelism": par, "states_per_rank": counts},
                 "ranks_seen": ranks_seen,
-                "roofline": {"kernel": "txm::reduce_colmajor_kernel (1-D pivot-shifted power sums, all states of the rank in one launch) + pivot + finalize",
-                             "bound": "hbm", "achieved": alg / (t_k * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": alg / (t_k * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None, "ms": t_k, "algorithmic_bytes": alg,
-                             "measured": "HIP events around 10 txm_reduce_vals_1d calls (rank 0's states)"},
             }
+            if args.full:
+                rec["roofline"] = {"kernel": "txm::reduce_colmajor_kernel (1-D pivot-shifted power sums, all states of the rank in one launch) + pivot + finalize",
+                                   "bound": "hbm", "achieved": alg / (t_k * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                   "frac": alg / (t_k * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None, "ms": t_k, "algorithmic_bytes": alg,
+                                   "measured": "HIP events around 10 txm_reduce_vals_1d calls (rank 0's states)"}
             print(json.dumps(rec), flush=True)
         if world > 1:
             dist.destroy_process_group()
@@ -156,6 +161,15 @@ def main(args):
 
     dt = _timed_steps(torch, dist, world, step, args.warmup, args.steps)
     assert keep["gp"][1].shape == (S * (order + 1), C), keep["gp"][1].shape
+    if args.dump_outputs and rank == 0:
+        # the data_input tuple of the last timed step: GP inputs (alpha, derivative order), derivatives, covariances
+        bench.dump_outputs(args.dump_outputs, dict(zip(("gp_x", "gp_y", "gp_cov"), keep["gp"])))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(_c5_record(args, S, N, C, order, nrep, world, dt, par, counts, ranks_seen)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     dts = None
     if world == 1:
         serial(0)
@@ -176,24 +190,28 @@ def main(args):
     K = order + 1
     flops = 2.0 * S_loc * N * nrep * K * (C + 1)
     if rank == 0:
-        rec = {
-            "metric": "samples/s for 64-state GP input (order-3 derivatives + covariance over 100 bootstrap replicates)",
-            "value": S * N / dt, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"c5: {S} states x N_samp={N:.0e} x N_obs={C}, order {order}, nrep={nrep}: input_GP_from_states "
-                                   "(batched bootstrap + derivatives + covariance over replicates)",
-                       "states": S, "n_samp": N, "n_obs": C, "order": order, "nrep": nrep, "parallelism": par,
-                       "states_per_rank": counts},
-            "ranks_seen": ranks_seen,
-            "roofline": _c5_roofline(info, flops, t_k, S_loc, N, C, K, nrep),
-        }
+        rec = _c5_record(args, S, N, C, order, nrep, world, dt, par, counts, ranks_seen)
+        rec["roofline"] = _c5_roofline(info, flops, t_k, S_loc, N, C, K, nrep)
         if dts is not None:
             rec["serial_loop_ms_per_step"] = 1e3 * dts
             rec["speedup_vs_serial_loop"] = dts / dt
         print(json.dumps(rec), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def _c5_record(args, S, N, C, order, nrep, world, dt, par, counts, ranks_seen):
+    return {
+        "metric": "samples/s for 64-state GP input (order-3 derivatives + covariance over 100 bootstrap replicates)",
+        "value": S * N / dt, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"c5: {S} states x N_samp={N:.0e} x N_obs={C}, order {order}, nrep={nrep}: input_GP_from_states "
+                               "(batched bootstrap + derivatives + covariance over replicates)",
+                   "states": S, "n_samp": N, "n_obs": C, "order": order, "nrep": nrep, "parallelism": par,
+                   "states_per_rank": counts},
+        "ranks_seen": ranks_seen,
+    }
 
 
 def _c5_roofline(info, flops, t_k, S, N, C, K, nrep):

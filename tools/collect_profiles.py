@@ -68,7 +68,7 @@ sys.path.insert(0, str(root))
 from bench import csrc_sha  # noqa: E402
 
 json.dump({"tag": tag, "workload": workload, "csrc_sha": csrc_sha(),
-           "command": "python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline (one rocprofv3 --pmc pass per counter)",
+           "command": "python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline (one rocprofv3 --pmc pass per counter)",
            "note": "FETCH_SIZE x2 correction per MI355X_MICROARCH.md (calibrated for 16 B/lane streams; "
            "the bootstrap kernel's 8 B/lane x loads are uncalibrated, so its figure is an upper bound)",
            "kernels": traffic}, open(out / f"{tag}_traffic.json", "w"), indent=1)

@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 TAG=${1:-r01b}
-CMD="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+CMD="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
 rm -rf gpurun_out/${TAG}_trace gpurun_out/${TAG}_pmc_fetch gpurun_out/${TAG}_pmc_write
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_trace --output-format csv -- $CMD > gpurun_out/${TAG}_trace.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/${TAG}_pmc_fetch --output-format csv -- $CMD > gpurun_out/${TAG}_pmc_fetch.log 2>&1 || exit 1

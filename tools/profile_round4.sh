@@ -8,9 +8,9 @@ cd "$(dirname "$0")/.."
 TAG=${1:-r04a}
 mkdir -p gpurun_out
 bash tools/profile_round.sh $TAG || echo "profile_round failed"
-python3 bench.py --steps 10 --warmup 2 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit 1
+python3 bench.py --full --steps 10 --warmup 2 > profiles/${TAG}_bench.json || exit 1
 for c in c2 c4 c3 c5; do
-  python3 bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline > gpurun_out/${TAG}_bench_$c.json 2>> gpurun_out/${TAG}_bench.err || echo "bench $c failed"
+  python3 bench.py --full --config $c --steps 5 --warmup 1 --no-cpu-baseline > profiles/${TAG}_bench_$c.json || echo "bench $c failed"
 done
 PMC_TAG=${TAG}_pmc_i8t PMC_N=1e8 PMC_NREP=1000 bash tools/i8_pmc.sh 1e8 1000 > gpurun_out/${TAG}_pmc.log 2>&1 || echo "pmc failed"
 timeout -k 10 600 python3 tools/profile_shapes.py 1e8 > gpurun_out/${TAG}_shapes.jsonl 2> gpurun_out/${TAG}_shapes.err || echo "shapes failed"

@@ -24,9 +24,9 @@ if fs:
             w.writerow([r["Name"].replace("void ", "").split("(")[0], r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["MinNs"], r["MaxNs"], r["Percentage"]])
     print(open(f"profiles/{tag}_c4_kernel_stats.csv").read())
 PY
-python3 bench.py --steps 10 --warmup 2 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit 1
+python3 bench.py --full --steps 10 --warmup 2 > profiles/${TAG}_bench.json || exit 1
 for c in c2 c4 c3 c5; do
-  python3 bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline > gpurun_out/${TAG}_bench_$c.json 2>> gpurun_out/${TAG}_bench.err || echo "bench $c failed"
+  python3 bench.py --full --config $c --steps 5 --warmup 1 --no-cpu-baseline > profiles/${TAG}_bench_$c.json || echo "bench $c failed"
 done
 # (every wide order runs the table kernel by rule now; the fused kernel's counters: a 125-replicate slab of the north star, which it keeps)
 PMC_ORDER=${PMC_ORDER_FUSED:-4} PMC_TAG=${TAG}_pmc_i8t PMC_N=1e8 PMC_NREP=125 bash tools/i8_pmc.sh 1e8 125 > gpurun_out/${TAG}_pmc.log 2>&1 || echo "pmc failed"

@@ -26,9 +26,9 @@ PY
 # narrow states: SQ counters of the contraction launches and FETCH / WRITE of every kernel of the call (configs 2 and 5) -- before the
 # bench lines, which read the call's traffic from the summary
 bash tools/narrow_pmc.sh ${TAG}_pmc_narrow > gpurun_out/${TAG}_pmc_narrow.log 2>&1 || echo "narrow pmc failed"
-python3 bench.py --steps 10 --warmup 2 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit 1
+python3 bench.py --full --steps 10 --warmup 2 > profiles/${TAG}_bench.json || exit 1
 for c in c2 c4 c3 c5; do
-  python3 bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline > gpurun_out/${TAG}_bench_$c.json 2>> gpurun_out/${TAG}_bench.err || echo "bench $c failed"
+  python3 bench.py --full --config $c --steps 10 --warmup 2 --no-cpu-baseline > profiles/${TAG}_bench_$c.json || echo "bench $c failed"
 done
 # config 4's FETCH / WRITE passes and its bench line again, now with the call's traffic (three passes over one table + the second matrix)
 bash tools/profile_c4_traffic.sh $TAG > gpurun_out/${TAG}_c4_traffic.log 2>&1 || echo "c4 traffic failed"
