@@ -24,12 +24,19 @@ def eng(txm):
     return engine
 
 
-def data(N, C, seed, heavy=False):
+def data(N, C, seed, heavy=False, bounded=False):
+    """bounded: uniform noise of the same spread in place of the Gaussian (no window's maximum is far above its typical size,
+    so the precision guard flags nothing at any order -- test_guard_gpu.py puts its outliers into such data)"""
     g = torch.Generator(device="cuda").manual_seed(seed)
-    u = 174.85 + 5.31 * torch.randn(N, generator=g, dtype=torch.float64, device="cuda")
+
+    def noise(*shape):
+        if bounded:
+            return 3.0 ** 0.5 * (2.0 * torch.rand(*shape, generator=g, dtype=torch.float64, device="cuda") - 1.0)
+        return torch.randn(*shape, generator=g, dtype=torch.float64, device="cuda")
+
+    u = 174.85 + 5.31 * noise(N)
     a = torch.linspace(-1.0, 1.0, C, dtype=torch.float64, device="cuda")
-    x = 3.0 + a[None, :] * 0.7 + (0.01 + 0.003 * a[None, :]) * u[:, None] \
-        + 0.4 * torch.randn(N, C, generator=g, dtype=torch.float64, device="cuda")
+    x = 3.0 + a[None, :] * 0.7 + (0.01 + 0.003 * a[None, :]) * u[:, None] + 0.4 * noise(N, C)
     if heavy:  # outliers: one window sees values 1e4 x the spread
         x[N // 3] += 4.0e3
         u[N // 2] += 5.0e4

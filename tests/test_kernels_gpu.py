@@ -345,6 +345,47 @@ def test_resample_vals_narrow_states_packed_powers(eng, orc, C, order, weighted)
     assert_states_close(got, got2, scale, rtol=1e-13, what="packed vs one power per column")
 
 
+@pytest.mark.parametrize("C", [33, 64])
+@pytest.mark.parametrize("mode", ["sampler", "explicit"])
+@pytest.mark.parametrize("weighted", [False, True])
+def test_resample_vals_order8_two_column_blocks(eng, orc, C, mode, weighted):
+    """resample_kernel<K = 9, NBLK = 2>: order 8 with more than 16 observables (two 16-column blocks per workgroup), in scale
+    mode and on explicit frequencies -- the FP64 kernel is the only one of order 8 and the reference of every int8 test."""
+    N, nrep, order = 3000, 9, 8
+    rng = np.random.default_rng(8000 + C)
+    x, u = make_data(rng, N, C)
+    w = rng.uniform(0.2, 3.0, N) if weighted else None
+    wd = None if w is None else dev(w)
+    if mode == "sampler":
+        s = eng.DeviceSampler(88 + C, nrep, N)
+        got = eng.resample_vals(dev(x), dev(u), order, sampler=s, w=wd).cpu().numpy()
+        freq = s.freq().cpu().numpy()
+    else:
+        freq = orc.indices_to_freq(rng.choice(N, (nrep, N)), N)
+        got = eng.resample_vals(dev(x), dev(u), order, freq=dev(freq, torch.int64), w=wd).cpu().numpy()
+    assert eng.resample_info()["path"] == "fp64"
+    truth = np.stack([orc.truth_cov(x, u, order, w=w, freq_row=freq[r]) for r in range(nrep)])
+    assert_states_close(got, truth, moment_scale(x, u, order)[None], what=f"order 8, C = {C}, {mode}")
+
+
+@pytest.mark.parametrize("order", [5, 6, 7, 8])
+@pytest.mark.parametrize("C", [1, 17])
+def test_resample_vals_device_sampler_below_one_tile(eng, orc, order, C):
+    """Scale mode with N < one sampler tile (the SMALLN instances of resample_kernel) at the high orders, one and two
+    column blocks, weights on every other order."""
+    N, nrep = 777, 21
+    rng = np.random.default_rng(700 + 10 * order + C)
+    x, u = make_data(rng, N, C)
+    w = rng.uniform(0.2, 3.0, N) if order % 2 else None
+    s = eng.DeviceSampler(5 + order, nrep, N)
+    got = eng.resample_vals(dev(x), dev(u), order, sampler=s, w=None if w is None else dev(w)).cpu().numpy()
+    assert eng.resample_info()["path"] == "fp64"
+    freq = s.freq().cpu().numpy()
+    assert np.array_equal(freq, orc.sampler_freq(5 + order, nrep, N))
+    truth = np.stack([orc.truth_cov(x, u, order, w=w, freq_row=freq[r]) for r in range(nrep)])
+    assert_states_close(got, truth, moment_scale(x, u, order)[None], what=f"N < 1024, order {order}, C = {C}")
+
+
 def test_resample_user_pivot(eng, orc):
     rng = np.random.default_rng(2)
     x, u = make_data(rng, 2000, 4)
