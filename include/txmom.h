@@ -450,6 +450,41 @@ int txm_perturb(const double *x, int64_t ldx_s, const double *u, int64_t N, int6
                 const double *dalpha_host, int32_t n_alpha, const int64_t *freq, int64_t nrep,
                 double *out, void *ws, size_t ws_bytes, txm_stream stream);
 
+/* ---- (f-5) MBARModel: free energies and reweighted averages over K states --------- */
+/* K states (1 <= K <= 64) at alpha0[k], each a sample set (x [n][ldx_s], u [n]); samples are pooled
+ * in state order (pooled index = n_0 + ... + n_{s-1} + i) without being copied.  The kernels see u only
+ * as ut = u - upiv (one host-chosen pivot, e.g. the pooled mean) and the free energies f only as the
+ * shifted log-weights g[k] = ln N_k + f[k] - alpha0[k] * upiv (+ any constant shared by all k):
+ *   p[k][n]  = softmax_k(g[k] - alpha0[k] ut_n)            (max subtracted: no positive exponent)
+ *   logD[n]  = ln sum_k e^{g[k] - alpha0[k] ut_n}           (the MBAR log-denominator + that constant)
+ * replaces MBARModel._default_params / predict (reference models.py:1049-1111: pymbar.MBAR(u_kn, N_k)
+ * on u_kn = alpha0_k u_n, then compute_multiple_expectations(x, a * u)["mu"]).
+ * `states_host` is a HOST array of K entries; it is copied into the workspace by the call (not
+ * stream-capturable).  ws: txm_mbar_ws_bytes(K, C, n_alpha) serves an evaluation and a predict of
+ * (C, n_alpha); an evaluation alone needs txm_mbar_ws_bytes(K, 1, 1).  All sums are combined in a
+ * fixed order: bitwise reproducible run to run. */
+typedef struct txm_mbar_state {
+  const double *x; /* [n][ldx_s]; may be NULL for txm_mbar_eval */
+  const double *u; /* [n] */
+  int64_t n;       /* samples of this state, >= 1 */
+  int64_t ldx_s;   /* row pitch of x in elements (>= C) */
+} txm_mbar_state;
+size_t txm_mbar_ws_bytes(int32_t K, int64_t C, int32_t n_alpha);
+/* One evaluation pass over u for the log-weights g_host [K] (host), alpha0_host [K] (host):
+ *   out [K + K(K+1)/2 + 1] (device) = S[k] = sum_n p[k][n]  (the objective's gradient is S - N),
+ *     H[j][k] = sum_n p[j][n] p[k][n] for j <= k (row-major upper triangle), sum_n logD[n];
+ *   logD (nullable, device [sum n]) receives logD[n] of every pooled sample. */
+int txm_mbar_eval(const txm_mbar_state *states_host, int32_t K, const double *alpha0_host,
+                  const double *g_host, double upiv, double *out, double *logD, void *ws,
+                  size_t ws_bytes, txm_stream stream);
+/* Reweighted averages for n_alpha <= 8 targets alpha_host (host):
+ *   out[a][c] = sum_n x[n][c] e^{-alpha[a] ut_n - logD[n]} / sum_n e^{-alpha[a] ut_n - logD[n]}
+ * (out [n_alpha][C], device) with the logD a txm_mbar_eval of the same states and upiv stored; the
+ * largest exponent of every target is made exactly 0 by a max pass. */
+int txm_mbar_predict(const txm_mbar_state *states_host, int32_t K, int64_t C, double upiv,
+                     const double *logD, const double *alpha_host, int32_t n_alpha, double *out,
+                     void *ws, size_t ws_bytes, txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ Layout
   moments.py   mirror of the cmomy calls thermoextrap makes (the reference's boundary)
   data.py      DataCentralMoments, DataCentralMomentsVals, DataValues(Central), ...
   symbolic.py  derivative recursion as exact polynomials -> device tables
-  models.py    Derivatives, ExtrapModel, StateCollection
+  models.py    Derivatives, ExtrapModel, StateCollection, the multi-state models (InterpModel, MBARModel, ...)
   beta.py      factory_derivatives, factory_extrapmodel
 """
 
@@ -19,7 +19,7 @@ _LAZY = {
     "DataValuesCentral": "data", "DataCallback": "data", "DataCallbackABC": "data", "DataSelector": "data",
     "factory_data_values": "data", "xrwrap_uv": "data", "xrwrap_xv": "data", "xrwrap_alpha": "data",
     "Derivatives": "models", "ExtrapModel": "models", "StateCollection": "models", "PerturbModel": "models",
-    "ExtrapWeightedModel": "models", "InterpModel": "models", "InterpModelPiecewise": "models",
+    "ExtrapWeightedModel": "models", "InterpModel": "models", "InterpModelPiecewise": "models", "MBARModel": "models",
     "DataArray": "xrlite", "Dataset": "xrlite",
 }
 _MODULES = {"stack", "distributed", "gpr_input", "beta", "data", "models", "moments", "idealgas", "symbolic", "engine", "xrlite", "volume", "volume_idealgas", "lnpi"}

@@ -35,6 +35,12 @@ class StatePtrs(ct.Structure):
     _fields_ = [("x", c_void_p), ("u", c_void_p), ("w", c_void_p)]
 
 
+class MbarState(ct.Structure):
+    """txm_mbar_state (include/txmom.h): one state's samples for the MBAR entry points."""
+
+    _fields_ = [("x", c_void_p), ("u", c_void_p), ("n", c_i64), ("ldx_s", c_i64)]
+
+
 class Atom(ct.Structure):
     _fields_ = [("src", ct.c_int32), ("pad", ct.c_int32), ("offset", c_i64), ("s_rep", c_i64), ("s_val", c_i64)]
 
@@ -118,6 +124,11 @@ SIGNATURES = {
     "txm_perturb_ws_bytes": (c_size, [c_i64, c_i64, ct.c_int32, c_i64]),
     "txm_perturb": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, ct.POINTER(ct.c_double), ct.c_int32, c_void_p,
                             c_i64, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_mbar_ws_bytes": (c_size, [ct.c_int32, c_i64, ct.c_int32]),
+    "txm_mbar_eval": (c_int, [ct.POINTER(MbarState), ct.c_int32, ct.POINTER(ct.c_double), ct.POINTER(ct.c_double),
+                              ct.c_double, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_mbar_predict": (c_int, [ct.POINTER(MbarState), ct.c_int32, c_i64, ct.c_double, c_void_p, ct.POINTER(ct.c_double),
+                                 ct.c_int32, c_void_p, c_void_p, c_size, c_void_p]),
 }
 
 ABI_VERSION = 2  # include/txmom.h TXM_ABI_VERSION

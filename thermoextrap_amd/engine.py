@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as ct
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -862,3 +863,234 @@ def perturb(x: torch.Tensor, u: torch.Tensor, dalphas, freq: torch.Tensor | None
     if freq is None:
         res = res[0]
     return res[..., 0] if squeeze else res
+
+
+# ---------------------------------------------------------------------------
+# MBAR (MBARModel; reference models.py:1049-1111, which wraps pymbar)
+# ---------------------------------------------------------------------------
+class MbarSolution(NamedTuple):
+    """What ``mbar_solve`` returns: the free energies ``f`` (gauge f_0 = 0), the device buffer ``logD`` of the pooled
+    samples' log-denominators stored by the last evaluation, the pivot ``upiv`` it was computed with (``mbar_predict``
+    must use the same one), and how the solve went."""
+
+    f: np.ndarray
+    logD: torch.Tensor
+    upiv: float
+    iterations: int
+    evaluations: int
+    gradient: float
+
+
+def _mbar_table(us, xs=None):
+    """The host table of txm_mbar_state entries for K states (x may be omitted for the evaluation), the tensors it
+    points into (keep them alive over the call), the per-state sample counts and C."""
+    K = len(us)
+    if not 1 <= K <= 64:
+        raise ValueError(f"MBAR needs 1 <= K <= 64 states, got {K}")
+    if xs is not None and len(xs) != K:
+        raise ValueError("need one x per u")
+    u2, x2, ns, C = [], [], [], 1
+    for s in range(K):
+        u = us[s]
+        _check_f64_cuda(u, "u")
+        if u.dim() != 1 or u.shape[0] < 1:
+            raise ValueError("every u must be (n,) with n >= 1")
+        u2.append(u.contiguous())
+        ns.append(u.shape[0])
+        if xs is not None:
+            x = xs[s]
+            _check_f64_cuda(x, "x")
+            x = x.unsqueeze(1) if x.dim() == 1 else x
+            if x.dim() != 2 or x.shape[0] != u.shape[0]:
+                raise ValueError(f"x of state {s} must be ({u.shape[0]},) or ({u.shape[0]}, C)")
+            if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+                x = x.contiguous()
+            if s == 0:
+                C = x.shape[1]
+            elif x.shape[1] != C:
+                raise ValueError("every state's x must have the same number of columns")
+            x2.append(x)
+    tab = (_lib.MbarState * K)()
+    for s in range(K):
+        tab[s].u = u2[s].data_ptr()
+        tab[s].n = ns[s]
+        if xs is not None:
+            tab[s].x = x2[s].data_ptr()
+            tab[s].ldx_s = max(x2[s].stride(0), C) if ns[s] > 1 else C
+    return tab, (u2, x2), np.asarray(ns, dtype=np.float64), C
+
+
+def mbar_pivot(us) -> float:
+    """The pivot the MBAR kernels subtract from u: the pooled mean (torch's sum, a deterministic reduction)."""
+    tot = sum(float(u.sum()) for u in us)
+    return tot / sum(u.shape[0] for u in us)
+
+
+def mbar_eval(us, alpha0, g, upiv: float, logD: torch.Tensor | None = None):
+    """One device evaluation pass (txm_mbar_eval) at the shifted log-weights ``g``: (S (K,), H (K, K) symmetric, objective),
+    copied to the host; ``logD`` (float64 CUDA, pooled length) receives the per-sample log-denominators."""
+    L = _L()
+    tab, keep, ns, _ = _mbar_table(us)
+    K = len(us)
+    a0 = np.ascontiguousarray(alpha0, dtype=np.float64)
+    gg = np.ascontiguousarray(g, dtype=np.float64)
+    if a0.shape != (K,) or gg.shape != (K,):
+        raise ValueError("alpha0 and g need one entry per state")
+    if logD is not None:
+        _check_f64_cuda(logD, "logD")
+        if logD.shape != (int(ns.sum()),) or not logD.is_contiguous():
+            raise ValueError("logD must be a contiguous (sum n,) tensor")
+    nh = K * (K + 1) // 2
+    out = torch.empty(K + nh + 1, dtype=F64, device="cuda")
+    ws = workspace(L.txm_mbar_ws_bytes(K, 1, 1), tag="mbar")
+    dp = ct.POINTER(ct.c_double)
+    check(L.txm_mbar_eval(tab, K, a0.ctypes.data_as(dp), gg.ctypes.data_as(dp), float(upiv), _ptr(out), _ptr(logD), _ptr(ws),
+                          ws.numel(), _stream()), "txm_mbar_eval")
+    v = out.cpu().numpy()
+    del keep
+    H = np.zeros((K, K))
+    H[np.triu_indices(K)] = v[K:K + nh]
+    H = H + np.triu(H, 1).T
+    return v[:K].copy(), H, float(v[K + nh])
+
+
+_MBAR_MAX_STEP = 50.0   # cap (in units of f) on the part of a step along directions without curvature
+
+
+def mbar_newton(evaluate, N, b, *, f0=None, tol: float = 1e-12, max_iter: int = 100):
+    """Damped Newton on the convex MBAR objective  F(f) = sum_n logD_n(f) - sum_k N_k f_k  over the K - 1 free energies
+    f_1.. (gauge f_0 = 0).  ``evaluate(g) -> (S, H, obj)`` is one pass over the pooled samples at the log-weights
+    g = b + f + c (b_k = ln N_k - alpha0_k upiv; the constant c = -max_k(b + f) keeps them near 0): S_k = sum_n p_kn,
+    H_jk = sum_n p_jn p_kn (full symmetric) and obj = sum_n logD_n + c N_tot.  The gradient is S - N and the Hessian
+    diag(S) - H.
+
+    The reduced Hessian is eigen-decomposed: directions with curvature above 1e-12 of the largest get the Newton step;
+    the rest (states without overlap) get the gradient over that floor, capped at 50 units of f, so a singular Hessian
+    still gives a finite step.  The step is halved until the objective decreases (Armijo), or -- once the change is
+    below the objective's rounding -- until the gradient does.  Converged: max_k |S_k - N_k| / N_k <= tol.
+
+    Returns (f, g, iterations, evaluations, gradient) with g the log-weights of the last evaluation (the returned f)."""
+    N = np.asarray(N, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    K = len(N)
+    Ntot = float(N.sum())
+    f = np.zeros(K) if f0 is None else np.asarray(f0, dtype=np.float64) - float(f0[0])
+    eps = np.finfo(np.float64).eps
+
+    def point(f):
+        g = b + f
+        c = -float(g.max())
+        g = g + c
+        S, H, obj = evaluate(g)
+        S, H = np.asarray(S, dtype=np.float64), np.asarray(H, dtype=np.float64)
+        F = obj - c * Ntot - float(N @ f)
+        rnd = 64 * eps * (abs(obj) + abs(c) * Ntot + float(N @ np.abs(f)) + Ntot)
+        return S, H, F, rnd, g
+
+    S, H, F, rnd, g = point(f)
+    n_eval = 1
+    for it in range(max_iter + 1):
+        grad = S - N
+        err = float(np.max(np.abs(grad) / N))
+        if not np.isfinite(err):
+            raise _lib.TxmError(f"MBAR solve: the gradient is not finite (max |S_k - N_k| / N_k = {err})")
+        if err <= tol:
+            return f, g, it, n_eval, err
+        if it == max_iter:
+            break
+        Hr = (np.diag(S) - H)[1:, 1:]
+        gr = grad[1:]
+        lam, V = np.linalg.eigh(0.5 * (Hr + Hr.T))
+        floor = 1e-12 * max(float(lam.max()), float(N.min()))
+        good = lam > floor
+        proj = V.T @ gr
+        step = -(V[:, good] @ (proj[good] / lam[good]))
+        if not good.all():
+            flat = -(V[:, ~good] @ (proj[~good] / floor))
+            big = float(np.max(np.abs(flat)))
+            if big > _MBAR_MAX_STEP:
+                flat *= _MBAR_MAX_STEP / big
+            step = step + flat
+        slope = float(gr @ step)
+        t = 1.0
+        while True:
+            fn = f.copy()
+            fn[1:] += t * step
+            Sn, Hn, Fn, rn, gn = point(fn)
+            n_eval += 1
+            errn = float(np.max(np.abs(Sn - N) / N))
+            if Fn <= F + 1e-4 * t * slope or (abs(Fn - F) <= max(rnd, rn) and errn < err):
+                break
+            t *= 0.5
+            if t < 1e-10:
+                raise _lib.TxmError(f"MBAR solve: the line search found no decrease at iteration {it}; "
+                                    f"max |S_k - N_k| / N_k = {err:.3e}")
+        f, S, H, F, rnd, g = fn, Sn, Hn, Fn, rn, gn
+    raise _lib.TxmError(f"MBAR solve did not converge in {max_iter} Newton iterations: "
+                        f"max |S_k - N_k| / N_k = {err:.3e} > tol {tol:.1e}")
+
+
+def mbar_initial_f(us, alpha0) -> np.ndarray:
+    """Starting free energies by thermodynamic integration over the states sorted by alpha0 (df/dalpha = <u>, trapezoid
+    between neighbours), gauge f_0 = 0: close enough that no state's weights underflow, even without overlap."""
+    a0 = np.asarray(alpha0, dtype=np.float64)
+    means = np.array([float(u.mean()) for u in us])
+    order = np.argsort(a0, kind="stable")
+    f = np.zeros(len(a0))
+    for i in range(1, len(order)):
+        p, q = order[i - 1], order[i]
+        f[q] = f[p] + (a0[q] - a0[p]) * 0.5 * (means[p] + means[q])
+    return f - f[0]
+
+
+def mbar_solve(us, alpha0, *, tol: float = 1e-12, max_iter: int = 100) -> MbarSolution:
+    """MBAR free energies of K states (1 <= K <= 64) from their reduced potentials alpha0_k u_n over the pooled samples
+    (u: one float64 CUDA tensor per state, any lengths).  Damped Newton (``mbar_newton``), one device evaluation pass
+    (``mbar_eval``) per step: the host waits for each pass -- acceptable because a model solves once and caches the
+    result.  Every pass also stores the pooled log-denominators, so the buffer returned is the solution's."""
+    K = len(us)
+    a0 = np.asarray(alpha0, dtype=np.float64).reshape(-1)
+    if a0.shape != (K,):
+        raise ValueError("need one alpha0 per state")
+    ns = np.array([u.shape[0] for u in us], dtype=np.float64)
+    upiv = mbar_pivot(us)
+    logD = torch.empty(int(ns.sum()), dtype=F64, device="cuda")
+    b = np.log(ns) - a0 * upiv
+
+    def evaluate(g):
+        return mbar_eval(us, a0, g, upiv, logD)
+
+    f, _, it, n_eval, err = mbar_newton(evaluate, ns, b, f0=mbar_initial_f(us, a0), tol=tol, max_iter=max_iter)
+    return MbarSolution(f, logD, upiv, it, n_eval, err)
+
+
+def mbar_predict(xs, us, alpha0, f, logD, alphas, *, upiv: float | None = None) -> torch.Tensor:
+    """MBAR averages of x at each target alpha: (n_alpha, C), from the log-denominators ``logD`` that ``mbar_solve`` stored
+    (``upiv``: the pivot it used, ``MbarSolution.upiv``; by default the pooled mean, which is what the solve takes).  With
+    ``logD=None`` one evaluation pass at ``f`` computes them first.  Targets go 8 per pass over the samples."""
+    L = _L()
+    tab, keep, ns, C = _mbar_table(us, xs)
+    K = len(us)
+    if upiv is None:
+        upiv = mbar_pivot(us)
+    if logD is None:
+        a0 = np.asarray(alpha0, dtype=np.float64).reshape(-1)
+        g = np.log(ns) + np.asarray(f, dtype=np.float64) - a0 * upiv
+        logD = torch.empty(int(ns.sum()), dtype=F64, device="cuda")
+        mbar_eval(us, a0, g - g.max(), upiv, logD)
+    _check_f64_cuda(logD, "logD")
+    if logD.shape != (int(ns.sum()),):
+        raise ValueError("logD must hold one value per pooled sample")
+    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
+    outs = []
+    for i0 in range(0, len(al), 8):
+        chunk = np.ascontiguousarray(al[i0:i0 + 8])
+        na = len(chunk)
+        out = torch.empty((na, C), dtype=F64, device="cuda")
+        ws = workspace(L.txm_mbar_ws_bytes(K, C, na), tag="mbar")
+        check(L.txm_mbar_predict(tab, K, C, float(upiv), _ptr(logD), chunk.ctypes.data_as(ct.POINTER(ct.c_double)), na,
+                                 _ptr(out), _ptr(ws), ws.numel(), _stream()), "txm_mbar_predict")
+        outs.append(out)
+    res = torch.cat(outs, dim=0)
+    del keep
+    return res

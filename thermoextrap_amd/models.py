@@ -24,10 +24,10 @@ from . import _lib, engine
 from . import symbolic as S
 from .data import AbstractData, _Params, xrwrap_alpha
 from .moments import IndexSampler
-from .xrlite import DataArray, concat, is_labelled
+from .xrlite import DataArray, concat, is_dataset, is_labelled
 
-__all__ = ["Derivatives", "ExtrapModel", "ExtrapWeightedModel", "InterpModel", "InterpModelPiecewise", "PerturbModel",
-           "PiecewiseMixin", "StateCollection", "SymDerivBase", "taylor_series_norm", "xr_weights_minkowski"]
+__all__ = ["Derivatives", "ExtrapModel", "ExtrapWeightedModel", "InterpModel", "InterpModelPiecewise", "MBARModel",
+           "PerturbModel", "PiecewiseMixin", "StateCollection", "SymDerivBase", "taylor_series_norm", "xr_weights_minkowski"]
 
 
 class SymDerivBase(S.DerivSeries):
@@ -1026,3 +1026,88 @@ class InterpModelPiecewise(StateCollection, PiecewiseMixin):
         if len(outs) == 1:
             return outs[0]
         return concat(outs, dim=DataArray(np.asarray(seq), alpha_name))
+
+
+class MBARModel(StateCollection):
+    """MBAR over the pooled samples of every state (reference models.py:1049-1111, which hands u_kn = alpha0_k u_n to
+    pymbar):  <x>(alpha) = sum_n x_n e^{-alpha u_n - logD_n} / sum_n e^{-alpha u_n - logD_n}  with
+    logD_n = ln sum_k N_k e^{f_k - alpha0_k u_n} and the free energies f solved once per model (engine.mbar_solve: damped
+    Newton, one device pass per step) and cached with the device buffer of logD.  States hold sample values
+    (``DataValues`` / ``DataCentralMomentsVals``, any mix, any sample counts); their weights are not used, as in the
+    reference, which reads only ``uv`` and ``xv``."""
+
+    def __init__(self, states, kws=None):
+        super().__init__(states, kws)
+        self._samples_host()
+
+    def _samples_host(self):
+        """[(uv, xv, rec_dim)] per state, checked: sample values, not resampled, a DataArray observable, one shape."""
+        from .data import DataCentralMomentsVals, DataValuesBase
+
+        out = []
+        for i, m in enumerate(self.states):
+            d = getattr(m, "data", None)
+            if isinstance(d, DataValuesBase):
+                if d._resampled is not None:
+                    raise NotImplementedError(f"state {i}: MBARModel of resampled data")
+                uv, xv = d._uv, d._xv
+            elif isinstance(d, DataCentralMomentsVals):
+                if d.ds_layout is not None or is_dataset(d.xv):
+                    raise NotImplementedError(f"state {i}: MBARModel of xr.Dataset observables")
+                if d.rec_dim not in d.uv.dims:
+                    raise NotImplementedError(f"state {i}: MBARModel of resampled data")
+                uv, xv = d.uv, d.xv
+            else:
+                raise TypeError(f"state {i}: MBARModel needs the sample values of every state (DataValues or "
+                                f"DataCentralMomentsVals), got {type(d).__name__}")
+            rec = d.rec_dim
+            if tuple(uv.dims) != (rec,):
+                raise NotImplementedError(f"state {i}: uv must be 1-D along the record dim {rec!r}, got {tuple(uv.dims)}")
+            out.append((uv, xv, rec))
+        shapes = [tuple((dm, n) for dm, n in zip(xv.dims, xv.shape) if dm != rec) for _, xv, rec in out]
+        for i, sh in enumerate(shapes):
+            if sh != shapes[0]:
+                raise ValueError(f"the states' xv differ beyond the record dim: state 0 {shapes[0]}, state {i} {sh}")
+        return out
+
+    def _samples(self):
+        """Device tensors (u per state, x per state as (n, C)), the output dims after alpha and their shape."""
+        if "samples" not in self._cache:
+            from .moments import _dev_and_dims
+
+            us, xs = [], []
+            for uv, xv, rec in self._samples_host():
+                ut, _ = _dev_and_dims(uv)
+                xt, xdims = _dev_and_dims(xv)
+                x2 = xt.movedim(xdims.index(rec), 0)
+                us.append(ut)
+                xs.append(x2.reshape(x2.shape[0], -1))
+            _, xv, rec = self._samples_host()[0]
+            others = [dm for dm in xv.dims if dm != rec]
+            cshape = [n for dm, n in zip(xv.dims, xv.shape) if dm != rec]
+            self._cache["samples"] = (us, xs, others, cshape)
+        return self._cache["samples"]
+
+    def _solution(self) -> "engine.MbarSolution":
+        if "mbar" not in self._cache:
+            us, _, _, _ = self._samples()
+            self._cache["mbar"] = engine.mbar_solve(us, self.alpha0)
+        return self._cache["mbar"]
+
+    def predict(self, alpha, alpha_name=None):
+        """<x> at every alpha: dims (alpha_name, *the non-record dims of xv); a scalar alpha keeps a length-1 alpha dim
+        (the reference's expand_dims, models.py:1085-1086)."""
+        if alpha_name is None:
+            alpha_name = self.alpha_name
+        alpha = xrwrap_alpha(alpha, name=alpha_name)
+        avals = np.atleast_1d(np.asarray(alpha.values, dtype=float))
+        if avals.ndim != 1:
+            raise ValueError("alpha must be a scalar or 1-D")
+        us, xs, others, cshape = self._samples()
+        sol = self._solution()
+        out = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
+        vals = out.cpu().numpy().reshape(len(avals), *cshape)
+        return DataArray(vals, (alpha_name, *others), coords={alpha_name: avals})
+
+    def resample(self, *args, **kwargs):
+        raise NotImplementedError("resample not implemented for this class")
