@@ -485,6 +485,47 @@ int txm_mbar_predict(const txm_mbar_state *states_host, int32_t K, int64_t C, do
                      const double *logD, const double *alpha_host, int32_t n_alpha, double *out,
                      void *ws, size_t ws_bytes, txm_stream stream);
 
+/* ---- (f-6) MBARModel.bootstrap: nrep weighted MBAR problems over the same pooled samples ----------- */
+/* Extends (f-5) where the reference stops (models.py:1109-1111: MBARModel.resample raises): replicate r
+ * gives sample n of state s the integer count c[r][n] of row r of that state's multinomial sampler
+ * (spec.ndat = n_s draws out of n_s; spec.nsamp 0 or ndat; counts = the tile counts
+ * txm_sampler_tile_counts wrote for the spec, [nrep][txm_sampler_ntiles(n_s)]; every state the same
+ * spec.nrep).  The per-sample counts are regenerated from the sampler stream inside the kernels:
+ * nothing of size nrep x (sum n) is stored, logD is recomputed from g by predict.
+ *   S[r][k] = sum_n c p[k][n],  H[r][j][k] = sum_n c p[j][n] p[k][n],  obj[r] = sum_n c logD[n]
+ * with p, logD of (f-5) at the log-weights g[r][.] (DEVICE array [nrep][K]).  `states_host`,
+ * `samplers_host`, `alpha0_host` are HOST arrays of K entries (copied into the workspace: not
+ * stream-capturable).  A state's tiles are split over waves by a rule of (n_s, K) alone and all sums
+ * are combined in index order: bitwise reproducible, and row r depends on (seed, spec.rep0 + r, g[r])
+ * only -- not on the other replicates of the call (rows [a, b) of a call equal the call with the
+ * samplers' rows [a, b): rep0 + a, counts + a * ntiles). */
+typedef struct txm_mbar_boot_state {
+  txm_sampler_spec spec;  /* this state's sampler (host copy) */
+  const uint32_t *counts; /* device, [spec.nrep][txm_sampler_ntiles(spec.ndat)] */
+} txm_mbar_boot_state;
+/* 0 for arguments out of range; non-decreasing in n_total (= sum n) and nrep. */
+size_t txm_mbar_boot_ws_bytes(int32_t K, int64_t C, int32_t n_alpha, int64_t n_total, int64_t nrep);
+/* One weighted evaluation pass for the replicates active[0 .. n_active) (device int32 row indices;
+ * NULL: rows 0 .. n_active-1): out [nrep][K + K(K+1)/2 + 1] (device) = S, upper triangle of H
+ * (row-major), obj of each listed row; other rows are not written.
+ * ws >= txm_mbar_boot_ws_bytes(K, 1, 1, sum n, nrep). */
+int txm_mbar_boot_eval(const txm_mbar_state *states_host, const txm_mbar_boot_state *samplers_host,
+                       int32_t K, const double *alpha0_host, const double *g, const int32_t *active,
+                       int64_t n_active, double upiv, double *out, void *ws, size_t ws_bytes,
+                       txm_stream stream);
+/* Reweighted averages of every replicate at n_alpha <= 8 targets (host):
+ *   out[r][a][c] = sum_n c[r][n] x[n][c] w / sum_n c[r][n] w,  w = e^{-alpha[a] ut_n - logD[r][n]}
+ * (out [nrep][n_alpha][C], device).  gref_host [K]: reference log-weights, the SAME in every call whose
+ * rows are to agree bit for bit (the point solution's g): the exponents of (r, a) are shifted by
+ * Mref[a] - min_k (g[r][k] - gref[k]), Mref[a] the exact maximum of -alpha[a] ut - logD over all pooled
+ * samples at gref -- no shifted exponent is positive, and the largest is within
+ * (max_k - min_k)(g[r] - gref) plus the gap to the largest drawn sample of 0.
+ * ws >= txm_mbar_boot_ws_bytes(K, C, n_alpha, sum n, nrep). */
+int txm_mbar_boot_predict(const txm_mbar_state *states_host, const txm_mbar_boot_state *samplers_host,
+                          int32_t K, int64_t C, double upiv, const double *alpha0_host, const double *g,
+                          const double *gref_host, const double *alpha_host, int32_t n_alpha, double *out,
+                          void *ws, size_t ws_bytes, txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,12 @@ class MbarState(ct.Structure):
     _fields_ = [("x", c_void_p), ("u", c_void_p), ("n", c_i64), ("ldx_s", c_i64)]
 
 
+class MbarBootState(ct.Structure):
+    """txm_mbar_boot_state (include/txmom.h): one state's sampler for the MBAR bootstrap entry points."""
+
+    _fields_ = [("spec", SamplerSpec), ("counts", c_void_p)]
+
+
 class Atom(ct.Structure):
     _fields_ = [("src", ct.c_int32), ("pad", ct.c_int32), ("offset", c_i64), ("s_rep", c_i64), ("s_val", c_i64)]
 
@@ -129,6 +135,12 @@ SIGNATURES = {
                               ct.c_double, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "txm_mbar_predict": (c_int, [ct.POINTER(MbarState), ct.c_int32, c_i64, ct.c_double, c_void_p, ct.POINTER(ct.c_double),
                                  ct.c_int32, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_mbar_boot_ws_bytes": (c_size, [ct.c_int32, c_i64, ct.c_int32, c_i64, c_i64]),
+    "txm_mbar_boot_eval": (c_int, [ct.POINTER(MbarState), ct.POINTER(MbarBootState), ct.c_int32, ct.POINTER(ct.c_double),
+                                   c_void_p, c_void_p, c_i64, ct.c_double, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_mbar_boot_predict": (c_int, [ct.POINTER(MbarState), ct.POINTER(MbarBootState), ct.c_int32, c_i64, ct.c_double,
+                                      ct.POINTER(ct.c_double), c_void_p, ct.POINTER(ct.c_double), ct.POINTER(ct.c_double),
+                                      ct.c_int32, c_void_p, c_void_p, c_size, c_void_p]),
 }
 
 ABI_VERSION = 2  # include/txmom.h TXM_ABI_VERSION

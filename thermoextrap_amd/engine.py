@@ -1094,3 +1094,249 @@ def mbar_predict(xs, us, alpha0, f, logD, alphas, *, upiv: float | None = None) 
     res = torch.cat(outs, dim=0)
     del keep
     return res
+
+
+# ---------------------------------------------------------------------------
+# MBAR bootstrap (MBARModel.bootstrap; include/txmom.h section (f-6)).  The reference stops at
+# models.py:1109-1111 (MBARModel.resample raises): replicate r is the weighted MBAR with the multinomial counts of
+# row r of every state's DeviceSampler, solved for all replicates at once from the point solution.
+# ---------------------------------------------------------------------------
+def _mbar_boot_tables(us, samplers, xs=None):
+    """The two host tables of the bootstrap entry points (txm_mbar_state, txm_mbar_boot_state), what they point into,
+    the per-state sample counts, C and nrep."""
+    tab, keep, ns, C = _mbar_table(us, xs)
+    K = len(us)
+    if len(samplers) != K:
+        raise ValueError("need one sampler per state")
+    nrep = int(samplers[0].nrep)
+    stab = (_lib.MbarBootState * K)()
+    counts = []
+    for s, sm in enumerate(samplers):
+        if not isinstance(sm, DeviceSampler):
+            raise TypeError(f"state {s}: the MBAR bootstrap needs a DeviceSampler, got {type(sm).__name__}")
+        if sm.ndat != us[s].shape[0] or sm.spec.nsamp not in (0, sm.ndat):
+            raise ValueError(f"state {s}: the sampler draws {sm.spec.nsamp or sm.ndat} of {sm.ndat}, the state has {us[s].shape[0]} samples")
+        if sm.nrep != nrep:
+            raise ValueError(f"state {s}: sampler nrep = {sm.nrep} differs from state 0's {nrep}")
+        c = sm.counts.contiguous()
+        counts.append(c)
+        stab[s].spec = SamplerSpec(seed=sm.spec.seed, nrep=sm.spec.nrep, ndat=sm.spec.ndat, nsamp=sm.spec.nsamp, rep0=sm.spec.rep0)
+        stab[s].counts = c.data_ptr()
+    return tab, stab, (keep, counts), ns, C, nrep
+
+
+def _mbar_boot_slab(K: int, C: int, n_alpha: int, ntot: int, nrep: int) -> int:
+    """Replicates per library call: all of them when the call's workspace fits ``workspace_budget()``, else the most
+    that do (at least one).  Rows of a slab equal the rows of the unslabbed call bit for bit (DeviceSampler.rows)."""
+    L = _L()
+    need = lambda n: L.txm_mbar_boot_ws_bytes(K, C, n_alpha, ntot, n)  # noqa: E731  (grows with n)
+    budget = workspace_budget()
+    if need(nrep) <= budget:
+        return nrep
+    lo, hi = 1, nrep
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if need(mid) <= budget:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def mbar_boot_eval(us, alpha0, samplers, g, upiv: float, active=None):
+    """One batched weighted evaluation pass (txm_mbar_boot_eval) at the log-weights ``g`` (nrep, K) of the replicates
+    ``active`` (row indices; None: all): (S (R, K), H (R, K, K) symmetric, objective (R,)) of those rows, on the host."""
+    L = _L()
+    tab, stab, keep, ns, _, nrep = _mbar_boot_tables(us, samplers)
+    K = len(us)
+    a0 = np.ascontiguousarray(alpha0, dtype=np.float64)
+    gg = np.ascontiguousarray(g, dtype=np.float64)
+    if a0.shape != (K,) or gg.shape != (nrep, K):
+        raise ValueError("alpha0 needs one entry per state and g one row of them per replicate")
+    rows = np.arange(nrep) if active is None else np.asarray(active, dtype=np.int64).reshape(-1)
+    if len(rows) < 1 or rows.min() < 0 or rows.max() >= nrep or len(np.unique(rows)) != len(rows):
+        raise ValueError(f"active must list distinct rows of [0, {nrep})")
+    nh = K * (K + 1) // 2
+    nv = K + nh + 1
+    gd = torch.as_tensor(gg).to("cuda")
+    ad = None if active is None else torch.as_tensor(rows.astype(np.int32)).to("cuda")
+    out = torch.zeros((nrep, nv), dtype=F64, device="cuda")
+    ws = workspace(L.txm_mbar_boot_ws_bytes(K, 1, 1, int(ns.sum()), nrep), tag="mbar_boot")
+    check(L.txm_mbar_boot_eval(tab, stab, K, a0.ctypes.data_as(ct.POINTER(ct.c_double)), _ptr(gd), _ptr(ad), len(rows),
+                               float(upiv), _ptr(out), _ptr(ws), ws.numel(), _stream()), "txm_mbar_boot_eval")
+    v = out.cpu().numpy()[rows]
+    del keep
+    iu = np.triu_indices(K)
+    H = np.zeros((len(rows), K, K))
+    H[:, iu[0], iu[1]] = v[:, K:K + nh]
+    H[:, iu[1], iu[0]] = v[:, K:K + nh]
+    return v[:, :K].copy(), H, v[:, K + nh].copy()
+
+
+def mbar_newton_batched(evaluate, N, b, f0, *, tol: float = 1e-12, max_iter: int = 100):
+    """``mbar_newton`` for R replicates at once: the same damped Newton per replicate (eigen-floor, step halving,
+    convergence max_k |S_k - N_k| / N_k <= tol), one batched evaluation per trial point.
+
+    ``evaluate(g, active) -> (S, H, obj)``: ``g`` is the full (R, K) array of log-weights (row r = b + f_r + c_r, the
+    constant c_r = -max_k keeps them near 0), ``active`` the int array of the rows wanted; S (A, K), H (A, K, K) full
+    symmetric and obj (A,) are those rows' weighted sums (S_k = sum_n c_n p_kn, ...), in the order of ``active``.
+    A converged replicate is frozen: its f never changes again and it is absent from every later ``active``.
+    ``f0``: (R, K), one start per replicate (``np.tile(f, (R, 1))`` for a common one).
+
+    Returns (f (R, K), g (R, K) -- each row's log-weights at its f --, iterations (R,), evaluations, gradient (R,));
+    ``evaluations`` counts calls of ``evaluate``."""
+    N = np.asarray(N, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    K = len(N)
+    Ntot = float(N.sum())
+    f = np.array(f0, dtype=np.float64)
+    if f.ndim != 2 or f.shape[1] != K:
+        raise ValueError(f"f0 must be (R, {K})")
+    R = f.shape[0]
+    f -= f[:, :1]
+    eps = np.finfo(np.float64).eps
+    g = np.zeros((R, K))          # what the device is shown (trial rows included)
+    g_acc = np.zeros((R, K))      # each row's log-weights at its accepted f
+    n_eval = 0
+
+    def point(fa, rows):
+        nonlocal n_eval
+        ga = b[None, :] + fa
+        c = -ga.max(axis=1)
+        g[rows] = ga + c[:, None]
+        S, H, obj = evaluate(g, rows.copy())
+        n_eval += 1
+        S, H, obj = np.asarray(S, dtype=np.float64), np.asarray(H, dtype=np.float64), np.asarray(obj, dtype=np.float64)
+        F = obj - c * Ntot - fa @ N
+        rnd = 64 * eps * (np.abs(obj) + np.abs(c) * Ntot + np.abs(fa) @ N + Ntot)
+        return S, H, F, rnd
+
+    rows = np.arange(R)
+    S, H, F, rnd = point(f, rows)
+    g_acc[:] = g
+    err = np.max(np.abs(S - N) / N, axis=1)
+    its = np.zeros(R, dtype=np.int64)
+    done = np.zeros(R, dtype=bool)
+    for it in range(max_iter + 1):
+        if not np.all(np.isfinite(err)):
+            r = int(np.flatnonzero(~np.isfinite(err))[0])
+            raise _lib.TxmError(f"MBAR bootstrap solve: the gradient of replicate {r} is not finite")
+        done |= err <= tol
+        rows = np.flatnonzero(~done)
+        if len(rows) == 0:
+            return f, g_acc, its, n_eval, err
+        if it == max_iter:
+            break
+        steps = np.zeros((R, K - 1))
+        slopes = np.zeros(R)
+        for r in rows:
+            grad = S[r] - N
+            Hr = (np.diag(S[r]) - H[r])[1:, 1:]
+            gr = grad[1:]
+            lam, V = np.linalg.eigh(0.5 * (Hr + Hr.T))
+            floor = 1e-12 * max(float(lam.max()), float(N.min()))
+            good = lam > floor
+            proj = V.T @ gr
+            step = -(V[:, good] @ (proj[good] / lam[good]))
+            if not good.all():
+                flat = -(V[:, ~good] @ (proj[~good] / floor))
+                big = float(np.max(np.abs(flat)))
+                if big > _MBAR_MAX_STEP:
+                    flat *= _MBAR_MAX_STEP / big
+                step = step + flat
+            steps[r] = step
+            slopes[r] = float(gr @ step)
+        t = np.ones(R)
+        pending = rows
+        while len(pending):
+            fn = f[pending].copy()
+            fn[:, 1:] += t[pending, None] * steps[pending]
+            Sn, Hn, Fn, rn = point(fn, pending)
+            errn = np.max(np.abs(Sn - N) / N, axis=1)
+            ok = (Fn <= F[pending] + 1e-4 * t[pending] * slopes[pending]) | \
+                ((np.abs(Fn - F[pending]) <= np.maximum(rnd[pending], rn)) & (errn < err[pending]))
+            acc = pending[ok]
+            f[acc], S[acc], H[acc], F[acc], rnd[acc], err[acc] = fn[ok], Sn[ok], Hn[ok], Fn[ok], rn[ok], errn[ok]
+            g_acc[acc] = g[acc]
+            its[acc] += 1
+            pending = pending[~ok]
+            t[pending] *= 0.5
+            if len(pending) and t[pending].min() < 1e-10:
+                r = int(pending[np.argmin(t[pending])])
+                raise _lib.TxmError(f"MBAR bootstrap solve: the line search of replicate {r} found no decrease at "
+                                    f"iteration {it}; max |S_k - N_k| / N_k = {err[r]:.3e}")
+    worst = int(rows[np.argmax(err[rows])])
+    raise _lib.TxmError(f"MBAR bootstrap solve did not converge in {max_iter} Newton iterations: {len(rows)} of {R} "
+                        f"replicates left, the worst is replicate {worst} with max |S_k - N_k| / N_k = "
+                        f"{err[worst]:.3e} > tol {tol:.1e}")
+
+
+def mbar_bootstrap_solve(us, alpha0, samplers, sol0: MbarSolution, *, tol: float = 1e-12, max_iter: int = 100) -> np.ndarray:
+    """Free energies of every bootstrap replicate, (nrep, K) on the host, gauge f[:, 0] = 0: replicate r is the MBAR
+    of the pooled samples weighted by row r of each state's sampler, solved by ``mbar_newton_batched`` from the point
+    solution ``sol0`` (``mbar_solve`` of the same states; its pivot is reused).  Replicates go in slabs whose
+    workspace fits ``workspace_budget()``; a slab's rows are the rows of the unslabbed call bit for bit."""
+    K = len(us)
+    a0 = np.asarray(alpha0, dtype=np.float64).reshape(-1)
+    if a0.shape != (K,):
+        raise ValueError("need one alpha0 per state")
+    if len(samplers) != K:
+        raise ValueError("need one sampler per state")
+    ns = np.array([u.shape[0] for u in us], dtype=np.float64)
+    nrep = int(samplers[0].nrep)
+    upiv = float(sol0.upiv)
+    b = np.log(ns) - a0 * upiv
+    f0 = np.asarray(sol0.f, dtype=np.float64)
+    slab = _mbar_boot_slab(K, 1, 1, int(ns.sum()), nrep)
+    out = np.empty((nrep, K))
+    for r0 in range(0, nrep, slab):
+        r1 = min(r0 + slab, nrep)
+        sub = list(samplers) if (r0, r1) == (0, nrep) else [sm.rows(r0, r1) for sm in samplers]
+
+        def evaluate(g, active, sub=sub):
+            return mbar_boot_eval(us, a0, sub, g, upiv, None if len(active) == g.shape[0] else active)
+
+        out[r0:r1] = mbar_newton_batched(evaluate, ns, b, np.tile(f0, (r1 - r0, 1)), tol=tol, max_iter=max_iter)[0]
+    return out
+
+
+def mbar_bootstrap_predict(xs, us, alpha0, samplers, f, sol0: MbarSolution, alphas) -> torch.Tensor:
+    """MBAR averages of x of every bootstrap replicate at each target: (nrep, n_alpha, C), from the replicates' free
+    energies ``f`` (nrep, K) of ``mbar_bootstrap_solve``.  logD is recomputed from f inside the kernel; the exponents
+    are shifted by a bound taken from the point solution ``sol0`` (txm_mbar_boot_predict).  Targets go 8 per pass,
+    replicates in slabs under ``workspace_budget()``."""
+    L = _L()
+    tab, _, keep, ns, C, nrep = _mbar_boot_tables(us, samplers, xs)
+    K = len(us)
+    a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(-1))
+    f = np.asarray(f, dtype=np.float64)
+    if a0.shape != (K,) or f.shape != (nrep, K):
+        raise ValueError("alpha0 needs one entry per state and f one row of them per replicate")
+    upiv = float(sol0.upiv)
+    b = np.log(ns) - a0 * upiv
+    g = b[None, :] + f
+    g = np.ascontiguousarray(g - g.max(axis=1, keepdims=True))
+    gref = b + np.asarray(sol0.f, dtype=np.float64)
+    gref = np.ascontiguousarray(gref - gref.max())
+    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
+    ntot = int(ns.sum())
+    slab = _mbar_boot_slab(K, C, min(8, len(al)), ntot, nrep)
+    dp = ct.POINTER(ct.c_double)
+    res = torch.empty((nrep, len(al), C), dtype=F64, device="cuda")
+    for r0 in range(0, nrep, slab):
+        r1 = min(r0 + slab, nrep)
+        sub = list(samplers) if (r0, r1) == (0, nrep) else [sm.rows(r0, r1) for sm in samplers]
+        _, stab, keep2, _, _, _ = _mbar_boot_tables(us, sub)
+        gd = torch.as_tensor(g[r0:r1]).to("cuda")
+        for i0 in range(0, len(al), 8):
+            chunk = np.ascontiguousarray(al[i0:i0 + 8])
+            na = len(chunk)
+            out = torch.empty((r1 - r0, na, C), dtype=F64, device="cuda")
+            ws = workspace(L.txm_mbar_boot_ws_bytes(K, C, na, ntot, r1 - r0), tag="mbar_boot")
+            check(L.txm_mbar_boot_predict(tab, stab, K, C, upiv, a0.ctypes.data_as(dp), _ptr(gd), gref.ctypes.data_as(dp),
+                                          chunk.ctypes.data_as(dp), na, _ptr(out), _ptr(ws), ws.numel(), _stream()),
+                  "txm_mbar_boot_predict")
+            res[r0:r1, i0:i0 + na] = out
+        del keep2
+    del keep
+    return res

@@ -1110,4 +1110,68 @@ class MBARModel(StateCollection):
         return DataArray(vals, (alpha_name, *others), coords={alpha_name: avals})
 
     def resample(self, *args, **kwargs):
-        raise NotImplementedError("resample not implemented for this class")
+        raise NotImplementedError("resample not implemented for this class (MBARModel.bootstrap gives the replicates)")
+
+    def bootstrap(self, sampler, rep_dim="rep"):
+        """Bootstrap replicates of this model (the capability the reference's ``resample`` lacks, models.py:1109-1111):
+        every replicate redraws N_s of the N_s samples of each state s and solves MBAR again.  ``sampler``: a mapping
+        with ``"nrep"`` and ``"seed"`` or ``"rng"`` (a seed is drawn from it), optional ``"rep0"`` and ``"rep_dim"``;
+        state s draws the stream replicates rep0 + s * nrep + r of the device sampler of that seed -- the draws
+        ``StateCollection.resample`` makes for the same mapping.  Returns an ``MBARBootstrap``."""
+        accepted = 'a mapping {"nrep": n, "seed": s} or {"nrep": n, "rng": rng} (optional "rep0", "rep_dim", "device": True)'
+        if not isinstance(sampler, Mapping):
+            raise NotImplementedError(f"MBARModel.bootstrap takes {accepted}, got {type(sampler).__name__}")
+        if "indices" in sampler or "freq" in sampler:
+            raise NotImplementedError(f"MBARModel.bootstrap takes {accepted}: explicit indices / freq tables are not supported")
+        if "nrep" not in sampler:
+            raise NotImplementedError(f"MBARModel.bootstrap takes {accepted}")
+        if sampler.get("device") is not None and not sampler.get("device"):
+            raise ValueError('MBARModel.bootstrap draws from the device sampler stream: "device": False (numpy index '
+                             "draws have no replicate index) is not possible")
+        nrep = int(sampler["nrep"])
+        if nrep < 1:
+            raise ValueError(f"nrep = {nrep}: need at least one replicate")
+        seed = sampler.get("seed")
+        if seed is None:
+            from . import moments as cm
+
+            seed = int(cm.validate_rng(sampler.get("rng")).integers(0, 2**63 - 1))
+        rep0 = int(sampler.get("rep0", 0))
+        us, _, _, _ = self._samples()
+        samplers = [engine.DeviceSampler(int(seed), nrep, int(u.shape[0]), rep0=rep0 + s * nrep) for s, u in enumerate(us)]
+        return MBARBootstrap(self, samplers, sampler.get("rep_dim") or rep_dim)
+
+
+class MBARBootstrap:
+    """The bootstrap replicates of an ``MBARModel`` (``MBARModel.bootstrap``): ``parent`` the model, ``nrep``, the
+    per-state ``samplers`` and -- solved once, from the parent's point solution, and cached -- the replicates' free
+    energies ``f`` (nrep, K), gauge f[:, 0] = 0."""
+
+    def __init__(self, parent, samplers, rep_dim="rep"):
+        self.parent = parent
+        self.samplers = list(samplers)
+        self.rep_dim = rep_dim
+        self.nrep = int(self.samplers[0].nrep)
+        self._f = None
+
+    @property
+    def f(self) -> np.ndarray:
+        if self._f is None:
+            us, _, _, _ = self.parent._samples()
+            self._f = engine.mbar_bootstrap_solve(us, self.parent.alpha0, self.samplers, self.parent._solution())
+        return self._f
+
+    def predict(self, alpha, alpha_name=None):
+        """<x> of every replicate at every alpha: dims (alpha_name, rep_dim, *the non-record dims of xv) --
+        PerturbModel's resampled layout; a scalar alpha keeps a length-1 alpha dim, as ``MBARModel.predict``."""
+        p = self.parent
+        if alpha_name is None:
+            alpha_name = p.alpha_name
+        alpha = xrwrap_alpha(alpha, name=alpha_name)
+        avals = np.atleast_1d(np.asarray(alpha.values, dtype=float))
+        if avals.ndim != 1:
+            raise ValueError("alpha must be a scalar or 1-D")
+        us, xs, others, cshape = p._samples()
+        out = engine.mbar_bootstrap_predict(xs, us, p.alpha0, self.samplers, self.f, p._solution(), avals)
+        vals = np.moveaxis(out.cpu().numpy(), 0, 1).reshape(len(avals), self.nrep, *cshape)
+        return DataArray(vals, (alpha_name, self.rep_dim, *others), coords={alpha_name: avals})
