@@ -441,7 +441,8 @@ int txm_cov_over_rep(const double *vals, int32_t n_ord, int64_t nrep, int64_t nv
 /* out[a][c] = sum_i x[i][c] e^{-dalpha[a] (u_i - uref[a])} / sum_i e^{-dalpha[a] (u_i - uref[a])}
  * for n_alpha perturbations in ONE pass over the samples; uref[a] is the u extreme that
  * makes the largest exponent 0 (min u for dalpha > 0, max u for dalpha < 0), computed by
- * the library.   replaces PerturbModel.predict (reference models.py:1019-1039:
+ * the library -- with freq per replicate, over the samples of positive count, so a replicate
+ * that misses the global extreme keeps finite weights.   replaces PerturbModel.predict (reference models.py:1019-1039:
  * exp(dalpha_uv - max) weights, xr.dot / mean).  x row-major (ldx_c == 1); freq (nullable,
  * [nrep][N] int64) adds bootstrap weights -> out [nrep][n_alpha][C]; n_alpha <= 8.
  * dalpha_host: host array.  ws: txm_perturb_ws_bytes. */

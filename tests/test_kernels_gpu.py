@@ -123,13 +123,20 @@ def test_reduce_vals_notebook_kat(eng, kat, idealgas_data):
     assert rel_close(st.ravel(), kat["data_org"]["values"], sig=5)
 
 
-@pytest.mark.parametrize("R,N,mom", [(1, 1000, 5), (16, 5000, 5), (3, 777, 7), (2, 1, 3)])
-def test_reduce_vals_1d(eng, orc, R, N, mom):
+_SHAPES_1D = [(1, 1000, 5), (16, 5000, 5), (3, 777, 7), (2, 1, 3), (300, 1000, 5), (3, 200_000, 5)]
+
+
+@pytest.mark.parametrize(
+    "R,N,mom,weighted",
+    [pytest.param(*c, wt, id="-".join(map(str, c)) + ("-weighted" if wt else "")) for wt in (False, True) for c in _SHAPES_1D],
+)
+def test_reduce_vals_1d(eng, orc, R, N, mom, weighted):
     rng = np.random.default_rng(R + N)
     u = rng.normal(3.0, 1.5, (R, N))
-    got = eng.reduce_vals_1d(dev(u), mom).cpu().numpy()
+    w = rng.random(N) + 0.05 if weighted else None          # one weight vector, shared by all rows
+    got = eng.reduce_vals_1d(dev(u), mom, w=None if w is None else dev(w)).cpu().numpy()
     for r in range(R):
-        t = orc.truth_1d(u[r], mom)
+        t = orc.truth_1d(u[r], mom, w=w)
         sc = np.std(u[r]) ** np.arange(mom + 1) if N > 1 else np.ones(mom + 1)
         err = np.abs(got[r] - t) / (np.abs(t) + sc)
         assert err.max() < RTOL

@@ -7,8 +7,12 @@
 // All n_alpha perturbations are evaluated in one pass (the samples are read
 // once: 8*(C+1) bytes per sample regardless of n_alpha); uref_a is the extreme
 // of u that makes the largest exponent zero (the reference subtracts the max
-// of -da*u for the same reason).  Thread layout as reduce_rowmajor_kernel: a lane
-// owns VEC fixed columns, 2^L lanes span a row; sums live in registers.
+// of -da*u for the same reason).  With bootstrap counts the extreme is taken per
+// replicate over the samples it holds (f_i > 0), as the reference does on the
+// resampled series: a replicate that misses the global extreme by a wide gap
+// would otherwise see every weight underflow and return 0/0.  Thread layout as
+// reduce_rowmajor_kernel: a lane owns VEC fixed columns, 2^L lanes span a row;
+// sums live in registers.
 #include "txm_common.h"
 
 namespace txm {
@@ -16,10 +20,15 @@ namespace txm {
 constexpr int PB_BLOCK = 256;
 constexpr int PB_MAXA = 8;
 
+// extremes of u over the samples of replicate blockIdx.y with a positive count (all samples when freq == NULL):
+// part[rep][gridDim.x][2]
 __global__ __launch_bounds__(PB_BLOCK) void minmax_kernel(const double *__restrict__ u, int64_t N,
+                                                          const int64_t *__restrict__ freq,
                                                           double *__restrict__ part) {
   double lo = INFINITY, hi = -INFINITY;
+  const int64_t *f = freq ? freq + (int64_t)blockIdx.y * N : nullptr;
   for (int64_t i = (int64_t)blockIdx.x * PB_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * PB_BLOCK) {
+    if (f && f[i] <= 0) continue;
     const double v = u[i];
     lo = v < lo ? v : lo;
     hi = v > hi ? v : hi;
@@ -36,19 +45,34 @@ __global__ __launch_bounds__(PB_BLOCK) void minmax_kernel(const double *__restri
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = sl[0];
-    part[2 * blockIdx.x + 1] = sh[0];
+    double *dst = part + 2 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+    dst[0] = sl[0];
+    dst[1] = sh[0];
   }
 }
 
-__global__ void minmax_final_kernel(const double *__restrict__ part, int nblk, double *__restrict__ mm) {
+// mm[rep][2]; thread per replicate
+__global__ __launch_bounds__(PB_BLOCK) void minmax_final_kernel(const double *__restrict__ part, int nblk,
+                                                                int64_t nrep, double *__restrict__ mm) {
+  const int64_t rep = (int64_t)blockIdx.x * PB_BLOCK + threadIdx.x;
+  if (rep >= nrep) return;
+  const double *p = part + 2 * (size_t)rep * nblk;
   double lo = INFINITY, hi = -INFINITY;
   for (int b = 0; b < nblk; ++b) {
-    lo = part[2 * b] < lo ? part[2 * b] : lo;
-    hi = part[2 * b + 1] > hi ? part[2 * b + 1] : hi;
+    lo = p[2 * b] < lo ? p[2 * b] : lo;
+    hi = p[2 * b + 1] > hi ? p[2 * b + 1] : hi;
   }
-  mm[0] = lo;
-  mm[1] = hi;
+  if (lo > hi) lo = hi = 0.0;  // a replicate without samples: its averages are 0/0 whatever the reference point
+  mm[2 * rep] = lo;
+  mm[2 * rep + 1] = hi;
+}
+
+// blocks per replicate of the extremes pre-pass: all replicates together stay within 8 blocks per CU
+static int pb_mm_blocks(int64_t N, int64_t nrep) {
+  int64_t g = cdiv(N, PB_BLOCK * 8);
+  const int64_t cap = (int64_t)num_cus() * 8 / nrep;
+  if (g > cap) g = cap;
+  return g < 1 ? 1 : (int)g;
 }
 
 struct PerturbArgs {
@@ -71,7 +95,7 @@ __global__ __launch_bounds__(PB_BLOCK) void perturb_kernel(const double *__restr
   const int64_t rep = blockIdx.z;
   double uref[NA];
 #pragma unroll
-  for (int a = 0; a < NA; ++a) uref[a] = pa.da[a] >= 0.0 ? mm[0] : mm[1];
+  for (int a = 0; a < NA; ++a) uref[a] = pa.da[a] >= 0.0 ? mm[2 * rep] : mm[2 * rep + 1];
   double num[NA][VEC], den[NA];
 #pragma unroll
   for (int a = 0; a < NA; ++a) {
@@ -111,7 +135,8 @@ __global__ __launch_bounds__(PB_BLOCK) void perturb_kernel(const double *__restr
             da_mine = pa.da[a];
             ur_mine = uref[a];
           }
-        const double w_mine = fw * exp(-da_mine * (ui - ur_mine));
+        // (a sample the replicate does not hold may lie beyond its extremes: its exponential can overflow)
+        const double w_mine = fw == 0.0 ? 0.0 : fw * exp(-da_mine * (ui - ur_mine));
         const int lane = tid & 63;
         const int row_lane0 = lane & ~(LPR - 1);
 #pragma unroll
@@ -124,7 +149,7 @@ __global__ __launch_bounds__(PB_BLOCK) void perturb_kernel(const double *__restr
       } else {
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
-          const double w = fw * exp(-pa.da[a] * (ui - uref[a]));
+          const double w = fw == 0.0 ? 0.0 : fw * exp(-pa.da[a] * (ui - uref[a]));
           den[a] += w;
 #pragma unroll
           for (int v = 0; v < VEC; ++v) num[a][v] = fma(w, xv[v], num[a][v]);
@@ -209,6 +234,12 @@ static PbPlan pb_plan(const double *x, int64_t ldx_s, int64_t N, int64_t C, int6
   return p;
 }
 
+// head of the workspace: mm[nrep][2], then the pre-pass partials [nrep][pb_mm_blocks][2]
+static size_t pb_mm_bytes(int64_t N, int64_t nrep) {
+  return align_up((size_t)nrep * 2 * sizeof(double), 256) +
+         align_up((size_t)nrep * pb_mm_blocks(N, nrep) * 2 * sizeof(double), 256);
+}
+
 }  // namespace txm
 
 using namespace txm;
@@ -218,10 +249,10 @@ extern "C" size_t txm_perturb_ws_bytes(int64_t N, int64_t C, int32_t n_alpha, in
   int64_t cols_pad = 1;
   while (cols_pad < C) cols_pad <<= 1;
   if (cols_pad > 512) cols_pad = cdiv(C, 512) * 512;
-  const size_t mm = 256 + (size_t)num_cus() * 8 * 2 * sizeof(double);
+  const size_t mm = pb_mm_bytes(N, nrep);
   int64_t gx_cap = (int64_t)num_cus() * 8 / (nrep > 8 ? 8 : nrep);  // as pb_plan()
   if (gx_cap < 1) gx_cap = 1;
-  return align_up(mm, 256) + (size_t)nrep * gx_cap * cols_pad * n_alpha * 2 * sizeof(double) + 256;
+  return mm + (size_t)nrep * gx_cap * cols_pad * n_alpha * 2 * sizeof(double) + 256;
 }
 
 extern "C" int txm_perturb(const double *x, int64_t ldx_s, const double *u, int64_t N, int64_t C,
@@ -237,14 +268,13 @@ extern "C" int txm_perturb(const double *x, int64_t ldx_s, const double *u, int6
   }
   hipStream_t st = (hipStream_t)stream;
   double *mm = (double *)ws;
-  double *mpart = mm + 2;
-  const int mblk = num_cus() * 8;
-  double *partial = (double *)((char *)ws + align_up(256 + (size_t)mblk * 2 * sizeof(double), 256));
-  int gmm = (int)cdiv(N, PB_BLOCK * 8);
-  if (gmm > mblk) gmm = mblk;
-  hipLaunchKernelGGL(minmax_kernel, dim3(gmm), dim3(PB_BLOCK), 0, st, u, N, mpart);
+  double *mpart = (double *)((char *)ws + align_up((size_t)nrep * 2 * sizeof(double), 256));
+  double *partial = (double *)((char *)ws + pb_mm_bytes(N, nrep));
+  const int gmm = pb_mm_blocks(N, nrep);
+  hipLaunchKernelGGL(minmax_kernel, dim3(gmm, (unsigned)nrep), dim3(PB_BLOCK), 0, st, u, N, freq, mpart);
   TXM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(1), 0, st, mpart, gmm, mm);
+  hipLaunchKernelGGL(minmax_final_kernel, dim3((unsigned)cdiv(nrep, PB_BLOCK)), dim3(PB_BLOCK), 0, st, mpart, gmm,
+                     nrep, mm);
   TXM_LAUNCH_CHECK();
   const PbPlan p = pb_plan(x, ldx_s, N, C, nrep);
   PerturbArgs pa;

@@ -80,30 +80,37 @@ __global__ __launch_bounds__(256) void convert_1d_kernel(const double *__restric
 // (mean of the block means), summed with the bootstrap counts, and shifted
 // back once.  Same algebra as the sample kernels, so partials add exactly.
 
-// pivot[c] = {mean over records of <u>, mean over records of <x>}
+// pivot[c] = {mean over records of <u>, mean over records of <x>}, over the records that carry weight: an empty
+// record (weight 0, moments 0) has no mean, and counting its zeros would drag the pivot away from the data -- for
+// data 33 sigma from zero into the cancellation the pivot is there to avoid
 __global__ __launch_bounds__(256) void data_pivot_kernel(const double *__restrict__ data,
                                                          int64_t nrec, int64_t C, int K,
                                                          double *__restrict__ pivot) {
   const int c = blockIdx.x;
-  double su = 0.0, sx = 0.0;
+  double su = 0.0, sx = 0.0, cnt = 0.0;
   for (int64_t i = threadIdx.x; i < nrec; i += blockDim.x) {
     const double *st = data + (i * C + c) * 2 * K;
+    if (st[0] == 0.0) continue;
     su += (K > 1) ? st[1] : 0.0;
     sx += st[K];
+    cnt += 1.0;
   }
-  __shared__ double sh[2][256];
+  __shared__ double sh[3][256];
   sh[0][threadIdx.x] = su;
   sh[1][threadIdx.x] = sx;
+  sh[2][threadIdx.x] = cnt;
   __syncthreads();
   for (int off = 128; off > 0; off >>= 1) {
     if ((int)threadIdx.x < off) {
       sh[0][threadIdx.x] += sh[0][threadIdx.x + off];
       sh[1][threadIdx.x] += sh[1][threadIdx.x + off];
+      sh[2][threadIdx.x] += sh[2][threadIdx.x + off];
     }
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    double pu = sh[0][0] / (double)nrec, px = sh[1][0] / (double)nrec;
+    const double n = sh[2][0] > 0.0 ? sh[2][0] : 1.0;
+    double pu = sh[0][0] / n, px = sh[1][0] / n;
     if (!(pu - pu == 0.0)) pu = 0.0;
     if (!(px - px == 0.0)) px = 0.0;
     pivot[2 * c] = pu;
@@ -175,8 +182,10 @@ __global__ __launch_bounds__(256) void data_combine_kernel(const double *__restr
       S1[j] = sh[0][K + j];
     }
     pivot_sums_to_state<K>(S0, S1, pivot[2 * c], pivot[2 * c + 1], st);
+    // no weight at all (a row of zero counts, or only weight-0 records): the empty state, as a merge of nothing
+    const bool empty = S0[0] == 0.0;
 #pragma unroll
-    for (int q = 0; q < 2 * K; ++q) out[(r * C + c) * 2 * K + q] = st[q];
+    for (int q = 0; q < 2 * K; ++q) out[(r * C + c) * 2 * K + q] = empty ? 0.0 : st[q];
   }
 }
 
