@@ -527,6 +527,25 @@ int txm_mbar_boot_predict(const txm_mbar_state *states_host, const txm_mbar_boot
                           const double *gref_host, const double *alpha_host, int32_t n_alpha, double *out,
                           void *ws, size_t ws_bytes, txm_stream stream);
 
+/* ---- (f-7) timeseries: symmetrised lag sums for the statistical inefficiency ----------------------------- */
+/* R_ab(t) = sum_{i=0}^{n-1-t} (da_i db_{i+t} + db_i da_{i+t}),  da = a - <a>, db = b - <b>, for n_pairs pairs of the
+ * series {u, x_0 .. x_{C-1}} and the lags t0 .. t0 + nlags - 1 (both multiples of 256, nlags <= 4096); lags >= n give 0.
+ * The normalised fluctuation correlation function is C(t) = R(t) / (2 (n - t) sigma^2) with sigma^2 = R(0) / (2 n).
+ *   replaces pymbar.timeseries.statistical_inefficiency's correlation sums, which the reference takes of every
+ *   observable column, of the potential energy and of every (column, energy) pair before it subsamples
+ *   (gpr_active/active_utils.py:244-269, DataWrapper.get_data).
+ * Pair index 0 is (u, u), 1 + c is (x_c, x_c), 1 + C + c is (x_c, u).  x is [n][ldx_s] row-major (pitch ldx_s >= C); x = NULL
+ * with C = 0 is legal.  center (device, [1 + C]): <u>, <x_0> .. <x_{C-1}> -- the means of txm_reduce_vals.
+ * `pairs_host` is a HOST array of n_pairs indices; it is copied into the workspace by the call (not stream-capturable).
+ * out (device): [n_pairs][nlags].  The sample chunking is a function of n alone, each (chunk, pair, lag) partial is
+ * written once and the chunks are added in index order: two runs give the same bits, and R(t) has the same bits whichever
+ * 256-aligned (t0, nlags) block it is computed in.  ws also holds the 1 + C centred series as contiguous rows
+ * (8 (1 + C) n bytes). */
+size_t txm_lag_sums_ws_bytes(int64_t n, int64_t C, int32_t n_pairs, int32_t nlags);
+int txm_lag_sums(const double *x, int64_t ldx_s, const double *u, int64_t n, int64_t C, const double *center,
+                 const int32_t *pairs_host, int32_t n_pairs, int64_t t0, int32_t nlags, double *out, void *ws,
+                 size_t ws_bytes, txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ Layout
   symbolic.py  derivative recursion as exact polynomials -> device tables
   models.py    Derivatives, ExtrapModel, StateCollection, the multi-state models (InterpModel, MBARModel, ...)
   beta.py      factory_derivatives, factory_extrapmodel
+  timeseries.py  statistical inefficiency, subsampling and decorrelation of correlated series (pymbar.timeseries)
 """
 
 from ._lib import TxmError, load, require_gpu  # noqa: F401
@@ -21,8 +22,10 @@ _LAZY = {
     "Derivatives": "models", "ExtrapModel": "models", "StateCollection": "models", "PerturbModel": "models",
     "ExtrapWeightedModel": "models", "InterpModel": "models", "InterpModelPiecewise": "models", "MBARModel": "models", "MBARBootstrap": "models",
     "DataArray": "xrlite", "Dataset": "xrlite",
+    "statistical_inefficiency": "timeseries", "statistical_inefficiencies": "timeseries", "subsample_correlated_data": "timeseries",
+    "normalized_fluctuation_correlation_function": "timeseries", "decorrelate": "timeseries",
 }
-_MODULES = {"stack", "distributed", "gpr_input", "beta", "data", "models", "moments", "idealgas", "symbolic", "engine", "xrlite", "volume", "volume_idealgas", "lnpi"}
+_MODULES = {"stack", "distributed", "gpr_input", "beta", "data", "models", "moments", "idealgas", "symbolic", "engine", "xrlite", "volume", "volume_idealgas", "lnpi", "timeseries"}
 
 
 def __getattr__(name):

@@ -1,0 +1,243 @@
+// txm_lagsum.hip -- symmetrised lag sums of centred series (timeseries.statistical_inefficiency; the reference reaches
+// pymbar.timeseries from gpr_active/active_utils.py:244-269):
+//
+//   R_ab(t) = sum_{i=0}^{n-1-t} (da_i db_{i+t} + db_i da_{i+t}),   da = a - <a>, db = b - <b>
+//
+// for a list of series pairs out of {u, x_0 .. x_{C-1}} and a block of lags [t0, t0 + nlags).  n T (3C + 1) FMAs for the
+// 2C + 1 pairs of a state: matrix-pipe work.  Per wave and per step of four samples at s, one v_mfma_f64_16x16x4_f64 on a
+// Toeplitz slice
+//        A[m][k] = da[s + k - m]              (16 x 4, one f64 per lane: m = lane & 15, k = lane >> 4)
+//        B[k][j] = db[s + k + 16 j + t]       (4 x 16:                   j = lane & 15, k = lane >> 4)
+//        D[m][j] += A B                       gathers lag t + 16 j + m of the samples i = s + k - m
+// so one accumulator tile (4 f64 per lane) holds 256 lags of one pair and every MFMA is 1024 useful FMAs.  A cross pair
+// (x_c, u) is two MFMAs into the same tile (A_x B_u + A_u B_x); an auto pair one, doubled (exactly) at the end.
+//
+// Three kernels:
+//   lag_center_kernel   the series, centred with the caller's means and transposed to one contiguous row each
+//                       (d[1 + C][ldd]): the contraction then stages with unit-stride loads (reading a column of the
+//                       row-major x per workgroup costs a 128-byte line per 8 useful bytes, per pair and per L2).
+//   lag_kernel<NT, X>   a workgroup takes (sample chunk, pair, group of NT lag tiles).  The chunk is walked in stages of
+//                       LG_L = 1008 samples: the stage of a is put in LDS between zeros (16 before, 16 behind; zeros
+//                       also past the chunk's end), the window of b (LG_L + 256 NT samples from stage start + t, zeros
+//                       past n) next to it, and 256 steps (s = stage start + 4 q, q = 0 .. 255: 252 + 4 for the skew
+//                       of m) are split over the four waves, 64 consecutive steps each.  Sample i of the stage meets
+//                       row m in exactly one step (4 q + k = i - start + m), so it is counted once per lag; the loop
+//                       has no bounds handling.  The b window is stored with one pad double per 16 (the lanes of a B
+//                       read are 16 doubles apart: 8-way bank conflicts without it); with the step loop unrolled by 4
+//                       every LDS offset is an immediate.  Accumulators stay in registers over all stages of a chunk;
+//                       at the end the four waves' tiles are added in wave order through LDS and ONE partial per
+//                       (chunk, pair, lag) is written.
+//   lag_sum_kernel      adds the chunks in index order (no atomics) and doubles the auto pairs.
+//
+// The chunk length is a function of n alone and a lag's products are accumulated in the same order whichever tile of
+// whichever (t0, nlags) block holds it (adding the +-0 products of the zero padding changes no bits): R(t) is bitwise
+// reproducible from run to run and across block schedules.
+#include <cstring>
+
+#include "txm_common.h"
+
+namespace txm {
+
+typedef double lg_v4d __attribute__((ext_vector_type(4)));
+
+constexpr int LG_BLOCK = 256;
+constexpr int LG_L = 1008;            // samples per stage: LG_L / 4 + 4 = 256 steps, 64 per wave
+constexpr int LG_A = LG_L + 32;       // a stage: 16 zeros, the samples, 16 zeros
+constexpr int LG_MAX_CHUNKS = 512;
+constexpr int LG_MAX_LAGS = 4096;     // per call
+
+static inline int64_t lg_chunk_len(int64_t n) {  // a function of n alone
+  const int64_t stages = cdiv(n, (int64_t)LG_L * LG_MAX_CHUNKS);
+  return (stages < 1 ? 1 : stages) * LG_L;
+}
+static inline int64_t lg_ldd(int64_t n) { return (n + 15) / 16 * 16; }
+static inline int lg_tiles(int32_t nlags) { return nlags % 1024 == 0 ? 4 : (nlags % 512 == 0 ? 2 : 1); }
+static inline size_t lg_lds_bytes(int nt, bool cross) {
+  const size_t nb = LG_L + 256 * nt;
+  const size_t stage = (cross ? 2 : 1) * (LG_A + nb + nb / 16);
+  const size_t red = (size_t)4 * nt * 256;
+  return (stage > red ? stage : red) * sizeof(double);
+}
+
+__global__ __launch_bounds__(LG_BLOCK) void lag_center_kernel(const double *__restrict__ x, int64_t ldx,
+                                                              const double *__restrict__ u, int64_t n, int64_t C,
+                                                              const double *__restrict__ center,
+                                                              double *__restrict__ d, int64_t ldd) {
+  __shared__ double tile[32][65];
+  const int tid = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  if (blockIdx.y == 0 && tid < 64 && r0 + tid < n) d[r0 + tid] = u[r0 + tid] - center[0];
+  const int64_t c0 = (int64_t)blockIdx.y * 32;
+  if (c0 >= C) return;
+#pragma unroll
+  for (int pass = 0; pass < 8; ++pass) {
+    const int r = (tid >> 5) + 8 * pass, c = tid & 31;
+    if (r0 + r < n && c0 + c < C) tile[c][r] = x[(r0 + r) * ldx + c0 + c] - center[1 + c0 + c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int pass = 0; pass < 8; ++pass) {
+    const int c = (tid >> 6) + 4 * pass, r = tid & 63;
+    if (r0 + r < n && c0 + c < C) d[(1 + c0 + c) * ldd + r0 + r] = tile[c][r];
+  }
+}
+
+// partial: [chunk][n_pairs][nlags]
+template <int NT, bool CROSS>
+__global__ __launch_bounds__(LG_BLOCK) void lag_kernel(const double *__restrict__ d, int64_t ldd, int64_t n, int C,
+                                                       const int32_t *__restrict__ pairs, int64_t chunk_len,
+                                                       int64_t t0, int nlags, double *__restrict__ partial) {
+  constexpr int NB = LG_L + 256 * NT;  // the b window of a stage (a multiple of 16)
+  constexpr int NBP = NB + NB / 16;    // ... with one pad double per 16
+  extern __shared__ double smem[];
+  const int p = pairs[blockIdx.y];
+  if ((p > C) != CROSS) return;        // the other instance's pair
+  const double *__restrict__ da = d + (int64_t)(CROSS ? p - C : p) * ldd;
+  const double *__restrict__ db = CROSS ? d : da;
+  double *sa0 = smem, *sb0 = sa0 + LG_A, *sa1 = sb0 + NBP, *sb1 = sa1 + LG_A;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int m = lane & 15, k = lane >> 4;
+  const int64_t cb = (int64_t)blockIdx.x * chunk_len;
+  const int64_t ce = cb + chunk_len < n ? cb + chunk_len : n;
+  const int64_t tg = t0 + (int64_t)blockIdx.z * (256 * NT);
+  lg_v4d acc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j] = lg_v4d{0.0, 0.0, 0.0, 0.0};
+  // (stages whose whole b window lies past n contribute zeros only)
+  for (int64_t c = cb; c < ce && c + tg < n; c += LG_L) {
+    const int64_t aend = c + LG_L < ce ? c + LG_L : ce;
+    __syncthreads();
+    for (int j = tid; j < LG_A; j += LG_BLOCK) {
+      const int64_t i = c - 16 + j;
+      const bool in = i >= c && i < aend;
+      sa0[j] = in ? da[i] : 0.0;
+      if (CROSS) sa1[j] = in ? db[i] : 0.0;
+    }
+    for (int q = tid; q < NB; q += LG_BLOCK) {
+      const int64_t i = c + tg + q;
+      const bool in = i < n;
+      sb0[q + (q >> 4)] = in ? db[i] : 0.0;
+      if (CROSS) sb1[q + (q >> 4)] = in ? da[i] : 0.0;
+    }
+    __syncthreads();
+    // step q = 4 g + r reads a at 4 q + k - m + 16 and b at e + 16 (m + 16 j), e = 4 q + k = 16 g + 4 r + k, which the
+    // padded layout puts at 17 g + 4 r + k + 17 m + 272 j
+    const double *pa0 = sa0 + 16 + k - m, *pa1 = sa1 + 16 + k - m;
+    const double *pb0 = sb0 + k + 17 * m, *pb1 = sb1 + k + 17 * m;
+    for (int g = 16 * wave; g < 16 * wave + 16; ++g) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double a0 = pa0[16 * g + 4 * r];
+        double a1 = 0.0;
+        if (CROSS) a1 = pa1[16 * g + 4 * r];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, pb0[17 * g + 4 * r + 272 * j], acc[j], 0, 0, 0);
+          if (CROSS) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, pb1[17 * g + 4 * r + 272 * j], acc[j], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // the four waves' tiles, added in wave order.  D layout: column = lane & 15, row = (lane >> 4) + 4 * reg; the lag of
+  // D[row][column] inside its tile is 16 * column + row
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) smem[(wave * NT + j) * 256 + 16 * m + k + 4 * r] = acc[j][r];
+  __syncthreads();
+  double *dst = partial + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * nlags + (size_t)blockIdx.z * (256 * NT);
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    double v = smem[j * 256 + tid];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) v += smem[(w * NT + j) * 256 + tid];
+    dst[j * 256 + tid] = v;
+  }
+}
+
+__global__ __launch_bounds__(LG_BLOCK) void lag_sum_kernel(const double *__restrict__ partial, int nchunks, int C,
+                                                           const int32_t *__restrict__ pairs, int n_pairs, int nlags,
+                                                           double *__restrict__ out) {
+  const int t = blockIdx.x * LG_BLOCK + threadIdx.x, slot = blockIdx.y;
+  double acc = 0.0;
+  for (int ch = 0; ch < nchunks; ++ch) acc += partial[((size_t)ch * n_pairs + slot) * nlags + t];
+  out[(size_t)slot * nlags + t] = pairs[slot] > C ? acc : 2.0 * acc;
+}
+
+static bool lg_shape_ok(int64_t n, int64_t C, int32_t n_pairs, int32_t nlags) {
+  return n >= 1 && n <= ((int64_t)1 << 36) && C >= 0 && C <= 16383 && n_pairs >= 1 && n_pairs <= 2 * C + 1 && nlags >= 256 &&
+         nlags <= LG_MAX_LAGS && nlags % 256 == 0;
+}
+
+}  // namespace txm
+
+using namespace txm;
+
+extern "C" size_t txm_lag_sums_ws_bytes(int64_t n, int64_t C, int32_t n_pairs, int32_t nlags) {
+  if (!lg_shape_ok(n, C, n_pairs, nlags)) return 0;
+  const size_t head = align_up((size_t)n_pairs * sizeof(int32_t), 256);
+  const size_t series = (size_t)(1 + C) * (size_t)lg_ldd(n) * sizeof(double);
+  const size_t nchunks = (size_t)cdiv(n, lg_chunk_len(n));
+  return head + series + nchunks * (size_t)n_pairs * (size_t)nlags * sizeof(double) + 256;
+}
+
+extern "C" int txm_lag_sums(const double *x, int64_t ldx_s, const double *u, int64_t n, int64_t C, const double *center,
+                            const int32_t *pairs_host, int32_t n_pairs, int64_t t0, int32_t nlags, double *out,
+                            void *ws, size_t ws_bytes, txm_stream stream) {
+  TXM_REQUIRE(u && center && pairs_host && out && ws, "lag_sums: null pointer");
+  TXM_REQUIRE(n >= 1 && n <= ((int64_t)1 << 36), "lag_sums: n = %lld outside [1, 2^36]", (long long)n);
+  TXM_REQUIRE(C >= 0 && C <= 16383, "lag_sums: C = %lld outside [0, 16383]", (long long)C);
+  TXM_REQUIRE(C == 0 || x, "lag_sums: null x with C = %lld columns", (long long)C);
+  TXM_REQUIRE(C == 0 || ldx_s >= C, "lag_sums: row pitch ldx_s = %lld < C = %lld", (long long)ldx_s, (long long)C);
+  TXM_REQUIRE(n_pairs >= 1 && n_pairs <= 2 * C + 1, "lag_sums: n_pairs = %d outside [1, 2 C + 1 = %lld]", (int)n_pairs,
+              (long long)(2 * C + 1));
+  for (int32_t s = 0; s < n_pairs; ++s)
+    TXM_REQUIRE(pairs_host[s] >= 0 && pairs_host[s] <= 2 * C, "lag_sums: pair index %d (entry %d) outside [0, 2 C = %lld]",
+                (int)pairs_host[s], (int)s, (long long)(2 * C));
+  TXM_REQUIRE(t0 >= 0 && t0 % 256 == 0 && t0 <= ((int64_t)1 << 36), "lag_sums: t0 = %lld is not a multiple of 256 in [0, 2^36]",
+              (long long)t0);
+  TXM_REQUIRE(nlags >= 256 && nlags % 256 == 0 && nlags <= LG_MAX_LAGS,
+              "lag_sums: nlags = %d is not a multiple of 256 in [256, %d]", (int)nlags, LG_MAX_LAGS);
+  if (ws_bytes < txm_lag_sums_ws_bytes(n, C, n_pairs, nlags)) {
+    set_error("lag_sums: workspace too small");
+    return TXM_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t head = align_up((size_t)n_pairs * sizeof(int32_t), 256);
+  const int64_t ldd = lg_ldd(n);
+  int32_t *pairs = (int32_t *)ws;
+  double *d = (double *)((char *)ws + head);
+  double *partial = d + (size_t)(1 + C) * ldd;
+  TXM_HIP(hipMemcpyAsync(pairs, pairs_host, (size_t)n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const int64_t cblocks = C > 0 ? cdiv(C, 32) : 1;
+  hipLaunchKernelGGL(lag_center_kernel, dim3((unsigned)cdiv(n, 64), (unsigned)cblocks), dim3(LG_BLOCK), 0, st, x, ldx_s,
+                     u, n, C, center, d, ldd);
+  TXM_LAUNCH_CHECK();
+  const int64_t chunk_len = lg_chunk_len(n);
+  const int64_t nchunks = cdiv(n, chunk_len);
+  const int nt = lg_tiles(nlags);
+  bool any_auto = false, any_cross = false;
+  for (int32_t s = 0; s < n_pairs; ++s) (pairs_host[s] > C ? any_cross : any_auto) = true;
+  const dim3 grid((unsigned)nchunks, (unsigned)n_pairs, (unsigned)(nlags / (256 * nt))), block(LG_BLOCK);
+#define TXM_LG(NT_, X_)                                                                                          \
+  hipLaunchKernelGGL((lag_kernel<NT_, X_>), grid, block, lg_lds_bytes(NT_, X_), st, d, ldd, n, (int)C, pairs, \
+                     chunk_len, t0, (int)nlags, partial)
+  if (any_auto) {
+    if (nt == 4) TXM_LG(4, false);
+    else if (nt == 2) TXM_LG(2, false);
+    else TXM_LG(1, false);
+    TXM_LAUNCH_CHECK();
+  }
+  if (any_cross) {
+    if (nt == 4) TXM_LG(4, true);
+    else if (nt == 2) TXM_LG(2, true);
+    else TXM_LG(1, true);
+    TXM_LAUNCH_CHECK();
+  }
+#undef TXM_LG
+  hipLaunchKernelGGL(lag_sum_kernel, dim3((unsigned)(nlags / LG_BLOCK), (unsigned)n_pairs), dim3(LG_BLOCK), 0, st, partial,
+                     (int)nchunks, (int)C, pairs, (int)n_pairs, (int)nlags, out);
+  TXM_LAUNCH_CHECK();
+  return TXM_OK;
+}

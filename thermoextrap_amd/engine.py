@@ -1340,3 +1340,60 @@ def mbar_bootstrap_predict(xs, us, alpha0, samplers, f, sol0: MbarSolution, alph
         del keep2
     del keep
     return res
+
+
+# ---------------------------------------------------------------------------
+# lag sums (timeseries.py; the reference takes pymbar.timeseries.statistical_inefficiency: gpr_active/active_utils.py:244-269)
+# ---------------------------------------------------------------------------
+LAG_BLOCK = 256        # t0 and nlags of a call are multiples of it
+LAG_MAX_LAGS = 4096    # lags per call
+LAG_STAGE = 1008       # samples per staged piece of a chunk; a chunk is LAG_STAGE * ceil(n / (LAG_STAGE * 512)) samples
+
+
+def lag_center(x: torch.Tensor | None, u: torch.Tensor) -> torch.Tensor:
+    """The means the lag sums are centred with, (1 + C,): <u>, <x_0> .. <x_{C-1}> -- from the package's own reduction."""
+    if x is None or x.shape[1] == 0:
+        return reduce_vals_1d(u, 1)[1:2].contiguous()
+    st = reduce_vals(x, u, 1)
+    return torch.cat([st[0, 0, 1:2], st[:, 1, 0]]).contiguous()
+
+
+def lag_sums(x: torch.Tensor | None, u: torch.Tensor, pairs, t0: int, nlags: int, center: torch.Tensor | None = None) -> torch.Tensor:
+    """R(t) = sum_i (da_i db_{i+t} + db_i da_{i+t}) of the centred series, t = t0 .. t0 + nlags - 1, for every pair of
+    ``pairs``: index 0 is (u, u), 1 + c is (x_c, x_c), 1 + C + c is (x_c, u).  x: (N, C) row-major (any row pitch), (N,)
+    or None; u: (N,).  Returns (len(pairs), nlags); lags >= N are 0.  Bitwise reproducible, and independent of how the
+    lags are cut into 256-aligned calls."""
+    L = _L()
+    _check_f64_cuda(u, "u")
+    if u.dim() != 1:
+        raise ValueError("u must be (N,)")
+    N = u.shape[0]
+    u = u.contiguous()
+    C, ls, x2 = 0, 0, None
+    if x is not None:
+        _check_f64_cuda(x, "x")
+        x2 = x.unsqueeze(1) if x.dim() == 1 else x
+        if x2.dim() != 2 or x2.shape[0] != N:
+            raise ValueError(f"x must be ({N},) or ({N}, C), got {tuple(x.shape)}")
+        C = x2.shape[1]
+        if C == 0:
+            x2 = None
+        else:
+            if x2.stride(1) != 1 or (N > 1 and x2.stride(0) < C):
+                x2 = x2.contiguous()
+            ls = max(x2.stride(0), C) if N > 1 else C
+    if center is None:
+        center = lag_center(x2, u)
+    _check_f64_cuda(center, "center")
+    if center.shape != (1 + C,):
+        raise ValueError(f"center must have shape ({1 + C},), got {tuple(center.shape)}")
+    center = center.contiguous()
+    pl = np.ascontiguousarray(np.atleast_1d(np.asarray(pairs)).astype(np.int32))
+    if pl.ndim != 1 or pl.size == 0:
+        raise ValueError("pairs must be a non-empty list of pair indices")
+    out = torch.empty((pl.size, int(nlags)), dtype=F64, device="cuda")
+    nws = L.txm_lag_sums_ws_bytes(N, C, pl.size, int(nlags))
+    ws = workspace(nws, tag="lag")
+    check(L.txm_lag_sums(_ptr(x2), ls, _ptr(u), N, C, _ptr(center), pl.ctypes.data_as(ct.POINTER(ct.c_int32)), pl.size,
+                         int(t0), int(nlags), _ptr(out), _ptr(ws), ws.numel(), _stream()), "txm_lag_sums")
+    return out
