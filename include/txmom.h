@@ -486,6 +486,25 @@ int txm_mbar_predict(const txm_mbar_state *states_host, int32_t K, int64_t C, do
                      const double *logD, const double *alpha_host, int32_t n_alpha, double *out,
                      void *ws, size_t ws_bytes, txm_stream stream);
 
+/* The sums over the pooled samples behind MBAR's asymptotic covariance (Shirts & Chodera 2008, eq. 8 and appendix D --
+ * pymbar's dA of compute_expectations, df of compute_free_energy_differences) for n_alpha <= 8 targets alpha_host (host).
+ * With the columns W_nk = p[k][n] / N_k of the sampled states (p at the log-weights g_host [K], alpha0_host [K]: the
+ * solution a txm_mbar_eval wrote `logD` at, same upiv), W_na = w_an / sum_n w_an of the targets
+ * (w_an = e^{-alpha[a] ut_n - logD[n]}) and d_nc = x[n][c] - mean[a][c] (mean [n_alpha][C], device: txm_mbar_predict's
+ * output for the same targets):
+ *   out[a] (device, [n_alpha][1 + K + C (1 + K)]) = Q_a = sum_n W_na^2, B_a[k] = sum_n W_nk W_na (k < K), then per
+ *   column c: yy_ac = sum_n W_na^2 d_nc^2, b_ac[k] = sum_n W_nk W_na d_nc (k < K).
+ *   lnw (nullable, device [n_alpha]) receives ln sum_n e^{-alpha[a] ut_n - logD[n]} (minus it: the target's free energy
+ *   up to the constants the caller put into g and upiv).
+ * One pass over u, logD and x behind predict's max pass (no exponent is positive); the contraction runs on the FP64
+ * matrix pipe; the denominators ride in the same pass.  Partials are combined in a fixed order: bitwise reproducible.
+ * `states_host` is copied into the workspace as by txm_mbar_eval; nothing waits on the host.
+ * ws: txm_mbar_cov_ws_bytes(K, C, n_alpha) (0 for arguments out of range). */
+size_t txm_mbar_cov_ws_bytes(int32_t K, int64_t C, int32_t n_alpha);
+int txm_mbar_cov(const txm_mbar_state *states_host, int32_t K, int64_t C, double upiv, const double *alpha0_host,
+                 const double *g_host, const double *logD, const double *alpha_host, int32_t n_alpha,
+                 const double *mean, double *out, double *lnw, void *ws, size_t ws_bytes, txm_stream stream);
+
 /* ---- (f-6) MBARModel.bootstrap: nrep weighted MBAR problems over the same pooled samples ----------- */
 /* Extends (f-5) where the reference stops (models.py:1109-1111: MBARModel.resample raises): replicate r
  * gives sample n of state s the integer count c[r][n] of row r of that state's multinomial sampler

@@ -28,23 +28,9 @@
 #include <cmath>
 #include <cstring>
 
-#include "txm_common.h"
+#include "txm_mbar.h"
 
 namespace txm {
-
-constexpr int MB_BLOCK = 256;
-constexpr int MB_MAXK = 64;
-constexpr int MB_REGK = 8;   // K <= MB_REGK: register kernel
-constexpr int MB_MAXA = 8;   // targets per predict call
-constexpr int MB_TILE = MB_BLOCK / 4;  // samples per LDS tile (four lanes per sample)
-
-// workspace head: the state table, g[MB_MAXK], alpha0[MB_MAXK] (one host-to-device copy), then M[MB_MAXA]
-constexpr size_t MB_TAB_BYTES = MB_MAXK * sizeof(txm_mbar_state) + 2 * MB_MAXK * sizeof(double);
-constexpr size_t MB_HEAD_BYTES = MB_TAB_BYTES + 256;
-
-struct MbarTargets {
-  double a[MB_MAXA];
-};
 
 __device__ inline int64_t state_offset(const txm_mbar_state *tab, int s) {
   int64_t off = 0;

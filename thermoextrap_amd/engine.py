@@ -1097,6 +1097,130 @@ def mbar_predict(xs, us, alpha0, f, logD, alphas, *, upiv: float | None = None) 
 
 
 # ---------------------------------------------------------------------------
+# MBAR's asymptotic covariance (Shirts & Chodera 2008, eq. 8 and appendix D; include/txmom.h txm_mbar_cov).
+# Theta = W^T (I_N - W N W^T)^+ W over the columns W_nk = p_kn / N_k of the sampled states and W_na of the targets needs
+# only the Gram matrix G = W^T W: the sampled block is H / (N_j N_k) of one evaluation pass at the solution, the target
+# blocks are the sums of txm_mbar_cov.
+# ---------------------------------------------------------------------------
+_MBAR_PINV_CUT = 1e-12   # eigenvalues of I - sqrt(N) G sqrt(N) below this fraction of the largest are its null space
+
+
+def mbar_solution_g(ns, alpha0, sol: MbarSolution):
+    """The shifted log-weights the solve's last evaluation ran at (``mbar_newton``'s g = b + f - max(b + f)) and the
+    shift c = -max(b + f): ``sol.logD`` is ln sum_k N_k e^{f_k - alpha0_k u_n} + c."""
+    a0 = np.asarray(alpha0, dtype=np.float64).reshape(-1)
+    g = np.log(np.asarray(ns, dtype=np.float64)) - a0 * sol.upiv + np.asarray(sol.f, dtype=np.float64)
+    c = -float(g.max())
+    return g + c, c
+
+
+def mbar_gram(us, alpha0, sol: MbarSolution) -> np.ndarray:
+    """G_jk = sum_n W_nj W_nk of the sampled states: one ``mbar_eval`` at the solution's g, H_jk / (N_j N_k)."""
+    ns = np.array([u.shape[0] for u in us], dtype=np.float64)
+    g, _ = mbar_solution_g(ns, alpha0, sol)
+    _, H, _ = mbar_eval(us, np.asarray(alpha0, dtype=np.float64).reshape(-1), g, sol.upiv)
+    return H / np.outer(ns, ns)
+
+
+def _sym_pinv(A: np.ndarray) -> np.ndarray:
+    lam, V = np.linalg.eigh(0.5 * (A + A.T))
+    keep = lam > _MBAR_PINV_CUT * max(float(np.max(np.abs(lam))), 1.0)
+    return (V[:, keep] / lam[keep]) @ V[:, keep].T
+
+
+def mbar_theta(G, N) -> np.ndarray:
+    """Theta = W^T (I - W N W^T)^+ W from the Gram matrix G = W^T W = V L V^T alone: V S (I - S V^T N V S)^+ S V^T with
+    S = L^{1/2} (negative eigenvalues of G, rounding, clipped to 0).  N: the sample count of every column, 0 for the
+    columns that were not sampled (targets)."""
+    G = np.asarray(G, dtype=np.float64)
+    N = np.asarray(N, dtype=np.float64).reshape(-1)
+    if G.shape != (len(N), len(N)):
+        raise ValueError("G must be square with one row per entry of N")
+    lam, V = np.linalg.eigh(0.5 * (G + G.T))
+    S = np.sqrt(np.clip(lam, 0.0, None))
+    VS = V * S
+    A = np.eye(len(N)) - VS.T @ (N[:, None] * VS)
+    return VS @ _sym_pinv(A) @ VS.T
+
+
+def mbar_reduced_pinv(Gs, N) -> np.ndarray:
+    """(I_K - sqrt(N) G_s sqrt(N))^+ of the sampled block: singular along sqrt(N) by construction (the rows of the
+    overlap matrix sum to 1), hence a pseudo-inverse.  Taken once per model."""
+    rn = np.sqrt(np.asarray(N, dtype=np.float64).reshape(-1))
+    Gs = np.asarray(Gs, dtype=np.float64)
+    return _sym_pinv(np.eye(len(rn)) - rn[:, None] * Gs * rn[None, :])
+
+
+def mbar_mean_variance(Gs, N, yy, b, *, pinv=None) -> np.ndarray:
+    """var of an MBAR average at a target from the K x K block alone: with y_n = W_na (x_n - <x>_a), the unsampled column
+    y has Theta_yy = yy + (sqrt(N) b)^T (I_K - sqrt(N) G_s sqrt(N))^+ (sqrt(N) b), yy = sum_n y_n^2 and
+    b_k = sum_n W_nk y_n.  ``yy`` (...,) and ``b`` (..., K) broadcast; ``pinv``: ``mbar_reduced_pinv(Gs, N)`` if the
+    caller keeps it."""
+    rn = np.sqrt(np.asarray(N, dtype=np.float64).reshape(-1))
+    P = mbar_reduced_pinv(Gs, N) if pinv is None else pinv
+    rb = np.asarray(b, dtype=np.float64) * rn
+    return np.asarray(yy, dtype=np.float64) + np.einsum("...j,jk,...k->...", rb, P, rb)
+
+
+def mbar_overlap(Gs, N):
+    """The overlap matrix O = G_s diag(N) of the sampled states (rows sum to 1), its eigenvalues in descending order --
+    those of the symmetric sqrt(N) G_s sqrt(N), which is similar to O -- and the scalar 1 - the second largest
+    (1 for a single state)."""
+    Gs = np.asarray(Gs, dtype=np.float64)
+    N = np.asarray(N, dtype=np.float64).reshape(-1)
+    rn = np.sqrt(N)
+    ev = np.linalg.eigvalsh(rn[:, None] * (0.5 * (Gs + Gs.T)) * rn[None, :])[::-1].copy()
+    return Gs * N[None, :], ev, (float(1.0 - ev[1]) if len(ev) > 1 else 1.0)
+
+
+def mbar_cov_sums(xs, us, alpha0, sol: MbarSolution, alphas, means, *, with_lnw: bool = False):
+    """The target sums of the asymptotic covariance (txm_mbar_cov), 8 targets per pass over the samples, on the host:
+    Q (n_alpha,) = sum_n W_na^2, B (n_alpha, K) = sum_n W_nk W_na, yy (n_alpha, C) = sum_n W_na^2 (x_nc - mean_ac)^2 and
+    b (n_alpha, C, K) = sum_n W_nk W_na (x_nc - mean_ac).  ``means``: (n_alpha, C) float64 CUDA, ``mbar_predict``'s output
+    for the same targets.  ``with_lnw``: also ln sum_n e^{-alpha u_n - logD_n} (n_alpha,) with the true log-denominators
+    (the solve's pivot and shift taken out): minus the target's free energy in the gauge of ``sol.f``."""
+    L = _L()
+    tab, keep, ns, C = _mbar_table(us, xs)
+    K = len(us)
+    a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(-1))
+    if a0.shape != (K,):
+        raise ValueError("need one alpha0 per state")
+    g, c = mbar_solution_g(ns, a0, sol)
+    g = np.ascontiguousarray(g)
+    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
+    _check_f64_cuda(means, "means")
+    if means.shape != (len(al), C):
+        raise ValueError(f"means must be ({len(al)}, {C}), got {tuple(means.shape)}")
+    if sol.logD.shape != (int(ns.sum()),):
+        raise ValueError("sol.logD must hold one value per pooled sample")
+    dp = ct.POINTER(ct.c_double)
+    width = 1 + K + C * (1 + K)
+    outs, lnws = [], []
+    for i0 in range(0, len(al), 8):
+        chunk = np.ascontiguousarray(al[i0:i0 + 8])
+        na = len(chunk)
+        mean = means[i0:i0 + na].contiguous()
+        out = torch.empty((na, width), dtype=F64, device="cuda")
+        lnw = torch.empty(na, dtype=F64, device="cuda")
+        ws = workspace(L.txm_mbar_cov_ws_bytes(K, C, na), tag="mbar_cov")
+        check(L.txm_mbar_cov(tab, K, C, float(sol.upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp), _ptr(sol.logD),
+                             chunk.ctypes.data_as(dp), na, _ptr(mean), _ptr(out), _ptr(lnw), _ptr(ws), ws.numel(),
+                             _stream()), "txm_mbar_cov")
+        outs.append(out)
+        lnws.append(lnw)
+    v = torch.cat(outs, dim=0).cpu().numpy()
+    del keep
+    Q = v[:, 0].copy()
+    B = v[:, 1:1 + K].copy()
+    rest = v[:, 1 + K:].reshape(len(al), C, 1 + K)
+    yy, b = rest[:, :, 0].copy(), rest[:, :, 1:].copy()
+    if not with_lnw:
+        return Q, B, yy, b
+    # the kernel's exponents are -alpha (u - upiv) - (logD + c): sum_n e^{-alpha u_n - logD_n} = e^{-alpha upiv + c} x its sum
+    return Q, B, yy, b, torch.cat(lnws).cpu().numpy() - al * sol.upiv + c
+
+
+# ---------------------------------------------------------------------------
 # MBAR bootstrap (MBARModel.bootstrap; include/txmom.h section (f-6)).  The reference stops at
 # models.py:1109-1111 (MBARModel.resample raises): replicate r is the weighted MBAR with the multinomial counts of
 # row r of every state's DeviceSampler, solved for all replicates at once from the point solution.

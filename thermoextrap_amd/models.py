@@ -16,6 +16,7 @@ import ctypes as ct
 import math
 from collections.abc import Mapping
 from functools import lru_cache
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -1028,6 +1029,15 @@ class InterpModelPiecewise(StateCollection, PiecewiseMixin):
         return concat(outs, dim=DataArray(np.asarray(seq), alpha_name))
 
 
+class MBAROverlap(NamedTuple):
+    """What ``MBARModel.overlap`` returns: the K x K overlap ``matrix``, its ``eigenvalues`` (descending) and the
+    ``scalar`` 1 - the second largest eigenvalue."""
+
+    matrix: np.ndarray
+    eigenvalues: np.ndarray
+    scalar: float
+
+
 class MBARModel(StateCollection):
     """MBAR over the pooled samples of every state (reference models.py:1049-1111, which hands u_kn = alpha0_k u_n to
     pymbar):  <x>(alpha) = sum_n x_n e^{-alpha u_n - logD_n} / sum_n e^{-alpha u_n - logD_n}  with
@@ -1108,6 +1118,100 @@ class MBARModel(StateCollection):
         out = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
         vals = out.cpu().numpy().reshape(len(avals), *cshape)
         return DataArray(vals, (alpha_name, *others), coords={alpha_name: avals})
+
+    # ---- the estimator's asymptotic covariance (Shirts & Chodera 2008, eq. 8 and appendix D) --------------------------
+    # It assumes independent samples: decorrelate first (timeseries.statistical_inefficiencies).
+    def _counts(self) -> np.ndarray:
+        us, _, _, _ = self._samples()
+        return np.array([u.shape[0] for u in us], dtype=np.float64)
+
+    def _gram(self) -> np.ndarray:
+        """G_jk = sum_n W_nj W_nk of the sampled states: one evaluation pass at the solution, cached."""
+        if "mbar_gram" not in self._cache:
+            us, _, _, _ = self._samples()
+            self._cache["mbar_gram"] = engine.mbar_gram(us, self.alpha0, self._solution())
+        return self._cache["mbar_gram"]
+
+    def _reduced_pinv(self) -> np.ndarray:
+        if "mbar_pinv" not in self._cache:
+            self._cache["mbar_pinv"] = engine.mbar_reduced_pinv(self._gram(), self._counts())
+        return self._cache["mbar_pinv"]
+
+    def _alpha_values(self, alpha, alpha_name):
+        if alpha_name is None:
+            alpha_name = self.alpha_name
+        alpha = xrwrap_alpha(alpha, name=alpha_name)
+        avals = np.atleast_1d(np.asarray(alpha.values, dtype=float))
+        if avals.ndim != 1:
+            raise ValueError("alpha must be a scalar or 1-D")
+        return avals, alpha_name
+
+    def predict_with_error(self, alpha, alpha_name=None):
+        """(mean, err): ``predict(alpha)`` bit for bit and its asymptotic standard deviation (pymbar's ``dA`` of
+        compute_expectations), both with ``predict``'s dims.  One more pass over the samples per 8 targets; no re-solve."""
+        avals, alpha_name = self._alpha_values(alpha, alpha_name)
+        us, xs, others, cshape = self._samples()
+        sol = self._solution()
+        means = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
+        _, _, yy, b = engine.mbar_cov_sums(xs, us, self.alpha0, sol, avals, means)
+        var = engine.mbar_mean_variance(self._gram(), self._counts(), yy, b, pinv=self._reduced_pinv())
+        dims, coords = (alpha_name, *others), {alpha_name: avals}
+        mean = DataArray(means.cpu().numpy().reshape(len(avals), *cshape), dims, coords=coords)
+        err = DataArray(np.sqrt(np.clip(var, 0.0, None)).reshape(len(avals), *cshape), dims, coords=coords)
+        return mean, err
+
+    def _target_sums(self, avals):
+        """(Q, B, ln sum_n w_an) of the targets: the covariance pass over the first observable column only."""
+        us, xs, _, _ = self._samples()
+        sol = self._solution()
+        x1 = [x[:, :1] for x in xs]
+        means = engine.mbar_predict(x1, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
+        Q, B, _, _, lnw = engine.mbar_cov_sums(x1, us, self.alpha0, sol, avals, means, with_lnw=True)
+        return Q, B, lnw
+
+    def free_energy_covariance(self) -> np.ndarray:
+        """The K x K matrix Theta of the sampled states: var(f_i - f_j) = Theta_ii + Theta_jj - 2 Theta_ij."""
+        if "mbar_theta" not in self._cache:
+            self._cache["mbar_theta"] = engine.mbar_theta(self._gram(), self._counts())
+        return self._cache["mbar_theta"].copy()
+
+    def free_energy(self, alpha=None, alpha_name=None):
+        """(f, df) relative to state 0 (pymbar's compute_free_energy_differences, row 0): of the sampled states
+        (``alpha=None``: the cached solution, df[0] = 0), or of the targets ``alpha``, f(a) = -ln sum_n e^{-a u_n - logD_n}."""
+        if alpha is None:
+            name = self.alpha_name if alpha_name is None else alpha_name
+            th = self.free_energy_covariance()
+            var = np.diag(th) + th[0, 0] - 2.0 * th[0]
+            var[0] = 0.0
+            coords = {name: np.asarray(self.alpha0, dtype=float)}
+            return (DataArray(np.array(self._solution().f, dtype=float), (name,), coords=coords),
+                    DataArray(np.sqrt(np.clip(var, 0.0, None)), (name,), coords=coords))
+        avals, alpha_name = self._alpha_values(alpha, alpha_name)
+        Q, B, lnw = self._target_sums(avals)
+        K, N, Gs = len(self.states), self._counts(), self._gram()
+        G = np.zeros((K + 1, K + 1))
+        G[:K, :K] = Gs
+        var = np.empty(len(avals))
+        for i in range(len(avals)):
+            G[:K, K] = G[K, :K] = B[i]
+            G[K, K] = Q[i]
+            th = engine.mbar_theta(G, np.append(N, 0.0))
+            var[i] = th[K, K] + th[0, 0] - 2.0 * th[0, K]
+        coords = {alpha_name: avals}
+        return (DataArray(-lnw - float(self._solution().f[0]), (alpha_name,), coords=coords),
+                DataArray(np.sqrt(np.clip(var, 0.0, None)), (alpha_name,), coords=coords))
+
+    def overlap(self) -> "MBAROverlap":
+        """The overlap matrix O = G diag(N_k) of the sampled states (rows sum to 1; O_jk: the share of state k's samples
+        in what state j sees), its eigenvalues in descending order and the scalar 1 - the second largest (pymbar's
+        compute_overlap): near 0 when the states fall into groups that share no samples.  K = 1 gives the scalar 1."""
+        return MBAROverlap(*engine.mbar_overlap(self._gram(), self._counts()))
+
+    def effective_samples(self, alpha, alpha_name=None):
+        """Kish's effective sample number of the pooled samples at every target: 1 / sum_n W_na^2."""
+        avals, alpha_name = self._alpha_values(alpha, alpha_name)
+        Q, _, _ = self._target_sums(avals)
+        return DataArray(1.0 / Q, (alpha_name,), coords={alpha_name: avals})
 
     def resample(self, *args, **kwargs):
         raise NotImplementedError("resample not implemented for this class (MBARModel.bootstrap gives the replicates)")
