@@ -565,6 +565,31 @@ int txm_lag_sums(const double *x, int64_t ldx_s, const double *u, int64_t n, int
                  const int32_t *pairs_host, int32_t n_pairs, int64_t t0, int32_t nlags, double *out, void *ws,
                  size_t ws_bytes, txm_stream stream);
 
+/* ---- (f-8) timeseries: the lag sums of every suffix, for equilibration detection -------------------------- */
+/* For n_series of the series {u, x_0 .. x_{C-1}} (index 0 is u, 1 + c is x_c; any order, a subset) and every origin
+ * j nskip, j = 0 .. n_origins - 1, n_origins = ceil((n - 1) / nskip) in [1, 4096]: the auto lag sum of the suffix
+ * a[j nskip : n], centred with the suffix's OWN mean m_j,
+ *   R_j(t) = 2 sum_{i = j nskip}^{n-1-t} (a_i - m_j)(a_{i+t} - m_j),   t = t0 .. t0 + nlags - 1
+ * (t0 and nlags multiples of 256, nlags <= 4096; lags >= n - j nskip give 0), so that origin j's statistical
+ * inefficiency follows from R_j exactly as in (f-7) with n - j nskip for n.
+ *   replaces the loop of pymbar.timeseries.detect_equilibration, which calls statistical_inefficiency on A_t[t0:] for
+ *   every origin t0 in range(0, T - 1, nskip): one pass over the samples here instead of one per origin.
+ * center (device, [1 + C]): one pivot p per series, ANY value near the data -- the series are centred on it once and
+ *   R_j(t) = 2 [Q_j(t) - delta_j X_j(t) + (n - j nskip - t) delta_j^2],  delta_j = m_j - p,
+ * with Q_j, X_j the lag sums of d = a - p with itself and with a series of ones over i >= j nskip.  The expansion loses
+ * what delta_j^2 / var(a) is large against: pass the mean of the part of the series that is in equilibrium (engine.py:
+ * the second half).  x is [n][ldx_s] row-major (pitch ldx_s >= C); x = NULL with C = 0 is legal.
+ * `series_host` is a HOST array of n_series indices; it is copied into the workspace by the call (not stream-capturable).
+ * out (device): [n_series][n_origins][nlags].  mean_out (device, [n_series][n_origins], may be NULL): the suffix means
+ * p + delta_j.  Each (segment, series, lag) partial is written once and the segments are added from the last to the first
+ * in index order, every delta_j comes from per-segment sums of d taken the same way: two runs give the same bits, and
+ * R_j(t) has the same bits whichever 256-aligned (t0, nlags) block it is computed in.  ws holds the 1 + C centred series
+ * (8 (1 + C) n bytes) and 16 n_origins n_series nlags bytes of partials. */
+size_t txm_lag_origin_sums_ws_bytes(int64_t n, int64_t C, int32_t n_series, int64_t nskip, int32_t nlags);
+int txm_lag_origin_sums(const double *x, int64_t ldx_s, const double *u, int64_t n, int64_t C, const double *center,
+                        const int32_t *series_host, int32_t n_series, int64_t nskip, int64_t t0, int32_t nlags,
+                        double *out, double *mean_out, void *ws, size_t ws_bytes, txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

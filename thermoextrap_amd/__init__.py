@@ -10,7 +10,7 @@ Layout
   symbolic.py  derivative recursion as exact polynomials -> device tables
   models.py    Derivatives, ExtrapModel, StateCollection, the multi-state models (InterpModel, MBARModel, ...)
   beta.py      factory_derivatives, factory_extrapmodel
-  timeseries.py  statistical inefficiency, subsampling and decorrelation of correlated series (pymbar.timeseries)
+  timeseries.py  statistical inefficiency, subsampling, decorrelation and equilibration detection of correlated series (pymbar.timeseries)
 """
 
 from ._lib import TxmError, load, require_gpu  # noqa: F401
@@ -24,6 +24,7 @@ _LAZY = {
     "DataArray": "xrlite", "Dataset": "xrlite",
     "statistical_inefficiency": "timeseries", "statistical_inefficiencies": "timeseries", "subsample_correlated_data": "timeseries",
     "normalized_fluctuation_correlation_function": "timeseries", "decorrelate": "timeseries",
+    "detect_equilibration": "timeseries", "detect_equilibrations": "timeseries", "equilibrate": "timeseries",
 }
 _MODULES = {"stack", "distributed", "gpr_input", "beta", "data", "models", "moments", "idealgas", "symbolic", "engine", "xrlite", "volume", "volume_idealgas", "lnpi", "timeseries"}
 

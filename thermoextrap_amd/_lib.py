@@ -148,6 +148,9 @@ SIGNATURES = {
     "txm_lag_sums_ws_bytes": (c_size, [c_i64, c_i64, ct.c_int32, ct.c_int32]),
     "txm_lag_sums": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, ct.POINTER(ct.c_int32), ct.c_int32, c_i64,
                              ct.c_int32, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_lag_origin_sums_ws_bytes": (c_size, [c_i64, c_i64, ct.c_int32, c_i64, ct.c_int32]),
+    "txm_lag_origin_sums": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, ct.POINTER(ct.c_int32), ct.c_int32,
+                                    c_i64, c_i64, ct.c_int32, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
 }
 
 ABI_VERSION = 2  # include/txmom.h TXM_ABI_VERSION

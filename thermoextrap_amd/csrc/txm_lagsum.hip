@@ -32,6 +32,25 @@
 // The chunk length is a function of n alone and a lag's products are accumulated in the same order whichever tile of
 // whichever (t0, nlags) block holds it (adding the +-0 products of the zero padding changes no bits): R(t) is bitwise
 // reproducible from run to run and across block schedules.
+//
+// Lag sums of every suffix (timeseries.detect_equilibration; pymbar.timeseries.detect_equilibration loops
+// statistical_inefficiency over the origins).  With the series centred once on a pivot p (d = a - p), the origin j * nskip,
+// M = n - j nskip and delta = mean(a[j nskip:]) - p,
+//   R_j(t) = 2 [Q_j(t) - delta X_j(t) + (M - t) delta^2],   Q_j(t) = sum_{i >= j nskip} d_i d_{i+t},
+//                                                           X_j(t) = sum_{i >= j nskip} (d_i + d_{i+t})      (i + t < n)
+// Q is the auto lag sum and X the symmetrised cross lag sum of d with a series of ones, both restricted to the "a" index
+// i >= j nskip: suffix sums over the segments [j nskip, (j + 1) nskip) of per-segment partials.  Four more kernels:
+//   lag_origin_kernel<NT>     the Toeplitz loop of lag_kernel with the chunks cut at the origins (the last segment runs to
+//                             n) and two accumulator tile sets from one staging of d: Q += A_d B_d, X += A_d B_1 + A_1 B_d
+//                             (three MFMAs per step and tile; the ones are made in the staging loop, 1 inside the segment /
+//                             below n and 0 elsewhere; products by 1.0 are exact).  The 16-sample groups of a stage that
+//                             lie wholly behind a short segment's end are skipped (they would add +-0 products).
+//   lag_origin_segsum_kernel  sum of d over each segment, a fixed tree; lag_origin_delta_kernel adds the segments from the
+//                             last to the first: delta_j, and the suffix means p + delta_j.
+//   lag_origin_scan_kernel    one thread per (series, lag) walks the segments from the last to the first, keeps the running
+//                             Q and X and writes R_j(t) of every origin (0 for t >= M).  Fixed order, no atomics.
+// Every delta comes from the segment sums, not from X_j(0), so a lag block needs no other block: R_j(t) has the same bits
+// whichever 256-aligned (t0, nlags) block it is computed in.
 #include <cstring>
 
 #include "txm_common.h"
@@ -45,6 +64,7 @@ constexpr int LG_L = 1008;            // samples per stage: LG_L / 4 + 4 = 256 s
 constexpr int LG_A = LG_L + 32;       // a stage: 16 zeros, the samples, 16 zeros
 constexpr int LG_MAX_CHUNKS = 512;
 constexpr int LG_MAX_LAGS = 4096;     // per call
+constexpr int LG_MAX_ORIGINS = 4096;  // per call (lag_origin_*)
 
 static inline int64_t lg_chunk_len(int64_t n) {  // a function of n alone
   const int64_t stages = cdiv(n, (int64_t)LG_L * LG_MAX_CHUNKS);
@@ -165,6 +185,144 @@ __global__ __launch_bounds__(LG_BLOCK) void lag_sum_kernel(const double *__restr
   out[(size_t)slot * nlags + t] = pairs[slot] > C ? acc : 2.0 * acc;
 }
 
+// partial: [segment][series][Q, X][nlags].  Segment j is [j nskip, (j + 1) nskip), the last one runs to n.
+template <int NT>
+__global__ __launch_bounds__(LG_BLOCK) void lag_origin_kernel(const double *__restrict__ d, int64_t ldd, int64_t n,
+                                                              const int32_t *__restrict__ series, int64_t nskip,
+                                                              int64_t t0, int nlags, double *__restrict__ partial) {
+  constexpr int NB = LG_L + 256 * NT;
+  constexpr int NBP = NB + NB / 16;
+  extern __shared__ double smem[];
+  const double *__restrict__ da = d + (int64_t)series[blockIdx.y] * ldd;
+  double *sa0 = smem, *sb0 = sa0 + LG_A, *sa1 = sb0 + NBP, *sb1 = sa1 + LG_A;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int m = lane & 15, k = lane >> 4;
+  const int64_t cb = (int64_t)blockIdx.x * nskip;
+  const int64_t ce = blockIdx.x + 1 == gridDim.x ? n : cb + nskip;
+  const int64_t tg = t0 + (int64_t)blockIdx.z * (256 * NT);
+  lg_v4d accq[NT], accx[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) accq[j] = accx[j] = lg_v4d{0.0, 0.0, 0.0, 0.0};
+  for (int64_t c = cb; c < ce && c + tg < n; c += LG_L) {
+    const int64_t aend = c + LG_L < ce ? c + LG_L : ce;
+    __syncthreads();
+    for (int j = tid; j < LG_A; j += LG_BLOCK) {
+      const int64_t i = c - 16 + j;
+      const bool in = i >= c && i < aend;
+      sa0[j] = in ? da[i] : 0.0;
+      sa1[j] = in ? 1.0 : 0.0;
+    }
+    for (int q = tid; q < NB; q += LG_BLOCK) {
+      const int64_t i = c + tg + q;
+      const bool in = i < n;
+      sb0[q + (q >> 4)] = in ? da[i] : 0.0;
+      sb1[q + (q >> 4)] = in ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    // (the steps of group g read the stage's samples 16 g - 15 .. 16 g + 15: nothing but zeros once 16 g - 15 >= len)
+    const int gend = (int)((aend - c + 30) / 16);
+    const int glast = gend < 16 * wave + 16 ? gend : 16 * wave + 16;
+    const double *pa0 = sa0 + 16 + k - m, *pa1 = sa1 + 16 + k - m;
+    const double *pb0 = sb0 + k + 17 * m, *pb1 = sb1 + k + 17 * m;
+    for (int g = 16 * wave; g < glast; ++g) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double a0 = pa0[16 * g + 4 * r];
+        const double a1 = pa1[16 * g + 4 * r];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          const double b0 = pb0[17 * g + 4 * r + 272 * j];
+          const double b1 = pb1[17 * g + 4 * r + 272 * j];
+          accq[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, accq[j], 0, 0, 0);
+          accx[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, accx[j], 0, 0, 0);
+          accx[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, accx[j], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // the four waves' tiles, added in wave order: Q, then X through the same LDS
+  double *dst = partial + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 2 * nlags + (size_t)blockIdx.z * (256 * NT);
+#pragma unroll
+  for (int set = 0; set < 2; ++set) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) smem[(wave * NT + j) * 256 + 16 * m + k + 4 * r] = set ? accx[j][r] : accq[j][r];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      double v = smem[j * 256 + tid];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) v += smem[(w * NT + j) * 256 + tid];
+      dst[(size_t)set * nlags + j * 256 + tid] = v;
+    }
+  }
+}
+
+// segsum: [series][segment]
+__global__ __launch_bounds__(LG_BLOCK) void lag_origin_segsum_kernel(const double *__restrict__ d, int64_t ldd, int64_t n,
+                                                                     const int32_t *__restrict__ series, int64_t nskip,
+                                                                     double *__restrict__ segsum) {
+  __shared__ double red[LG_BLOCK];
+  const double *__restrict__ da = d + (int64_t)series[blockIdx.y] * ldd;
+  const int tid = threadIdx.x;
+  const int64_t cb = (int64_t)blockIdx.x * nskip;
+  const int64_t ce = blockIdx.x + 1 == gridDim.x ? n : cb + nskip;
+  double acc = 0.0;
+  for (int64_t i = cb + tid; i < ce; i += LG_BLOCK) acc += da[i];
+  red[tid] = acc;
+  __syncthreads();
+  for (int w = LG_BLOCK / 2; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) segsum[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+}
+
+// delta, mean_out: [series][origin]
+__global__ __launch_bounds__(LG_BLOCK) void lag_origin_delta_kernel(const double *__restrict__ segsum,
+                                                                    const double *__restrict__ center,
+                                                                    const int32_t *__restrict__ series, int n_series,
+                                                                    int n_origins, int64_t n, int64_t nskip,
+                                                                    double *__restrict__ delta, double *__restrict__ mean_out) {
+  const int s = blockIdx.x * LG_BLOCK + threadIdx.x;
+  if (s >= n_series) return;
+  const double p = center[series[s]];
+  double acc = 0.0;
+  for (int j = n_origins - 1; j >= 0; --j) {
+    acc += segsum[(size_t)s * n_origins + j];
+    const double dl = acc / (double)(n - (int64_t)j * nskip);
+    delta[(size_t)s * n_origins + j] = dl;
+    if (mean_out) mean_out[(size_t)s * n_origins + j] = p + dl;
+  }
+}
+
+// out: [series][origin][nlags]
+__global__ __launch_bounds__(LG_BLOCK) void lag_origin_scan_kernel(const double *__restrict__ partial,
+                                                                   const double *__restrict__ delta, int n_series,
+                                                                   int n_origins, int64_t n, int64_t nskip, int64_t t0,
+                                                                   int nlags, double *__restrict__ out) {
+  const int t = blockIdx.x * LG_BLOCK + threadIdx.x, s = blockIdx.y;
+  const int64_t lag = t0 + t;
+  double q = 0.0, x = 0.0;
+  for (int j = n_origins - 1; j >= 0; --j) {
+    const double *__restrict__ p = partial + ((size_t)j * n_series + s) * 2 * nlags + t;
+    q += p[0];
+    x += p[nlags];
+    const int64_t M = n - (int64_t)j * nskip;
+    const double dl = delta[(size_t)s * n_origins + j];
+    out[((size_t)s * n_origins + j) * nlags + t] = lag < M ? 2.0 * (q - dl * x + (double)(M - lag) * dl * dl) : 0.0;
+  }
+}
+
+static inline int64_t lgo_origins(int64_t n, int64_t nskip) { return n >= 2 && nskip >= 1 ? cdiv(n - 1, nskip) : 0; }
+static bool lgo_shape_ok(int64_t n, int64_t C, int32_t n_series, int64_t nskip, int32_t nlags) {
+  const int64_t no = lgo_origins(n, nskip);
+  return n >= 2 && n <= ((int64_t)1 << 36) && C >= 0 && C <= 16383 && n_series >= 1 && n_series <= C + 1 && no >= 1 &&
+         no <= LG_MAX_ORIGINS && nlags >= 256 && nlags <= LG_MAX_LAGS && nlags % 256 == 0;
+}
+
 static bool lg_shape_ok(int64_t n, int64_t C, int32_t n_pairs, int32_t nlags) {
   return n >= 1 && n <= ((int64_t)1 << 36) && C >= 0 && C <= 16383 && n_pairs >= 1 && n_pairs <= 2 * C + 1 && nlags >= 256 &&
          nlags <= LG_MAX_LAGS && nlags % 256 == 0;
@@ -238,6 +396,76 @@ extern "C" int txm_lag_sums(const double *x, int64_t ldx_s, const double *u, int
 #undef TXM_LG
   hipLaunchKernelGGL(lag_sum_kernel, dim3((unsigned)(nlags / LG_BLOCK), (unsigned)n_pairs), dim3(LG_BLOCK), 0, st, partial,
                      (int)nchunks, (int)C, pairs, (int)n_pairs, (int)nlags, out);
+  TXM_LAUNCH_CHECK();
+  return TXM_OK;
+}
+
+extern "C" size_t txm_lag_origin_sums_ws_bytes(int64_t n, int64_t C, int32_t n_series, int64_t nskip, int32_t nlags) {
+  if (!lgo_shape_ok(n, C, n_series, nskip, nlags)) return 0;
+  const size_t no = (size_t)lgo_origins(n, nskip);
+  const size_t head = align_up((size_t)n_series * sizeof(int32_t), 256);
+  const size_t rows = (size_t)(1 + C) * (size_t)lg_ldd(n) * sizeof(double);
+  const size_t sums = 2 * (size_t)n_series * no * sizeof(double);  // segment sums, deltas
+  return head + rows + sums + no * (size_t)n_series * 2 * (size_t)nlags * sizeof(double) + 256;
+}
+
+extern "C" int txm_lag_origin_sums(const double *x, int64_t ldx_s, const double *u, int64_t n, int64_t C,
+                                   const double *center, const int32_t *series_host, int32_t n_series, int64_t nskip,
+                                   int64_t t0, int32_t nlags, double *out, double *mean_out, void *ws, size_t ws_bytes,
+                                   txm_stream stream) {
+  TXM_REQUIRE(u && center && series_host && out && ws, "lag_origin_sums: null pointer");
+  TXM_REQUIRE(n >= 2 && n <= ((int64_t)1 << 36), "lag_origin_sums: n = %lld outside [2, 2^36]", (long long)n);
+  TXM_REQUIRE(C >= 0 && C <= 16383, "lag_origin_sums: C = %lld outside [0, 16383]", (long long)C);
+  TXM_REQUIRE(C == 0 || x, "lag_origin_sums: null x with C = %lld columns", (long long)C);
+  TXM_REQUIRE(C == 0 || ldx_s >= C, "lag_origin_sums: row pitch ldx_s = %lld < C = %lld", (long long)ldx_s, (long long)C);
+  TXM_REQUIRE(n_series >= 1 && n_series <= C + 1, "lag_origin_sums: n_series = %d outside [1, 1 + C = %lld]", (int)n_series,
+              (long long)(C + 1));
+  for (int32_t s = 0; s < n_series; ++s)
+    TXM_REQUIRE(series_host[s] >= 0 && series_host[s] <= C, "lag_origin_sums: series index %d (entry %d) outside [0, C = %lld]",
+                (int)series_host[s], (int)s, (long long)C);
+  TXM_REQUIRE(nskip >= 1, "lag_origin_sums: nskip = %lld < 1", (long long)nskip);
+  const int64_t no = lgo_origins(n, nskip);
+  TXM_REQUIRE(no <= LG_MAX_ORIGINS, "lag_origin_sums: nskip = %lld gives %lld origins, more than %d (smallest legal nskip: %lld)",
+              (long long)nskip, (long long)no, LG_MAX_ORIGINS, (long long)cdiv(n - 1, (int64_t)LG_MAX_ORIGINS));
+  TXM_REQUIRE(t0 >= 0 && t0 % 256 == 0 && t0 <= ((int64_t)1 << 36),
+              "lag_origin_sums: t0 = %lld is not a multiple of 256 in [0, 2^36]", (long long)t0);
+  TXM_REQUIRE(nlags >= 256 && nlags % 256 == 0 && nlags <= LG_MAX_LAGS,
+              "lag_origin_sums: nlags = %d is not a multiple of 256 in [256, %d]", (int)nlags, LG_MAX_LAGS);
+  if (ws_bytes < txm_lag_origin_sums_ws_bytes(n, C, n_series, nskip, nlags)) {
+    set_error("lag_origin_sums: workspace too small");
+    return TXM_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t head = align_up((size_t)n_series * sizeof(int32_t), 256);
+  const int64_t ldd = lg_ldd(n);
+  int32_t *series = (int32_t *)ws;
+  double *d = (double *)((char *)ws + head);
+  double *segsum = d + (size_t)(1 + C) * ldd;
+  double *delta = segsum + (size_t)n_series * no;
+  double *partial = delta + (size_t)n_series * no;
+  TXM_HIP(hipMemcpyAsync(series, series_host, (size_t)n_series * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const int64_t cblocks = C > 0 ? cdiv(C, 32) : 1;
+  hipLaunchKernelGGL(lag_center_kernel, dim3((unsigned)cdiv(n, 64), (unsigned)cblocks), dim3(LG_BLOCK), 0, st, x, ldx_s,
+                     u, n, C, center, d, ldd);
+  TXM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lag_origin_segsum_kernel, dim3((unsigned)no, (unsigned)n_series), dim3(LG_BLOCK), 0, st, d, ldd, n,
+                     series, nskip, segsum);
+  TXM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lag_origin_delta_kernel, dim3((unsigned)cdiv(n_series, LG_BLOCK)), dim3(LG_BLOCK), 0, st, segsum, center,
+                     series, (int)n_series, (int)no, n, nskip, delta, mean_out);
+  TXM_LAUNCH_CHECK();
+  const int nt = lg_tiles(nlags);
+  const dim3 grid((unsigned)no, (unsigned)n_series, (unsigned)(nlags / (256 * nt))), block(LG_BLOCK);
+#define TXM_LGO(NT_)                                                                                               \
+  hipLaunchKernelGGL((lag_origin_kernel<NT_>), grid, block, lg_lds_bytes(NT_, true), st, d, ldd, n, series, nskip, \
+                     t0, (int)nlags, partial)
+  if (nt == 4) TXM_LGO(4);
+  else if (nt == 2) TXM_LGO(2);
+  else TXM_LGO(1);
+#undef TXM_LGO
+  TXM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lag_origin_scan_kernel, dim3((unsigned)(nlags / LG_BLOCK), (unsigned)n_series), dim3(LG_BLOCK), 0, st,
+                     partial, delta, (int)n_series, (int)no, n, nskip, t0, (int)nlags, out);
   TXM_LAUNCH_CHECK();
   return TXM_OK;
 }

@@ -1482,12 +1482,8 @@ def lag_center(x: torch.Tensor | None, u: torch.Tensor) -> torch.Tensor:
     return torch.cat([st[0, 0, 1:2], st[:, 1, 0]]).contiguous()
 
 
-def lag_sums(x: torch.Tensor | None, u: torch.Tensor, pairs, t0: int, nlags: int, center: torch.Tensor | None = None) -> torch.Tensor:
-    """R(t) = sum_i (da_i db_{i+t} + db_i da_{i+t}) of the centred series, t = t0 .. t0 + nlags - 1, for every pair of
-    ``pairs``: index 0 is (u, u), 1 + c is (x_c, x_c), 1 + C + c is (x_c, u).  x: (N, C) row-major (any row pitch), (N,)
-    or None; u: (N,).  Returns (len(pairs), nlags); lags >= N are 0.  Bitwise reproducible, and independent of how the
-    lags are cut into 256-aligned calls."""
-    L = _L()
+def _lag_series_args(x, u):
+    """(x2, u, N, C, row pitch) as txm_lag_sums and txm_lag_origin_sums take them."""
     _check_f64_cuda(u, "u")
     if u.dim() != 1:
         raise ValueError("u must be (N,)")
@@ -1506,6 +1502,16 @@ def lag_sums(x: torch.Tensor | None, u: torch.Tensor, pairs, t0: int, nlags: int
             if x2.stride(1) != 1 or (N > 1 and x2.stride(0) < C):
                 x2 = x2.contiguous()
             ls = max(x2.stride(0), C) if N > 1 else C
+    return x2, u, N, C, ls
+
+
+def lag_sums(x: torch.Tensor | None, u: torch.Tensor, pairs, t0: int, nlags: int, center: torch.Tensor | None = None) -> torch.Tensor:
+    """R(t) = sum_i (da_i db_{i+t} + db_i da_{i+t}) of the centred series, t = t0 .. t0 + nlags - 1, for every pair of
+    ``pairs``: index 0 is (u, u), 1 + c is (x_c, x_c), 1 + C + c is (x_c, u).  x: (N, C) row-major (any row pitch), (N,)
+    or None; u: (N,).  Returns (len(pairs), nlags); lags >= N are 0.  Bitwise reproducible, and independent of how the
+    lags are cut into 256-aligned calls."""
+    L = _L()
+    x2, u, N, C, ls = _lag_series_args(x, u)
     if center is None:
         center = lag_center(x2, u)
     _check_f64_cuda(center, "center")
@@ -1521,3 +1527,61 @@ def lag_sums(x: torch.Tensor | None, u: torch.Tensor, pairs, t0: int, nlags: int
     check(L.txm_lag_sums(_ptr(x2), ls, _ptr(u), N, C, _ptr(center), pl.ctypes.data_as(ct.POINTER(ct.c_int32)), pl.size,
                          int(t0), int(nlags), _ptr(out), _ptr(ws), ws.numel(), _stream()), "txm_lag_sums")
     return out
+
+
+LAG_MAX_ORIGINS = 4096  # origins per call of lag_origin_sums (txm_lagsum.hip: LG_MAX_ORIGINS)
+
+
+def lag_origin_center(x: torch.Tensor | None, u: torch.Tensor) -> torch.Tensor:
+    """The default pivots of ``lag_origin_sums``, (1 + C,): the mean of the SECOND HALF of each series."""
+    h = u.shape[0] // 2
+    return lag_center(None if x is None else (x.unsqueeze(1) if x.dim() == 1 else x)[h:], u[h:])
+
+
+def lag_origin_sums(x: torch.Tensor | None, u: torch.Tensor, series, nskip: int, t0: int, nlags: int,
+                    center: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The auto lag sums of every suffix: for each series of ``series`` (0 is u, 1 + c is x_c) and each origin
+    j * nskip in range(0, N - 1, nskip), R_j(t) = 2 sum_i (a_i - m_j)(a_{i+t} - m_j) over the suffix a[j nskip:] centred
+    with its own mean m_j, t = t0 .. t0 + nlags - 1 (multiples of 256; lags beyond the suffix give 0).  Returns
+    (R (len(series), n_origins, nlags), suffix means (len(series), n_origins)) from one pass over the samples.
+
+    ``center`` (1 + C,) is the pivot the series are centred on once; R_j is expanded around it (txmom.h, (f-8)).  None:
+    the mean of the second half of each series -- the origins that matter lie past the transient, so their
+    delta_j = m_j - pivot nearly vanishes and R_j is not a difference of large terms.
+
+    When the workspace for ``nlags`` exceeds ``workspace_budget()`` the call is made in shorter lag blocks; the bits do
+    not depend on that (nor on how the caller cuts the lags into 256-aligned calls), and two runs give the same bits."""
+    L = _L()
+    x2, u, N, C, ls = _lag_series_args(x, u)
+    if center is None:
+        center = lag_origin_center(x2, u)
+    _check_f64_cuda(center, "center")
+    if center.shape != (1 + C,):
+        raise ValueError(f"center must have shape ({1 + C},), got {tuple(center.shape)}")
+    center = center.contiguous()
+    sl = np.ascontiguousarray(np.atleast_1d(np.asarray(series)).astype(np.int32))
+    if sl.ndim != 1 or sl.size == 0:
+        raise ValueError("series must be a non-empty list of series indices")
+    nskip, t0, nlags = int(nskip), int(t0), int(nlags)
+    no = -(-(N - 1) // nskip) if N >= 2 and nskip >= 1 else 0   # len(range(0, N - 1, nskip))
+    from .timeseries import pick_nskip
+
+    pick_nskip(N, nskip)          # (ValueError before anything of n_origins x nlags is allocated)
+    step = nlags
+    if nlags >= 2 * LAG_BLOCK and L.txm_lag_origin_sums_ws_bytes(N, C, sl.size, nskip, nlags) > workspace_budget():
+        step = LAG_BLOCK
+        for cand in (2048, 1024, 512):
+            if cand < nlags and nlags % cand == 0 and L.txm_lag_origin_sums_ws_bytes(N, C, sl.size, nskip, cand) <= workspace_budget():
+                step = cand
+                break
+    out = torch.empty((sl.size, no, nlags), dtype=F64, device="cuda")
+    mean = torch.empty((sl.size, no), dtype=F64, device="cuda")
+    ws = workspace(L.txm_lag_origin_sums_ws_bytes(N, C, sl.size, nskip, step), tag="lag")
+    sp = sl.ctypes.data_as(ct.POINTER(ct.c_int32))
+    for off in range(0, nlags, step):
+        part = out if step == nlags else torch.empty((sl.size, no, step), dtype=F64, device="cuda")
+        check(L.txm_lag_origin_sums(_ptr(x2), ls, _ptr(u), N, C, _ptr(center), sp, sl.size, nskip, t0 + off, step, _ptr(part),
+                                    _ptr(mean), _ptr(ws), ws.numel(), _stream()), "txm_lag_origin_sums")
+        if part is not out:
+            out[:, :, off:off + step] = part
+    return out, mean

@@ -8,7 +8,10 @@ energy) pair, the largest of them as g, ``subsample_correlated_data`` with it, a
   statistical_inefficiency, normalized_fluctuation_correlation_function, subsample_correlated_data
       pymbar.timeseries' functions of the same names (unweighted series);
   statistical_inefficiencies(uv, xv)   all 2C + 1 pairs of a state through one set of launches;
-  decorrelate(uv, xv, w)               what get_data lines 253-269 do, the gather on the device.
+  decorrelate(uv, xv, w)               what get_data lines 253-269 do, the gather on the device;
+  detect_equilibration                 pymbar.timeseries' function of that name: where the initial transient ends;
+  detect_equilibrations(uv, xv)        the same for the energy and every observable column in one set of launches;
+  equilibrate(uv, xv, w)               drops the transient on the device; its output feeds decorrelate unchanged.
 
 The estimator.  dA = A - mean(A), dB = B - mean(B) (B = A when omitted), sigma^2 = mean(dA dB) (0 raises ValueError),
 
@@ -26,6 +29,13 @@ over t runs on the host over blocks of lags -- 256, 256, 512, 1024, ... lags, ea
 the next call's list; the scan ends when every pair has stopped or t reaches N - 1.  R(t) has the same bits in whichever
 block it is computed, so g does not depend on the schedule.  There is no CPU path: every function that takes series needs
 the device (``require_gpu``), as everywhere in this package.
+
+Equilibration (Chodera 2016).  For the origins t0 in range(0, T - 1, nskip): g(t0) = statistical_inefficiency(A[t0:]) (the
+estimator above on the suffix, centred with the suffix's own mean; a suffix of zero variance gives g = T - t0 + 1),
+Neff(t0) = (T - t0 + 1) / g(t0); the answer is the origin of the largest Neff (the first on a tie); a series of zero variance
+gives (0, 1, 1).  The lag sums of EVERY origin come from one pass over the samples per lag block (engine.lag_origin_sums ->
+txm_lag_origin_sums: per-segment partials, a suffix scan over the segments), not from one scan per origin; the host runs the
+loop above once per (series, origin) over one fetch of [series][origins][lags] per block.
 """
 
 from __future__ import annotations
@@ -37,6 +47,19 @@ import numpy as np
 
 LAG_BLOCK = 256
 LAG_MAX_LAGS = 4096
+
+
+class Equilibration(NamedTuple):
+    """What ``detect_equilibrations`` returns, series 0 the energy and 1 + c column c.  ``t0_max``: the largest detected
+    origin -- the conservative choice, as ``decorrelate`` takes the largest g."""
+
+    t0: np.ndarray         # (1 + C,) int64: the origin of the largest Neff
+    g: np.ndarray          # (1 + C,)  g of the series from there on
+    neff: np.ndarray       # (1 + C,)  (T - t0 + 1) / g
+    t0_max: int
+    origins: np.ndarray    # (1 + C, n_origins) int64: the origins tested, range(0, T - 1, nskip)
+    g_t: np.ndarray        # (1 + C, n_origins)
+    neff_t: np.ndarray     # (1 + C, n_origins)
 
 
 class Inefficiencies(NamedTuple):
@@ -64,6 +87,24 @@ def lag_blocks(n: int):
             return
 
 
+def _scan_block(R, t0: int, nl: int, n: int, sig2, tk: int, ik: int, gk, fast: bool, mintime: int, max_lag, name):
+    """The loop for g of one series of length n over one block R = R(t0 .. t0 + nl - 1) of its lag sums, from the state
+    (t, inc, g) the previous block left.  Returns (t, inc, g, done): done when the loop has ended inside this block."""
+    while tk < t0 + nl:
+        if tk >= n - 1:
+            return tk, ik, gk, True
+        if max_lag is not None and tk > max_lag:
+            raise ValueError(f"the correlation function of {name} has not crossed zero by max_lag = {max_lag}")
+        c = R[tk - t0] / (2.0 * (n - tk) * sig2)
+        if c <= 0.0 and tk > mintime:
+            return tk, ik, gk, True
+        gk += 2.0 * c * (1.0 - tk / n) * ik
+        tk += ik
+        if fast:
+            ik += 1
+    return tk, ik, gk, False
+
+
 def scan_lag_sums(fetch: Callable[[list, int, int], np.ndarray], n: int, pair_ids, *, fast: bool = False, mintime: int = 3,
                   max_lag: int | None = None, names=None):
     """The loop for g over blocks of lag sums.  ``fetch(pairs, t0, nlags)`` returns R(t0 .. t0 + nlags - 1) of the listed
@@ -89,26 +130,107 @@ def scan_lag_sums(fetch: Callable[[list, int, int], np.ndarray], n: int, pair_id
                 sig2[k] = R[row, 0] / (2.0 * n)
                 if sig2[k] == 0.0:
                     raise ValueError(f"sample covariance sigma_AB^2 = 0 for {names[k]}: cannot compute the statistical inefficiency")
-            tk, ik, gk, done = int(t[k]), int(inc[k]), g[k], False
-            while tk < t0 + nl:
-                if tk >= n - 1:
-                    done = True
-                    break
-                if max_lag is not None and tk > max_lag:
-                    raise ValueError(f"the correlation function of {names[k]} has not crossed zero by max_lag = {max_lag}")
-                c = R[row, tk - t0] / (2.0 * (n - tk) * sig2[k])
-                if c <= 0.0 and tk > mintime:
-                    done = True
-                    break
-                gk += 2.0 * c * (1.0 - tk / n) * ik
-                tk += ik
-                if fast:
-                    ik += 1
+            tk, ik, gk, done = _scan_block(R[row], t0, nl, n, sig2[k], int(t[k]), int(inc[k]), g[k], fast, mintime, max_lag, names[k])
             t[k], inc[k], g[k] = tk, ik, gk
             if not done and tk < n - 1:
                 still.append(k)
         active = still
     return np.maximum(g, 1.0), t
+
+
+def origin_count(T: int, nskip: int) -> int:
+    """len(range(0, T - 1, nskip))."""
+    return -(-(int(T) - 1) // int(nskip)) if T >= 2 else 0
+
+
+def pick_nskip(T: int, nskip: int | None = None, max_origins: int = 512) -> int:
+    """The origin step of ``detect_equilibration``: the given one, or (None) the smallest that gives at most ``max_origins``
+    origins.  ValueError for a series of fewer than 2 records and for a step that needs more origins than one device call
+    takes (engine.LAG_MAX_ORIGINS = 4096)."""
+    from .engine import LAG_MAX_ORIGINS as most
+
+    T = int(T)
+    if T < 2:
+        raise ValueError(f"a series of {T} record(s) has no origin to test")
+    if nskip is None:
+        if not 1 <= int(max_origins) <= most:
+            raise ValueError(f"max_origins = {max_origins} outside [1, {most}]")
+        return max(1, -(-(T - 1) // int(max_origins)))
+    nskip = int(nskip)
+    if nskip < 1:
+        raise ValueError(f"nskip = {nskip} < 1")
+    if origin_count(T, nskip) > most:
+        raise ValueError(f"nskip = {nskip} gives {origin_count(T, nskip)} origins for T = {T}, more than {most} per call: "
+                         f"the smallest legal nskip is {-(-(T - 1) // most)}")
+    return nskip
+
+
+def _expansion_bound(R0: float, M: int, delta: float) -> float:
+    """1e-12 * 2 (sqrt(Q) + sqrt(M) |delta|)^2 with Q = R0 / 2 + M delta^2: what R_j(0) of a pivot expansion is good to."""
+    q = max(0.5 * R0 + M * delta * delta, 0.0)
+    return 2e-12 * (math.sqrt(q) + math.sqrt(M) * abs(delta)) ** 2
+
+
+def scan_origin_lag_sums(fetch: Callable[[list, int, int], np.ndarray], n: int, nskip: int, series_ids, *, fast: bool = True,
+                         mintime: int = 3):
+    """``scan_lag_sums`` for every suffix of every listed series.  ``fetch(series, t0, nlags)`` returns R_j(t0 .. t0 + nlags - 1)
+    of the suffixes A[j nskip:] as a (len(series), n_origins, nlags) float64 array (the device call, or numpy in the CPU
+    tests).  Each (series, origin) runs the loop for g with its own length M = n - j nskip; a suffix with sigma^2 == 0 takes
+    g = M + 1 (pymbar's fallback in detect_equilibration).  A series leaves the fetch list when all its origins have stopped.
+
+    A fetch that expands R_j around a pivot (the device: R = 2 [Q - delta X + (M - t) delta^2]) gets a constant suffix away
+    from the pivot to zero only up to rounding.  Such a fetch returns (R, delta) on the block t0 == 0, delta
+    (len(series), n_origins) the suffix means minus the pivot, and sigma^2 counts as 0 when |R_j(0)| is within the
+    expansion's own rounding bound 1e-12 * 2 sum (|d| + |delta|)^2 <= 1e-12 * 2 (sqrt(Q_j(0)) + sqrt(M) |delta|)^2, with
+    Q_j(0) = R_j(0) / 2 + M delta^2 (the bound the device is tested to).  With delta == 0 that is R_j(0) == 0.
+
+    Returns (g, stop, zero): (len(series_ids), n_origins) arrays; ``zero`` marks the fallback."""
+    series_ids = [int(p) for p in series_ids]
+    m, no = len(series_ids), origin_count(n, nskip)
+    M = n - nskip * np.arange(no, dtype=np.int64)
+    g = np.ones((m, no))
+    t = np.ones((m, no), dtype=np.int64)
+    inc = np.ones((m, no), dtype=np.int64)
+    sig2 = np.zeros((m, no))
+    zero = np.zeros((m, no), dtype=bool)
+    live = [[j for j in range(no)] for _ in range(m)]      # the origins of each series whose loop has not ended
+    for t0, nl in lag_blocks(n):
+        active = [k for k in range(m) if live[k]]
+        if not active:
+            break
+        R = fetch([series_ids[k] for k in active], t0, nl)
+        delta = None
+        if isinstance(R, tuple):
+            R, delta = R
+        R = np.asarray(R, dtype=np.float64)
+        if R.shape != (len(active), no, nl):
+            raise ValueError(f"fetch returned {R.shape}, expected {(len(active), no, nl)}")
+        for row, k in enumerate(active):
+            still = []
+            for j in live[k]:
+                Mj = int(M[j])
+                if t0 == 0:
+                    sig2[k, j] = R[row, j, 0] / (2.0 * Mj)
+                    if abs(R[row, j, 0]) <= _expansion_bound(R[row, j, 0], Mj, 0.0 if delta is None else delta[row][j]):
+                        g[k, j], zero[k, j] = Mj + 1.0, True
+                        continue
+                tk, ik, gk, done = _scan_block(R[row, j], t0, nl, Mj, sig2[k, j], int(t[k, j]), int(inc[k, j]), g[k, j], fast,
+                                               mintime, None, None)
+                t[k, j], inc[k, j], g[k, j] = tk, ik, gk
+                if not done and tk < Mj - 1:
+                    still.append(j)
+            live[k] = still
+    return np.where(zero, g, np.maximum(g, 1.0)), t, zero
+
+
+def pick_origin(M, g, zero):
+    """(index, g, Neff) of the origin with the largest Neff = (M + 1) / g, the first on a tie, and the Neff of every origin;
+    a series whose first suffix -- the whole series -- has zero variance gives (0, 1.0, 1.0)."""
+    neff = (np.asarray(M, dtype=np.float64) + 1.0) / g
+    if zero[0]:
+        return 0, 1.0, 1.0, neff
+    j = int(np.argmax(neff))
+    return j, float(g[j]), float(neff[j]), neff
 
 
 def subsample_correlated_data(A_t, g: float | None = None, fast: bool = False, conservative: bool = False) -> np.ndarray:
@@ -285,4 +407,73 @@ def decorrelate(uv, xv, w=None, *, g: float | None = None, conservative: bool = 
     else:
         outs = [None if t is None else DataArray(t.cpu().numpy(), d) for t, d in zip(outs, dims)]
     info = {"g": float(g), "indices": idx, "n": int(idx.size), "inefficiencies": ineff}
+    return outs[0], outs[1], outs[2], info
+
+
+def detect_equilibrations(uv, xv, *, fast: bool = True, nskip: int | None = None, mintime: int = 3,
+                          max_origins: int = 512) -> Equilibration:
+    """``detect_equilibration`` of the energy series uv (rec) and of every column of xv (rec, val; may be None): the 1 + C
+    auto series through one set of launches per lag block.  See ``detect_equilibration`` for nskip and max_origins."""
+    from . import engine
+
+    u, x, _ = _prepare(uv, xv)
+    C = 0 if x is None else x.shape[1]
+    n = u.shape[0]
+    nskip = pick_nskip(n, nskip, max_origins)
+    center = engine.lag_origin_center(x, u)
+
+    def fetch(series, t0, nlags):
+        R, mean = engine.lag_origin_sums(x, u, series, nskip, t0, nlags, center=center)
+        if t0 == 0:
+            return R.cpu().numpy(), (mean - center[list(series)][:, None]).cpu().numpy()
+        return R.cpu().numpy()
+
+    g_t, _, zero = scan_origin_lag_sums(fetch, n, nskip, range(1 + C), fast=fast, mintime=mintime)
+    origins = nskip * np.arange(g_t.shape[1], dtype=np.int64)
+    picks = [pick_origin(n - origins, g_t[s], zero[s]) for s in range(1 + C)]
+    t0 = np.array([origins[p[0]] for p in picks], dtype=np.int64)
+    return Equilibration(t0, np.array([p[1] for p in picks]), np.array([p[2] for p in picks]), int(t0.max()),
+                         np.tile(origins, (1 + C, 1)), g_t, np.stack([p[3] for p in picks]))
+
+
+def detect_equilibration(A_t, fast: bool = True, nskip: int | None = None, *, mintime: int = 3, max_origins: int = 512):
+    """pymbar.timeseries.detect_equilibration: (t, g, Neff_max) -- the origin t in range(0, T - 1, nskip) from which the
+    series has the most uncorrelated samples, its statistical inefficiency from there on, and that number of samples.
+    nskip None picks the smallest step that gives at most ``max_origins`` origins (pymbar's default of 1 tests every record,
+    which is O(T^2) there and T origins here); an explicit nskip that needs more than 4096 origins raises ValueError."""
+    e = detect_equilibrations(A_t, None, fast=fast, nskip=nskip, mintime=mintime, max_origins=max_origins)
+    return int(e.t0[0]), float(e.g[0]), float(e.neff[0])
+
+
+def equilibrate(uv, xv, w=None, *, t0: int | None = None, **kw):
+    """Drop the initial transient of (uv, xv, w) on the device: the first ``t0`` records, by default
+    ``detect_equilibrations(uv, xv, **kw).t0_max``.  Returns (uv, xv, w, info) of the kinds and dims ``decorrelate`` returns --
+    they feed ``decorrelate`` and then ``from_vals`` unchanged -- and info = {"t0", "n", "equilibration"}."""
+    from .moments import DeviceDataArray
+    from .xrlite import DataArray
+
+    u, x, kind = _prepare(uv, xv)
+    if x is None:
+        raise TypeError("xv is required")
+    wt = None
+    if w is not None:
+        wt, _ = _device_series(w, 1, "w")
+        if wt.shape != u.shape:
+            raise ValueError(f"w has {wt.shape[0]} records, uv {u.shape[0]}")
+    eq = None
+    if t0 is None:
+        eq = detect_equilibrations(u, x, **kw)
+        t0 = eq.t0_max
+    elif kw:
+        raise TypeError(f"keywords {sorted(kw)} only apply when t0 is detected")
+    t0 = int(t0)
+    if not 0 <= t0 < u.shape[0]:
+        raise ValueError(f"t0 = {t0} outside [0, {u.shape[0] - 1}]")
+    outs = [u[t0:].contiguous(), x[t0:].contiguous(), None if wt is None else wt[t0:].contiguous()]
+    dims = [("rec",), ("rec", "val"), ("rec",)]
+    if kind == "device":
+        outs = [None if a is None else DeviceDataArray(a, d) for a, d in zip(outs, dims)]
+    else:
+        outs = [None if a is None else DataArray(a.cpu().numpy(), d) for a, d in zip(outs, dims)]
+    info = {"t0": t0, "n": int(u.shape[0] - t0), "equilibration": eq}
     return outs[0], outs[1], outs[2], info
