@@ -97,6 +97,9 @@ int launch_count_table(const uint32_t *counts, int64_t nrep, int64_t N, uint32_t
 bool i8g_applicable(const double *x, int64_t ldx_s, int64_t C, const double *y, int64_t ldy_s);  // C = all columns of the call
 int launch_resample_i8g(const I8Args &a, int K, bool weighted, const unsigned char *table, int64_t rep_begin, int n_grp,
                         hipStream_t st);
+// how the two-row-set passes deal Q replicate quarters out over six-quarter and four-quarter workgroups (fewest padded quarters,
+// then the most six-quarter workgroups); exported as txm_i8g_quarter_split for the tests
+void g_quarter_split(int Q, int *n6, int *n4);
 
 // ... and for narrow states (C <= 16; txm_resample_i8gn.hip): every pass of the order over the tables of the S states of a batched
 // launch (table_state_stride bytes apart; 0 for a single state)

@@ -1041,6 +1041,10 @@ extern "C" int txm_resample_operands_aligned(const double *x, int64_t ldx_s, int
   return table_operands_ok(x, ldx_s, C, 2, y, ldy_s) ? 1 : 0;  // (K only decides whether a narrow shape is served at all: txm_resample_kernel's business)
 }
 
+// (host only, not part of the public header: the workgroup widths of a two-row-set table pass over Q replicate quarters, for the
+// tests of the rule -- n6 six-quarter workgroups, then n4 four-quarter ones from quarter 6 n6 on)
+extern "C" void txm_i8g_quarter_split(int Q, int *n6, int *n4) { g_quarter_split(Q, n6, n4); }
+
 extern "C" size_t txm_resample_prep_bytes(int64_t N, int64_t C, int64_t nrep, int order) {
   if (N < 1 || C < 1 || nrep < 1 || order < 0 || order > TXM_MAX_ORDER) return 0;
   if (!i8_supported(N, C, nrep, order + 1)) return 256;

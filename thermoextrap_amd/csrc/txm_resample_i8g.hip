@@ -21,6 +21,12 @@
 //     two waves while the block before runs.
 //   * a pass of ONE row set (order 0) has registers to spare and takes TWO replicate groups per workgroup (256 replicates,
 //     eight tiles per wave): 74.4 -> 62.2 ms per call at N = 1e8, nrep = 1000.
+//   * a four-quarter pass of TWO row sets without a second matrix (193 registers before) takes x straight from global memory into a
+//     register ring X[4][2], one block ahead, with hand-counted s_waitcnt vmcnt: x is not shared between waves, so its trip through
+//     the LDS bought nothing -- no x ring, the loader waves issue 6 instead of 14 DMA pieces a block (G_XDIR).
+//   * the replicate quarters per workgroup are a template parameter: two-row-set passes without a second matrix also exist with SIX
+//     (twelve tiles), and a call's quarters go to a launch of six-quarter workgroups and a launch of four-quarter ones for the
+//     remainder, fewest padded quarters first (g_quarter_split).
 //   * grid = scaling windows x replicate groups; the int32 sums of a window are exact, the flush writes the same
 //     doubles into the same slots as resample_i8t_kernel: the two kernels agree BIT FOR BIT.
 #include "txm_i8g.h"
@@ -39,30 +45,39 @@ constexpr int G_FU = 2176;           // bytes between the factor lines of a lane
 // replicate QUARTERS (32 replicates = one MFMA row block = one 1-KiB piece of a table k-step) per workgroup: four (128 replicates),
 // and eight in a pass of ONE row set (order 0), which has the registers for eight accumulator tiles per wave: every x chunk, sliced
 // word and B operand then serves twice the replicates (74.4 -> 62.2 ms per call at the north-star size).  A workgroup's quarters
-// are addressed piece by piece and may straddle the table's 128-replicate groups -- six quarters in passes of two row sets (twelve
-// tiles, like three row sets at four) were built and measured: 7 % faster per replicate, but 1000 replicates are 32 quarters =
-// 5.33 workgroups of six, and the padding costs more: order 1 88.7 against 86.3 ms, order 3 146.9 / 141.9 (-DTXM_G_SIX_QUARTERS).
-#ifdef TXM_G_FOUR_QUARTERS  // (A/B build: 128 replicates per workgroup in every pass)
-template <int NS> constexpr int G_QUARTERS = 4;
-#elif defined(TXM_G_SIX_QUARTERS)  // (A/B build)
-template <int NS> constexpr int G_QUARTERS = NS == 1 ? 8 : NS == 2 ? 6 : 4;
+// are addressed piece by piece and may straddle the table's 128-replicate groups.  The count is a template parameter NQ of the
+// kernel: passes of two row sets without a second matrix also exist with SIX quarters (twelve tiles, like three row sets at four:
+// 7 % faster per replicate), and a call's quarters are dealt out over six-quarter workgroups and a second launch of four-quarter
+// ones so that the fewest are padded (g_quarter_split below: 1000 replicates = 32 quarters = 4 x 6 + 2 x 4).  Six quarters for every
+// workgroup lost to the padding: 5.33 workgroups of six, order 1 88.7 against 86.3 ms, order 3 146.9 / 141.9.
+template <int NS> constexpr int G_QUARTERS = NS == 1 ? 8 : 4;  // the quarter count every pass has an instance of
+constexpr int G_WIDE_Q = 6;                                    // ... and the wider one of two-row-set passes without a second matrix
+
+// x straight from global memory into registers, no x ring in the LDS: the four-quarter passes of two row sets without a second
+// matrix, which have the sixteen registers (193 of 256 before; the six-quarter instances and the three-row-set ones have none).
+// x is not shared -- wave w is the only reader of column quad w -- so its trip through the LDS bought nothing and cost the loader
+// waves 8 of their 14 DMA pieces a block.
+template <int JN, bool YS, int NQ>
+constexpr bool G_XDIR =
+#if defined(TXM_G_AB_NO_XDIR) || defined(TXM_G_ADIR)  // (A/B build: x through the LDS ring in every pass)
+    false;
 #else
-template <int NS> constexpr int G_QUARTERS = NS == 1 ? 8 : 4;
+    !YS && JN == 2 && NQ == 4;
 #endif
+template <int JN, bool YS, int NQ>
+constexpr int G_XRING = YS ? 2 * G_XR : G_XDIR<JN, YS, NQ> ? 0 : G_XRB;  // 1-KiB x (+ y) ring slots per wave
 
-// (in the six-quarter A/B build one instance does not fit its registers -- weighted order 0 with a second matrix -- and stays at four)
-template <int J0, int JN, bool WEIGHTED, bool YS>
-constexpr int G_NQ = (J0 == 0 && JN == 1 && WEIGHTED && YS) ? 4 : G_QUARTERS<JN + (YS ? 1 : 0)>;
-
-template <int J0, int JN, bool WEIGHTED, bool YS>
+// workgroup b of a launch takes the quarters q_begin + NQ grp .. + NQ - 1 of the n_grp table groups (n_wgg workgroups a window)
+template <int J0, int JN, bool WEIGHTED, bool YS, int NQ_>
 __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void resample_i8g_kernel(
-    const I8Args a, const int K, const unsigned char *__restrict__ table, const int64_t rep_begin, const int n_grp) {
+    const I8Args a, const int K, const unsigned char *__restrict__ table, const int64_t rep_begin, const int n_grp,
+    const int q_begin, const int n_wgg) {
   constexpr int NS = JN + (YS ? 1 : 0);  // row sets of the pass
   static_assert(JN >= 1 && NS <= 3 && J0 + JN <= 8, "row sets");
   constexpr int NPT = JN + ((YS && WEIGHTED && J0 > 0) ? 1 : 0);  // staged factors per sample (the y row set needs plain w)
   constexpr int NX = YS ? 2 : 1;                                 // x-ring DMAs per k-step
   constexpr int WREG = NS * T_PB;
-  constexpr int NQ = G_NQ<J0, JN, WEIGHTED, YS>;                  // replicate quarters (A operands, accumulator tiles per row set)
+  constexpr int NQ = NQ_;                                         // replicate quarters (A operands, accumulator tiles per row set)
   constexpr int A_STEP = NQ * 1024;                               // count words of one k-step in the ring: [quarter][1024]
   constexpr int PPW = G_BS * NQ / T_WAVES;                        // count pieces per wave and block when every wave requests its own
   static_assert(G_BS * NQ % T_WAVES == 0, "count pieces per wave");
@@ -77,7 +92,10 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #else
   constexpr bool ADIR = false;
 #endif
-  constexpr int XRN = XBLK ? G_XRB : G_XR;
+  constexpr bool XDIR = G_XDIR<JN, YS, NQ>;                       // x from global memory into the register ring X (no x ring)
+  static_assert(!XDIR || (XBLK && !ADIR), "x into registers: passes without a second matrix");
+  constexpr int XRN = XDIR ? 0 : XBLK ? G_XRB : G_XR;
+  static_assert((YS ? 2 : 1) * XRN == G_XRING<JN, YS, NQ>, "ring slots as the launch sizes them");
   constexpr int OFF_X = OFF_A + 2 * G_BS * A_STEP;                // [wave][XRN][32 samples][4 columns] doubles
   constexpr int OFF_Y = OFF_X + T_WAVES * XRN * 1024;
   constexpr int OFF_RAW = OFF_Y + (YS ? T_WAVES * XRN * 1024 : 0);  // [3][u | w][G_BS * 32] doubles
@@ -93,24 +111,24 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
   // ---- which window, which replicate group (the groups of a window share an XCD: b and b + 8 land on the same one)
   const int b = blockIdx.x;
-  const int n_wgg = (4 * n_grp + NQ - 1) / NQ;  // replicate groups of the grid (NQ quarters each; the table's groups hold 4)
   const int64_t win = (int64_t)((b >> 3) / n_wgg) * 8 + (b & 7);
   const int grp = (b >> 3) % n_wgg;
   if (win >= a.nwin) return;
   if (a.wflag[win] != 0u) return;  // precision guard: this window goes to the FP64 kernel
-  const int64_t rep0 = rep_begin + (int64_t)grp * (32 * NQ);
+  const int gq0 = q_begin + grp * NQ;  // the workgroup's first quarter
+  const int64_t rep0 = rep_begin + (int64_t)gq0 * 32;
   const int64_t WT = a.win_tiles;
   const int64_t t0 = win * WT;
   const int64_t t1 = t0 + WT < a.ntiles ? t0 + WT : a.ntiles;
   const int nsteps = (int)(t1 - t0) * T_STEPS;  // k-steps (32-sample chunks) of the window
   const int nblk = nsteps / G_BS;
   const unsigned char *tab = table + (size_t)t0 * G_TILE_BYTES;  // the window in table group 0
-  // quarter Q of the workgroup = quarter (grp NQ + Q) of the call: piece (that & 3) of table group (that >> 2).  Past the call's
+  // quarter Q of the workgroup = quarter (gq0 + Q) of the call: piece (that & 3) of table group (that >> 2).  Past the call's
   // last quarter (a last workgroup that is not full) the first quarter's words are read again; those rows -- all past nrep --
   // are not flushed
   auto q_off = [&](int Q) -> size_t {
-    int gq = grp * NQ + Q;
-    if (gq >= 4 * n_grp) gq = grp * NQ;
+    int gq = gq0 + Q;
+    if (gq >= 4 * n_grp) gq = gq0;
     return (size_t)(gq >> 2) * (size_t)a.ntiles * G_TILE_BYTES + (size_t)(gq & 3) * 1024;
   };
 
@@ -209,6 +227,28 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
         if constexpr (YS) yq += ystep;
       }
     }
+  };
+  // ---- (XDIR) the register ring: X[i] holds this lane's two doubles -- samples ps and ps + 16, column cl of the wave's quad: the
+  // producer mapping -- of chunk 4 B + 1 + i while block B runs.  Step p of a block slices X[p] in its first slot and reloads it right
+  // behind that use with the chunk four steps on (one block of lead); chunks past the window re-read its last one.  The loads are an
+  // asm the compiler does not track (a load it sees across the loop's back edge makes it wait for vmcnt(0) at the top of every
+  // block, profiles/r06_experiments.md section 1): the waits are counted by hand where X[p] is sliced, see there.
+  double X[XDIR ? G_BS : 1][2];
+  const uint32_t xd_voff = (uint32_t)ps * (uint32_t)(a.ldx_s * 8) + (uint32_t)(cl * 8);
+  const int64_t xd_half = 16 * a.ldx_s * 8;  // sample ps + 16
+  auto x_advance = [&]() {
+    ++cq;
+    if (cq < nsteps) {
+      if ((cq & 31) == 0) xq = reinterpret_cast<const char *>(a.x + chunk_sample(cq) * a.ldx_s);  // a new tile
+      else xq += xstep;
+    }
+  };
+  auto x_load = [&](auto ic) {  // chunk cq -> X[i]
+    constexpr int i = decltype(ic)::value;
+    const char *s0 = xq + xcol1;
+    asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(X[i][0]) : "v"(xd_voff), "s"(s0) : "memory");
+    asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(X[i][1]) : "v"(xd_voff), "s"(s0 + xd_half) : "memory");
+    x_advance();
   };
   // ---- count words of block B -> ring buffer B & 1: the wave's two 1-KiB pieces
   auto a_request = [&](int B, int piece = -1) {
@@ -369,11 +409,20 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
       if constexpr (WEIGHTED) d_w[uu] = a.w[i0 + 16 * uu + ps] * inv_w;
     }
   }
+  double x0[2] = {0.0, 0.0};  // (XDIR) chunk 0's x, a plain load like its u / w
+  if constexpr (XDIR) {
+    const double *xc0 = a.x + chunk_sample(0) * a.ldx_s + a.col0 + 4 * qsrc + cl;
+#pragma unroll
+    for (int uu = 0; uu < 2; ++uu) x0[uu] = xc0[(int64_t)(16 * uu + ps) * a.ldx_s];
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (nothing of the compiler's is in flight behind the DMAs below)
   raw_request(0);
   raw_request(1);
   if constexpr (!ADIR) a_request(0);
-  if constexpr (XBLK) {  // chunk c lives in slot (c - 1) & 7: chunk 0 in slot 7, block 0's chunks 1..4 in slots 0..3
+  if constexpr (XDIR) {  // chunk 0 is in x0; block 0's chunks 1..4 into X[0..3]
+    x_advance();
+    t_static_for<G_BS>([&](auto ic) { x_load(ic); });
+  } else if constexpr (XBLK) {  // chunk c lives in slot (c - 1) & 7: chunk 0 in slot 7, block 0's chunks 1..4 in slots 0..3
     x_request(7);
 #pragma unroll
     for (int c = 0; c < G_BS; ++c) x_request(c);
@@ -405,7 +454,8 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
     double dx[2], dy[2] = {0.0, 0.0};
 #pragma unroll
     for (int uu = 0; uu < 2; ++uu) {
-      dx[uu] = (*(lds_cd)(lds + xa + uu * 512) - px) * sc;
+      if constexpr (XDIR) dx[uu] = (x0[uu] - px) * sc;
+      else dx[uu] = (*(lds_cd)(lds + xa + uu * 512) - px) * sc;
       if constexpr (YS) dy[uu] = (*(lds_cd)(lds + xa + (yring - xring) + uu * 512) - py) * scy;
     }
     t_static_for<NS>([&](auto fic) {
@@ -468,11 +518,19 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
       }
     }
   };
+  // the lane id where a block's loop-carried bases are re-formed.  The six-quarter instances (twelve tiles AND six count operands) have
+  // no register to hold what these are formed from across the k-steps: held, the bases were spilled and reloaded once a block, each
+  // reload a scratch round trip behind an s_waitcnt vmcnt(0).  (The factor and x bases only: with the count base re-formed as well
+  // the allocator spilled 169 registers.)
+  auto lane_l = [&]() -> uint32_t {
+    if constexpr (NQ == G_WIDE_Q) return g_lane_now();
+    else return (uint32_t)lane;
+  };
   v4i A[NQ];
   // B operands: passes of >= 2 row sets hold TWO (this slot's and the next one's, read a slot ahead), not one per row set
   constexpr bool BT2 = NS >= 2;
   v2i Bt[BT2 ? 2 : 1][2];
-  double f[2], xr[2], yr[2] = {0.0, 0.0};
+  double f[2], xr[2] = {0.0, 0.0}, yr[2] = {0.0, 0.0};
   // loop-carried bases (opaque below: the reads take 16-bit immediate offsets): the factor buffer of the block, and the x ring
   // (half of the block when a block's chunks are requested together)
   uint32_t f_va = (uint32_t)(OFF_F + ps * NPT * 8);
@@ -487,7 +545,8 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
     Bt[0][1] = T_TRREAD((lds_v2i)(lds + rd_off + 128));
     read_factors(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, f_va, f);
 #pragma unroll
-    for (int uu = 0; uu < 2; ++uu) xr[uu] = *(lds_cd)(lds + x_va + (XBLK ? 0 : 1024) + uu * 512);  // chunk 1
+    for (int uu = 0; uu < 2; ++uu)
+      if constexpr (!XDIR) xr[uu] = *(lds_cd)(lds + x_va + (XBLK ? 0 : 1024) + uu * 512);  // chunk 1
   }
 #pragma unroll 1
   for (int B = 0; B < nblk; ++B) {
@@ -558,8 +617,10 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
       if constexpr (XBLK) {  // the next block's count words and x (chunks 4 (B + 1) + 1 .. + 4 into the ring half this block does not read)
 #pragma unroll
         for (int Q = 0; Q < NQ; ++Q) a_piece(Q);
+        if constexpr (!XDIR) {
 #pragma unroll
-        for (int i = 0; i < G_BS; ++i) x_chunk(i);
+          for (int i = 0; i < G_BS; ++i) x_chunk(i);
+        }
       } else {
         a_request(B + 1);
       }
@@ -574,6 +635,10 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
         if constexpr (ADIR) {  // four x chunks over the four slots of steps 0 and 1
           static_assert(!ADIR || ISSUE_SLOTS == G_BS, "one x chunk a slot");
           x_chunk(k);
+        } else if constexpr (XDIR) {  // count pieces only: x goes into registers
+#pragma unroll
+          for (int j = 0; j < NQ; ++j)
+            if (j * ISSUE_SLOTS / NQ == k) a_piece(j);
         } else {
 #pragma unroll
           for (int j = 0; j < NQ + 4; ++j)
@@ -588,7 +653,8 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
     G_TICK(2);
     // count words: this block's steps 1..3 from buffer B & 1, the next block's step 0 from the other buffer
     uint32_t a_va = (uint32_t)(OFF_A + (B & 1) * (G_BS * A_STEP)) + (uint32_t)lane * 16u;
-    asm volatile("" : "+v"(f_va), "+v"(x_va), "+v"(a_va));
+    if constexpr (XDIR) asm volatile("" : "+v"(f_va), "+v"(a_va));
+    else asm volatile("" : "+v"(f_va), "+v"(x_va), "+v"(a_va));
     // SLOT = one row set of one step: its four MFMAs, then the words of chunk s + 1 for that row set.  A wave issues in order,
     // and its LDS operations complete in order: a read consumed right where it was issued -- the first cuts read a slot's factors
     // behind the stores and operand reads of the slot before and waited for them three MFMAs later, and read x at the top of the
@@ -633,6 +699,12 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
             // seven count loads issued behind the last x piece are in flight: A[1] quarters 1..3 and A[2]; waves 4..7 issue no DMA
             if (loader) asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          } else if constexpr (XDIR) {
+            // the block's DMA (raw pieces at its top, count pieces in the slots of steps 0 and 1) has landed when at most the x
+            // loads issued behind the last count piece are in flight: X[2] and X[3] (all four when the pieces go out at the top);
+            // waves 4..7 issue no DMA
+            if (loader) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(SPREAD ? 4 : 8) : "memory");
+            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           } else {
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(XBLK ? 0 : 3 * NX) : "memory");
           }
@@ -647,7 +719,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
           } else if constexpr (p < G_BS - 1) {
             read_factors(std::integral_constant<int, p + 1>{}, std::integral_constant<int, 0>{}, f_va, f);
           } else {  // behind the barrier: the next block's buffer
-            f_va = (uint32_t)(OFF_F + ((B + 1) % 3) * (2 * G_FU) + ps * NPT * 8);
+            f_va = (uint32_t)(OFF_F + ((B + 1) % 3) * (2 * G_FU)) + (lane_l() >> 2) * (uint32_t)(NPT * 8);
             asm volatile("" : "+v"(f_va));
             read_factors(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, f_va, f);
           }
@@ -655,10 +727,10 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
             for (int uu = 0; uu < 2; ++uu) yr[uu] = *(lds_cd)(lds + x_va + (OFF_Y - OFF_X) + ((p + 1) & 3) * 1024 + uu * 512);
           }
-          if constexpr (last) {  // raw x of chunk s + 2, which the next step slices (dx is dead: into its registers)
+          if constexpr (last && !XDIR) {  // raw x of chunk s + 2, which the next step slices (dx is dead: into its registers)
             if constexpr (XBLK) {
               if constexpr (p == G_BS - 1) {  // the other half of the ring (landed: every loader waited before the barrier)
-                x_va = xring + (uint32_t)(ps * 32 + cl * 8) + (uint32_t)(((B + 1) & 1) * 4096);
+                x_va = xring + lane_l() * 8u + (uint32_t)(((B + 1) & 1) * 4096);  // (ps * 32 + cl * 8 = 8 lane)
                 asm volatile("" : "+v"(x_va));
               }
 #pragma unroll
@@ -707,7 +779,31 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
         G_PIN();
         // (a) the fixed-point words of chunk s + 1, row set fi
-        if constexpr (fi == 0) {
+        if constexpr (fi == 0 && XDIR) {
+          // X[p] was requested behind this use ONE BLOCK AGO.  Vector-memory operations complete in order; issued behind it since
+          // then is one block's worth of everything else: the six loads of the three other ring entries, and on a loader wave the NQ
+          // count pieces and the R raw pieces -- the same count at every p, whichever slots the pieces go out in.
+          // (No register operands on the two waits: tied through the branches they make the compiler copy the operands, in one
+          // branch in FRONT of the wait.  The empty asm behind them is what the slicing depends on; volatile asms keep their order.)
+          constexpr int R = WEIGHTED ? 2 : 1;
+          G_PIN();
+          if (loader) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NQ + 6 + R) : "memory");
+          else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+          asm volatile("" : "+v"(X[p][0]), "+v"(X[p][1]));
+          G_PIN();
+          double xc[2];
+#pragma unroll
+          for (int uu = 0; uu < 2; ++uu) xc[uu] = X[p][uu] - px;
+          // (the reload stays behind the last use, so that the ring entry keeps its registers: left to itself the compiler sinks
+          // the subtraction to where dx is used, past the reload, and rotates the ring through copies.  Only the DIFFERENCE is made
+          // opaque: with the product behind the empty asm as well, an unweighted power 0 -- factor 1 -- could no longer contract
+          // (x - px) * sc + magic into the one fused multiply-add the other kernels round with, and a word in 1e7 differed by a bit)
+          asm volatile("" : "+v"(xc[0]), "+v"(xc[1]));
+          G_PIN();
+          x_load(pc);
+#pragma unroll
+          for (int uu = 0; uu < 2; ++uu) dx[uu] = xc[uu] * sc;
+        } else if constexpr (fi == 0) {
 #pragma unroll
           for (int uu = 0; uu < 2; ++uu) dx[uu] = (xr[uu] - px) * sc;
         }
@@ -743,14 +839,14 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
         // (b) the u-row overlay (wave-uniform branch, kept by the volatile permute), then the reads of the NEXT slot
 #if !defined(TXM_G_NO_OVERLAY) && !defined(TXM_G_NO_SLICE)
         if (fi < JN && ofi == fi) {
-#ifdef TXM_G_OVERLAY_RECOMPUTE  // (selector and bias from the lane id, here: two registers fewer held across the k-steps, nine vector
-          // instructions more per overlay -- what the six-quarter A/B build needs to fit)
-          const uint32_t od_l = 4u * (uint32_t)(wave & 1) + (g_lane_now() & 3u);
-          const uint32_t osel_l = od_l < 7u ? ((od_l << 24) | 0x000c0c0cu) : 0x0c0c0c0cu;
-          const uint32_t oxor_l = od_l < 6u ? 0x80000000u : 0u;
-#else
-          const uint32_t osel_l = osel, oxor_l = oxor;
-#endif
+          uint32_t osel_l = osel, oxor_l = oxor;
+          if constexpr (NQ == G_WIDE_Q) {
+            // (six quarters: selector and bias from the lane id, here -- two registers fewer held across the k-steps, nine vector
+            // instructions more per overlay: what the twelve-tile instance with six count operands needs to fit)
+            const uint32_t od_l = 4u * (uint32_t)(wave & 1) + (g_lane_now() & 3u);
+            osel_l = od_l < 7u ? ((od_l << 24) | 0x000c0c0cu) : 0x0c0c0c0cu;
+            oxor_l = od_l < 6u ? 0x80000000u : 0u;
+          }
 #pragma unroll
           for (int uu = 0; uu < 2; ++uu) {
             const uint64_t ub = (uint64_t)__double_as_longlong(__builtin_ldexp(f[uu], 50) + T_MAGIC);
@@ -801,7 +897,14 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // byte of OTHER waves' columns stay per-digit slots (part_u), and so does the second matrix's row set (part_y): the finalize is told
   // (mode 2: x summed, u per digit).
   constexpr int XS = 65, XT = 16 * XS;
-  static_assert(OFF_A + T_WAVES * XT * 4 <= OFF_RAW, "flush scratch inside the count and x rings");
+  // (without an x ring the scratch runs on into the raw and factor buffers, idle as well behind the barrier; fsum is read below)
+  static_assert(OFF_A + T_WAVES * XT * 4 <= (XDIR ? OFF_FS : OFF_RAW), "flush scratch inside the count and x rings");
+  if constexpr (XDIR) {  // the last block's reloads land in the ring's registers: they stay allocated until nothing is in flight
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(X[0][0]), "+v"(X[0][1]), "+v"(X[1][0]), "+v"(X[1][1]), "+v"(X[2][0]), "+v"(X[2][1]), "+v"(X[3][0]), "+v"(X[3][1])
+                 :
+                 : "memory");
+  }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");  // no DMA piece in flight, no wave still reading the rings
   if (pg != nullptr && threadIdx.x == 0) __hip_atomic_store(&pg[grp & 15], 0xfffffff0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   auto odig_of = [](int w, int c) { return 4 * (w & 1) + c; };  // the u-row digit column c of wave w carries in its dead byte
@@ -889,18 +992,54 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 // ---------------------------------------------------------------------------
+// n_wg workgroups of NQ quarters a window, from quarter q_begin on
+template <int J0, int JN, bool WEIGHTED, bool YS, int NQ>
+static int launch_quarters_g(const I8Args &a, int K, const unsigned char *table, int64_t rep_begin, int n_grp, int q_begin, int n_wg,
+                             hipStream_t st) {
+  constexpr int NS = JN + (YS ? 1 : 0);
+  const size_t lds = (size_t)T_WAVES * NS * T_PB + 2 * G_BS * NQ * 1024 + (size_t)G_XRING<JN, YS, NQ> * T_WAVES * 1024 + 3 * G_RAW +
+                     3 * 2 * G_FU + 32 * NQ * sizeof(uint32_t);
+  const dim3 grid((unsigned)(cdiv(a.nwin, 8) * 8 * n_wg));
+  if (a.progress != nullptr) TXM_HIP(hipMemsetAsync(a.progress, 0, (size_t)cdiv(a.nwin, 8) * 8 * 16 * sizeof(uint32_t), st));
+  TXM_SET_MAX_LDS((&resample_i8g_kernel<J0, JN, WEIGHTED, YS, NQ>), lds);
+  hipLaunchKernelGGL((resample_i8g_kernel<J0, JN, WEIGHTED, YS, NQ>), grid, dim3(T_BLOCK), lds, st, a, K, table, rep_begin, n_grp,
+                     q_begin, n_wg);
+  TXM_LAUNCH_CHECK();
+  return TXM_OK;
+}
+
+// How Q replicate quarters are dealt out over n6 six-quarter and n4 four-quarter workgroups: 6 n6 + 4 n4 >= Q with the fewest padded
+// quarters, and among those the most six-quarter workgroups.  Four-quarter workgroups alone are one of the candidates, so six-quarter
+// ones never pad more than today's launch did (Q = 7: 4 + 4, not 6 + 4); 1000 replicates, Q = 32: 4 x 6 + 2 x 4.
+void g_quarter_split(int Q, int *n6, int *n4) {
+  int best6 = 0, best4 = 0, best_pad = -1;
+  for (int s6 = 0; 6 * (s6 - 1) < Q; ++s6) {
+    const int rest = Q - 6 * s6, s4 = rest > 0 ? (rest + 3) / 4 : 0;
+    const int pad = 6 * s6 + 4 * s4 - Q;
+    if (best_pad < 0 || pad <= best_pad) best6 = s6, best4 = s4, best_pad = pad;  // (ascending: ties go to the larger count of six)
+  }
+  *n6 = best6;
+  *n4 = best4;
+}
+
 template <int J0, int JN, bool WEIGHTED, bool YS>
 static int launch_pass_g(const I8Args &a, int K, const unsigned char *table, int64_t rep_begin, int n_grp, hipStream_t st) {
   constexpr int NS = JN + (YS ? 1 : 0);
-  constexpr int NQ = G_NQ<J0, JN, WEIGHTED, YS>;
-  const size_t lds = (size_t)T_WAVES * NS * T_PB + 2 * G_BS * NQ * 1024 + (size_t)(YS ? 2 * G_XR : G_XRB) * T_WAVES * 1024 + 3 * G_RAW +
-                     3 * 2 * G_FU + 32 * NQ * sizeof(uint32_t);
-  const dim3 grid((unsigned)(cdiv(a.nwin, 8) * 8 * cdiv(4 * (int64_t)n_grp, NQ)));
-  if (a.progress != nullptr) TXM_HIP(hipMemsetAsync(a.progress, 0, (size_t)cdiv(a.nwin, 8) * 8 * 16 * sizeof(uint32_t), st));
-  TXM_SET_MAX_LDS((&resample_i8g_kernel<J0, JN, WEIGHTED, YS>), lds);
-  hipLaunchKernelGGL((resample_i8g_kernel<J0, JN, WEIGHTED, YS>), grid, dim3(T_BLOCK), lds, st, a, K, table, rep_begin, n_grp);
-  TXM_LAUNCH_CHECK();
-  return TXM_OK;
+  constexpr int NQ = G_QUARTERS<NS>;
+#ifndef TXM_G_AB_NO_SIX  // (A/B build: every workgroup at G_QUARTERS)
+  if constexpr (NS == 2 && !YS) {
+    // the quarters that hold replicates of the call (rows past nrep are not flushed; their quarters need no workgroup)
+    const int64_t reps = a.nrep - rep_begin < (int64_t)n_grp * G_REPS ? a.nrep - rep_begin : (int64_t)n_grp * G_REPS;
+    int n6 = 0, n4 = 0;
+    g_quarter_split((int)cdiv(reps > 0 ? reps : 0, 32), &n6, &n4);
+    if (n6 > 0) {
+      if (int rc = launch_quarters_g<J0, JN, WEIGHTED, YS, G_WIDE_Q>(a, K, table, rep_begin, n_grp, 0, n6, st); rc != TXM_OK) return rc;
+      if (n4 == 0) return TXM_OK;
+      return launch_quarters_g<J0, JN, WEIGHTED, YS, NQ>(a, K, table, rep_begin, n_grp, G_WIDE_Q * n6, n4, st);
+    }
+  }
+#endif
+  return launch_quarters_g<J0, JN, WEIGHTED, YS, NQ>(a, K, table, rep_begin, n_grp, 0, (int)cdiv(4 * (int64_t)n_grp, NQ), st);
 }
 
 // what the kernel asks of a call beyond the shape (LDS-DMA moves 16 bytes per lane): x (and y) 16-byte aligned with an even
