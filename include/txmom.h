@@ -75,7 +75,13 @@ int txm_stream_sync(txm_stream stream);
  *   data.py:487-489 (DataValues*).
  * x[i*ldx_s + c*ldx_c], i < N, c < C.  Either ldx_c == 1 ((rec, val) layout,
  * core/xrutils.py:73-116) or ldx_s == 1 ((val, rec) layout).  w may be NULL.
- * out: [C][2][K].
+ * out: [C][2][K].  Total weight zero gives the empty state (all zeros), as cmomy does.
+ * The sums are taken about a pivot the library estimates itself: without w the mean of at most 1024 strided samples;
+ * with w the WEIGHTED mean of at most 1024 samples spread evenly over the series (rows floor(k N / 1024); rows of weight
+ * zero never enter it) -- or the weighted mean of all rows when that subsample is not the whole series and carries less
+ * than 32 effective rows of weight -- so that concentrated weights (reweighting, masks) keep the accuracy of the
+ * unweighted call.  A row of weight zero may hold any FINITE value; a non-finite one still gives NaN (0 * inf).  txm_push_vals, txm_reduce_vals_batched and txm_reduce_vals_1d
+ * follow the same rule.
  */
 size_t txm_reduce_vals_ws_bytes(int64_t N, int64_t C, int order);
 int txm_reduce_vals(const double *x, int64_t ldx_s, int64_t ldx_c, const double *u,
@@ -88,6 +94,9 @@ int txm_reduce_vals(const double *x, int64_t ldx_s, int64_t ldx_c, const double 
  * Sums about ONE pivot add exactly like the samples they stand for, so N samples split over ranks (or over time) are:
  * one pivot everybody uses, per-shard sums, one addition in a fixed order, one shift to the cmomy state.
  *   txm_reduce_vals_pivot   the library's own estimate (strided means of at most 1024 samples) for a shard: [1 + C]
+ *   txm_reduce_vals_pivot_w the same with weights (w may be NULL): the estimate txm_reduce_vals itself uses for (x, u, w) --
+ *                           a weighted reduce about the UNWEIGHTED pivot loses about (1 + delta)^order in accuracy when
+ *                           the weighted mean lies delta weighted sigmas from it
  *   txm_reduce_vals_sums    the sums of a shard about a GIVEN pivot: [C][2][K]            (ws: txm_reduce_vals_ws_bytes)
  *   txm_sums_to_state       out[C][2][K] = shift(sums[0] + sums[1] + ... + sums[n - 1]), sums [n][C][2][K], added in index
  *                           order -- an all-gathered stack of per-rank sums gives every rank the same bits
@@ -98,6 +107,8 @@ int txm_reduce_vals(const double *x, int64_t ldx_s, int64_t ldx_c, const double 
  * SURVEY 0.7 -- but it is the streaming form of the reduction above.)  ws: txm_push_vals_ws_bytes. */
 int txm_reduce_vals_pivot(const double *x, int64_t ldx_s, int64_t ldx_c, const double *u, int64_t N, int64_t C,
                           double *pivot, txm_stream stream);
+int txm_reduce_vals_pivot_w(const double *x, int64_t ldx_s, int64_t ldx_c, const double *u, const double *w, int64_t N,
+                            int64_t C, double *pivot, txm_stream stream);
 int txm_reduce_vals_sums(const double *x, int64_t ldx_s, int64_t ldx_c, const double *u, const double *w,
                          int64_t N, int64_t C, int order, const double *pivot, double *sums, void *ws,
                          size_t ws_bytes, txm_stream stream);

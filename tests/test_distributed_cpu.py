@@ -137,6 +137,20 @@ WORKER = textwrap.dedent(
     assert torch.equal(seen["piv"], piv_fn(xx, uu)) and torch.equal(seen["stack"][0], torch.zeros(2, 2, Kk, dtype=torch.float64))
     assert torch.allclose(tot2, sums_fn(xx, uu, Kk - 1, seen["piv"], None), rtol=1e-12, atol=1e-9)
     ref_t = tot2.clone(); dist.broadcast(ref_t, src=0); assert torch.equal(tot2, ref_t)
+    # weighted: the pivot stand-in is called as pivot(x, u, w) (the engine's reduce_pivot(x, u, w): the weighted estimate), the
+    # sums carry the weights; rank 0's WEIGHTED pivot is the one every rank uses
+    ww = 0.25 + torch.rand(1001, generator=g, dtype=torch.float64)
+    def wpiv_fn(x_, u_, w_=None):
+        w7 = torch.ones(7, dtype=torch.float64) if w_ is None else w_[:7]
+        return torch.cat([((w7 * u_[:7]).sum() / w7.sum())[None], (w7[:, None] * x_[:7]).sum(0) / w7.sum()])
+    def wsums_fn(x_, u_, o_, p_, w_):
+        du = u_ - p_[0]; dx = x_ - p_[1:]
+        return torch.stack([torch.stack([torch.stack([(w_ * du ** j).sum() for j in range(o_ + 1)]),
+                                         torch.stack([(w_ * dx[:, c] * du ** j).sum() for j in range(o_ + 1)])]) for c in range(x_.shape[1])])
+    tot3 = D.sharded_reduce(xx[sh.start:sh.stop], uu[sh.start:sh.stop], Kk - 1, w=ww[sh.start:sh.stop], ops=(wpiv_fn, wsums_fn, fin_fn))
+    assert torch.equal(seen["piv"], wpiv_fn(xx[:501], uu[:501], ww[:501])) and not torch.equal(seen["piv"], wpiv_fn(xx[:501], uu[:501]))
+    assert torch.allclose(tot3, wsums_fn(xx, uu, Kk - 1, seen["piv"], ww), rtol=1e-12, atol=1e-9)
+    ref_t = tot3.clone(); dist.broadcast(ref_t, src=0); assert torch.equal(tot3, ref_t)
     try:
         D.sharded_reduce(xx[:0], uu[:0], Kk - 1, ops=(piv_fn, sums_fn, fin_fn))
         raise SystemExit("sharded_reduce accepted all-empty shards")

@@ -78,6 +78,7 @@ SIGNATURES = {
     "txm_reduce_vals": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p,
                                 c_void_p, c_size, c_void_p]),
     "txm_reduce_vals_pivot": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p]),
+    "txm_reduce_vals_pivot_w": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p]),
     "txm_reduce_vals_sums": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p,
                                      c_void_p, c_size, c_void_p]),
     "txm_sums_to_state": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_int, c_void_p, c_void_p]),

@@ -13,6 +13,8 @@
 //
 // Kernels
 //   pivot_kernel          : pivot = mean of <=1024 strided samples per column
+//   pivot_w_kernel        : with weights, their weighted mean (txm_pivot.h: every row when the subsample saw too
+//                           little weight)
 //   reduce_rowmajor_kernel: x is (rec, val) row-major; a wave reads whole rows
 //                           with 16-B (or 8-B) loads per lane, fully coalesced;
 //                           each lane owns VEC fixed columns -> register sums.
@@ -42,6 +44,18 @@ __device__ __forceinline__ double2 red_ld2(const double *p) {
 // (the 8-byte path of odd or unaligned row pitches keeps plain loads: its rows share cache lines with their neighbours, which
 // other wave instructions load -- non-temporal there re-fetches them: N = 1e8, 33 observables: 8.94 -> 9.23 ms)
 __device__ __forceinline__ double red_ld1(const double *p) { return *p; }
+
+// Total weight zero (every w_i = 0): the empty state, all zeros -- what push_vals and resample_data give and what cmomy
+// returns -- instead of the 0 / 0 of the shift.
+template <int K>
+__device__ inline void pivot_sums_to_state_or_empty(const double *S0, const double *S1, double pu, double px, double *state) {
+  if (S0[0] == 0.0) {
+#pragma unroll
+    for (int q = 0; q < 2 * K; ++q) state[q] = 0.0;
+    return;
+  }
+  pivot_sums_to_state<K>(S0, S1, pu, px, state);
+}
 
 // ---------------------------------------------------------------------------
 // Row-major reduction.  Thread layout inside a 256-thread block:
@@ -214,7 +228,7 @@ __global__ __launch_bounds__(RED_BLOCK) void finalize_rowmajor_kernel(
         st[K + j] = S1[j];
       }
     } else {
-      pivot_sums_to_state<K>(S0, S1, pivot[0], pivot[1 + c], st);
+      pivot_sums_to_state_or_empty<K>(S0, S1, pivot[0], pivot[1 + c], st);
     }
 #pragma unroll
     for (int q = 0; q < 2 * K; ++q) out[c * 2 * K + q] = st[q];
@@ -351,7 +365,7 @@ __global__ __launch_bounds__(RED_BLOCK) void finalize_colmajor_kernel(
           st[K + j] = S1[j];
         }
       } else {
-        pivot_sums_to_state<K>(S0, S1, pivot[0], pivot[1 + s], st);
+        pivot_sums_to_state_or_empty<K>(S0, S1, pivot[0], pivot[1 + s], st);
       }
 #pragma unroll
       for (int q = 0; q < 2 * K; ++q) out[(size_t)s * 2 * K + q] = st[q];
@@ -363,7 +377,7 @@ __global__ __launch_bounds__(RED_BLOCK) void finalize_colmajor_kernel(
         S0[j] = sh[0][j];
         S1[j] = 0.0;
       }
-      pivot_sums_to_state<K>(S0, S1, pivot[s], 0.0, st);
+      pivot_sums_to_state_or_empty<K>(S0, S1, pivot[s], 0.0, st);
 #pragma unroll
       for (int j = 0; j < K; ++j) out[(size_t)s * K + j] = st[j];
     }
@@ -519,7 +533,18 @@ extern "C" size_t txm_reduce_vals_ws_bytes(int64_t N, int64_t C, int order) {
   return reduce_vals_ws_bytes_impl(N, C, order);
 }
 
-// pivot_in == nullptr: the library's strided estimate; sums_only: out = the pivot power sums [C][2][K] (S0 | S1), not the state
+// the library's pivot estimate: the unweighted kernel and launch of always when w == nullptr, else the weighted rule
+static int launch_pivot(const double *x, int64_t ldx_s, int64_t ldx_c, const double *u, const double *w, int64_t N, int64_t C,
+                        double *pivot, hipStream_t st) {
+  if (w)
+    hipLaunchKernelGGL(pivot_w_kernel, dim3((unsigned)(1 + C)), dim3(RED_BLOCK), 0, st, x, ldx_s, ldx_c, u, w, N, pivot);
+  else
+    hipLaunchKernelGGL(pivot_kernel, dim3((unsigned)(1 + C)), dim3(RED_BLOCK), 0, st, x, ldx_s, ldx_c, u, (int64_t)1, N, pivot);
+  TXM_LAUNCH_CHECK();
+  return TXM_OK;
+}
+
+// pivot_in == nullptr: the library's strided estimate (weighted when w is given); sums_only: out = the pivot power sums [C][2][K] (S0 | S1), not the state
 static int reduce_vals_impl(const double *x, int64_t ldx_s, int64_t ldx_c, const double *u, const double *w, int64_t N,
                             int64_t C, int order, const double *pivot_in, int sums_only, double *out, void *ws,
                             size_t ws_bytes, hipStream_t st, const char *who) {
@@ -537,8 +562,8 @@ static int reduce_vals_impl(const double *x, int64_t ldx_s, int64_t ldx_c, const
   if (pivot_in != nullptr) {
     TXM_HIP(hipMemcpyAsync(pivot, pivot_in, sizeof(double) * (size_t)(1 + C), hipMemcpyDeviceToDevice, st));
   } else {
-    hipLaunchKernelGGL(pivot_kernel, dim3((unsigned)(1 + C)), dim3(RED_BLOCK), 0, st, x, ldx_s, ldx_c, u, (int64_t)1, N, pivot);
-    TXM_LAUNCH_CHECK();
+    const int rc = launch_pivot(x, ldx_s, ldx_c, u, w, N, C, pivot, st);
+    if (rc != TXM_OK) return rc;
   }
   const int K = order + 1;
   if (ldx_c == 1 && !(C == 1 && ldx_s == 1)) {
@@ -567,10 +592,15 @@ extern "C" int txm_reduce_vals_pivot(const double *x, int64_t ldx_s, int64_t ldx
   TXM_REQUIRE(x && u && pivot, "reduce_vals_pivot: null pointer");
   TXM_REQUIRE(N >= 1 && C >= 1 && C <= 65535, "reduce_vals_pivot: need N >= 1 and 1 <= C <= 65535");
   TXM_REQUIRE(ldx_c == 1 || ldx_s == 1, "reduce_vals_pivot: need ldx_c == 1 or ldx_s == 1");
-  hipLaunchKernelGGL(pivot_kernel, dim3((unsigned)(1 + C)), dim3(RED_BLOCK), 0, (hipStream_t)stream, x, ldx_s, ldx_c, u,
-                     (int64_t)1, N, pivot);
-  TXM_LAUNCH_CHECK();
-  return TXM_OK;
+  return launch_pivot(x, ldx_s, ldx_c, u, nullptr, N, C, pivot, (hipStream_t)stream);
+}
+
+extern "C" int txm_reduce_vals_pivot_w(const double *x, int64_t ldx_s, int64_t ldx_c, const double *u, const double *w,
+                                       int64_t N, int64_t C, double *pivot, txm_stream stream) {
+  TXM_REQUIRE(x && u && pivot, "reduce_vals_pivot_w: null pointer");
+  TXM_REQUIRE(N >= 1 && C >= 1 && C <= 65535, "reduce_vals_pivot_w: need N >= 1 and 1 <= C <= 65535");
+  TXM_REQUIRE(ldx_c == 1 || ldx_s == 1, "reduce_vals_pivot_w: need ldx_c == 1 or ldx_s == 1");
+  return launch_pivot(x, ldx_s, ldx_c, u, w, N, C, pivot, (hipStream_t)stream);
 }
 
 extern "C" int txm_reduce_vals_sums(const double *x, int64_t ldx_s, int64_t ldx_c, const double *u, const double *w,
@@ -599,7 +629,7 @@ __global__ __launch_bounds__(256) void sums_to_state_kernel(const double *__rest
       S1[j] += src[K + j];
     }
   }
-  pivot_sums_to_state<K>(S0, S1, pivot[0], pivot[1 + c], st);
+  pivot_sums_to_state_or_empty<K>(S0, S1, pivot[0], pivot[1 + c], st);
 #pragma unroll
   for (int q = 0; q < 2 * K; ++q) out[c * 2 * K + q] = st[q];
 }
@@ -677,7 +707,8 @@ extern "C" int txm_push_vals(double *state, const double *x, int64_t ldx_s, int6
   double *pivot = (double *)ws;
   double *chunk = (double *)((char *)ws + align_up((size_t)(1 + C) * sizeof(double), 256));
   void *rws = (char *)chunk + align_up((size_t)C * 2 * (order + 1) * sizeof(double), 256);
-  int rc = txm_reduce_vals_pivot(x, ldx_s, ldx_c, u, N, C, pivot, stream);
+  TXM_REQUIRE(ldx_c == 1 || ldx_s == 1, "push_vals: need ldx_c == 1 or ldx_s == 1");
+  int rc = launch_pivot(x, ldx_s, ldx_c, u, w, N, C, pivot, st);
   if (rc != TXM_OK) return rc;
   rc = reduce_vals_impl(x, ldx_s, ldx_c, u, w, N, C, order, pivot, 1, chunk, rws, txm_reduce_vals_ws_bytes(N, C, order), st,
                         "push_vals");
@@ -718,7 +749,10 @@ extern "C" int txm_reduce_vals_batched(const txm_state_ptrs *states_host, int64_
   TXM_HIP(hipMemcpyAsync(tab, states_host, (size_t)S * sizeof(txm_state_ptrs), hipMemcpyHostToDevice, st));
   double *pivot = (double *)((char *)ws + align_up((size_t)S * sizeof(txm_state_ptrs), 256));
   double *partial = (double *)((char *)pivot + align_up((size_t)S * (1 + C) * sizeof(double), 256));
-  hipLaunchKernelGGL(pivot_batch_kernel, dim3((unsigned)(1 + C), (unsigned)S), dim3(RED_BLOCK), 0, st, tab, ldx_s, N, C, pivot);
+  if (weighted)
+    hipLaunchKernelGGL(pivot_batch_w_kernel, dim3((unsigned)(1 + C), (unsigned)S), dim3(RED_BLOCK), 0, st, tab, ldx_s, N, C, pivot);
+  else
+    hipLaunchKernelGGL(pivot_batch_kernel, dim3((unsigned)(1 + C), (unsigned)S), dim3(RED_BLOCK), 0, st, tab, ldx_s, N, C, pivot);
   TXM_LAUNCH_CHECK();
   const int K = order + 1;
   const double *w0 = weighted ? states_host[0].w : nullptr;  // only its null-ness selects the kernel
@@ -748,8 +782,10 @@ extern "C" int txm_reduce_vals_1d(const double *u, int64_t ldu_r, int64_t ldu_s,
   hipStream_t st = (hipStream_t)stream;
   double *pivot = (double *)ws;
   double *partial = (double *)((char *)ws + align_up((size_t)R * sizeof(double), 256));
-  hipLaunchKernelGGL(pivot_rows_kernel, dim3((unsigned)R), dim3(RED_BLOCK), 0, st, u, ldu_r, N,
-                     pivot);
+  if (w)
+    hipLaunchKernelGGL(pivot_rows_w_kernel, dim3((unsigned)R), dim3(RED_BLOCK), 0, st, u, ldu_r, w, N, pivot);
+  else
+    hipLaunchKernelGGL(pivot_rows_kernel, dim3((unsigned)R), dim3(RED_BLOCK), 0, st, u, ldu_r, N, pivot);
   TXM_LAUNCH_CHECK();
   TXM_K_SWITCH(M, return launch_1d<KK>(u, ldu_r, w, N, R, pivot, partial, out, st));
   return TXM_OK;

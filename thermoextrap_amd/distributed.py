@@ -102,12 +102,14 @@ def broadcast_tensor(t: torch.Tensor, src: int = 0, group=None) -> torch.Tensor:
 def sharded_reduce(x: torch.Tensor, u: torch.Tensor, order: int, w: torch.Tensor | None = None, group=None, ops=None) -> torch.Tensor:
     """SAMPLE-sharded reduce (SURVEY 8(e) partition (4)): every rank holds a shard ``x [N_r, C]``, ``u [N_r]`` (``w``) of one
     long sample array -- the plain reduce is the HBM-bound leg of the path, and N / world samples per rank put every
-    GPU's HBM stacks to work.  Rank 0's pivot estimate is broadcast, every rank takes the power sums of ITS samples about
-    that pivot (they add exactly like the samples), ONE all-gather of the ``[C, 2, K]`` sums (a few KB) and a fixed-order
+    GPU's HBM stacks to work.  Rank 0's pivot estimate (weighted when ``w`` is given) is broadcast, every rank takes the
+    power sums of ITS samples about that pivot (they add exactly like the samples), ONE all-gather of the ``[C, 2, K]`` sums (a few KB) and a fixed-order
     addition + shift give every rank the same state, bit for bit -- the state of the concatenated samples
     (``cmomy.wrap_reduce_vals`` over the whole array: reference data.py:1632-1640) to rounding.  No bulk data moves.
 
-    ``ops``: (pivot, sums, finish) callables standing in for the engine's (the gloo tests run the collective logic on the CPU)."""
+    ``ops``: (pivot, sums, finish) callables standing in for the engine's (the gloo tests run the collective logic on the
+    CPU): ``pivot(x, u, w=None)`` -- called with two arguments when the reduce is unweighted, with ``w`` as the third when it
+    is weighted --, ``sums(x, u, order, pivot, w)``, ``finish(stack, pivot)``."""
     from . import engine
 
     pivot_fn, sums_fn, finish_fn = ops if ops is not None else (
@@ -122,7 +124,7 @@ def sharded_reduce(x: torch.Tensor, u: torch.Tensor, order: int, w: torch.Tensor
     rank, nw = world()
     C = 1 if x.dim() == 1 else int(x.shape[1])
     if sizes[rank] > 0:
-        piv = pivot_fn(x, u) if rank == src else torch.empty(1 + C, dtype=torch.float64, device=x.device)
+        piv = (pivot_fn(x, u) if w is None else pivot_fn(x, u, w)) if rank == src else torch.empty(1 + C, dtype=torch.float64, device=x.device)
     else:
         piv = torch.empty(1 + C, dtype=torch.float64, device=x.device)
     piv = broadcast_tensor(piv, src, group)

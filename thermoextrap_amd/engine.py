@@ -151,12 +151,17 @@ def _rowmajor_operands(x, u, w):
     return x2, ls, lc, u, w, N, C, squeeze
 
 
-def reduce_pivot(x: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
-    """The library's pivot estimate {pivot_u, pivot_x[...]} for a (shard of a) sample matrix: (1 + C,) (txm_reduce_vals_pivot)."""
+def reduce_pivot(x: torch.Tensor, u: torch.Tensor, w: torch.Tensor | None = None) -> torch.Tensor:
+    """The library's pivot estimate {pivot_u, pivot_x[...]} for a (shard of a) sample matrix: (1 + C,) -- strided means
+    (txm_reduce_vals_pivot), with ``w`` the weighted estimate reduce_vals itself uses (txm_reduce_vals_pivot_w)."""
     L = _L()
-    x2, ls, lc, u, _, N, C, _ = _rowmajor_operands(x, u, None)
+    x2, ls, lc, u, w, N, C, _ = _rowmajor_operands(x, u, w)
     piv = torch.empty(1 + C, dtype=F64, device="cuda")
-    check(L.txm_reduce_vals_pivot(_ptr(x2), ls, lc, _ptr(u), N, C, _ptr(piv), _stream()), "txm_reduce_vals_pivot")
+    if w is None:
+        check(L.txm_reduce_vals_pivot(_ptr(x2), ls, lc, _ptr(u), N, C, _ptr(piv), _stream()), "txm_reduce_vals_pivot")
+    else:
+        check(L.txm_reduce_vals_pivot_w(_ptr(x2), ls, lc, _ptr(u), _ptr(w), N, C, _ptr(piv), _stream()),
+              "txm_reduce_vals_pivot_w")
     return piv
 
 
