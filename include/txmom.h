@@ -39,6 +39,9 @@ extern "C" {
 
 #define TXM_ABI_VERSION 2 /* 2: txm_sampler_spec.rep0 */
 #define TXM_MAX_ORDER 8 /* K = order + 1 <= 9 */
+/* the row pitch ld (doubles) a bootstrap call of C columns may have: 768 * ld + C <= 2^29 (txm_resample_vals, "ROW PITCH");
+ * ld <= 699050 for one column, 0 for nothing beyond C = 2^29 */
+#define TXM_RESAMPLE_PITCH_OK(ld, C) (768 * (int64_t)(ld) + (int64_t)(C) <= ((int64_t)1 << 29))
 #define TXM_SAMPLER_STREAM_VERSION 3 /* 3: one BTRS binomial per tree node (round 4); txm_sampler_stream_version() */
 
 typedef enum txm_status {
@@ -208,6 +211,20 @@ int txm_sampler_count_table(const txm_sampler_spec *spec_host, const uint32_t *c
  * NULL lets the library estimate one.  Requires ldx_c == 1.
  * out: [nrep][C][2][K]  (rep-major, i.e. already `.transpose(rep_dim, ...)`,
  * data.py:1812).
+ * Contract at the edges (tests/test_resample_kernel_gpu.py):
+ *   - EMPTY REPLICATE: a replicate whose weight sum  sum_i freq[r][i] w_i  is exactly zero -- a freq row of zeros, or
+ *     weights that are zero on every sample the replicate drew -- gets the empty state, all zeros (cmomy's convention;
+ *     txm_reduce_vals, txm_push_vals and txm_resample_data do the same), and out_y[r][*] = 0.  Every other replicate
+ *     is untouched by that rule.
+ *   - ROW PITCH: ldx_s (and opts.ldy_s; ldx_s of the batched entry) must satisfy TXM_RESAMPLE_PITCH_OK(ld, C),
+ *     768 * ld + C <= 2^29: the kernels address the rows of one 1024-sample tile through unsigned 32-bit byte offsets
+ *     (768 ld + column) * 8, and the column runs over all C columns of the call.  Anything else (a pitch above 699050
+ *     doubles at any C; a 600-column window at a pitch of 699050; a tight array of more than 698140 columns) returns
+ *     TXM_ERR_UNSUPPORTED before anything is enqueued; copy such a window to a tighter array.
+ *   - UNUSED ROWS: a row whose weight w_i is zero, or that no replicate of the call draws (count zero in every row), may
+ *     hold any values for which |u_i - pivot_u|^order * |x_ic - pivot_x[c]| is finite -- it enters every sum as
+ *     0 * (that product).  NaN, inf or magnitudes whose product overflows (1e150 at order >= 2) are not covered: the
+ *     narrow-state kernels form dx du^j before the zero count multiplies it.
  *
  * Scale mode has two kernel families behind it and the library picks one per call:
  *   TXM_PATH_FP64  the contraction on the FP64 matrix pipe (any order, any C);

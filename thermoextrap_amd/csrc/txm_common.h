@@ -95,4 +95,27 @@ __host__ __device__ inline void pivot_sums_to_state(const double *S0, const doub
   state[K] = px + dx;
 }
 
+// Total weight EXACTLY zero (every w_i = 0; a bootstrap replicate whose frequency row is all zeros, or that drew only
+// samples of weight zero): the empty state, all zeros -- what push_vals and resample_data give and what cmomy returns --
+// instead of the 0 / 0 of the shift.  Any other weight sum takes pivot_sums_to_state unchanged (the same bits).
+template <int K>
+__host__ __device__ inline void pivot_sums_to_state_or_empty(const double *S0, const double *S1, double pu, double px,
+                                                             double *state) {
+  if (S0[0] == 0.0) {
+#pragma unroll
+    for (int q = 0; q < 2 * K; ++q) state[q] = 0.0;
+    return;
+  }
+  pivot_sums_to_state<K>(S0, S1, pu, px, state);
+}
+
+// The bootstrap kernels (txm_resample*.hip) address a sample row of x through UNSIGNED 32-BIT BYTE offsets from a
+// wave-uniform base: the widest is the FP64 kernel's lane_xoff = (3 * 256 * ldx_s + column) * 8, where in the plain and the
+// batched launch the base is the unshifted x and `column` runs up to C - 1 (the listed launch folds its column group into
+// the base; the int8 kernels' own offsets span at most 31 rows and the C columns).  It stays below 2^32 iff
+// 768 * ldx_s + C <= 2^29: TXM_RESAMPLE_PITCH_OK (include/txmom.h); txm_resample_vals[_batched] refuse anything else.
+static_assert(TXM_RESAMPLE_PITCH_OK(699050, 512) && !TXM_RESAMPLE_PITCH_OK(699050, 513) && !TXM_RESAMPLE_PITCH_OK(699051, 1) &&
+                  ((uint64_t)(768 * (int64_t)699050 + 511) * 8 < ((uint64_t)1 << 32)) && ((uint64_t)(768 * (int64_t)699050 + 512) * 8 == ((uint64_t)1 << 32)),
+              "include/txmom.h: TXM_RESAMPLE_PITCH_OK");
+
 }  // namespace txm

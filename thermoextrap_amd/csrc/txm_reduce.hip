@@ -45,17 +45,7 @@ __device__ __forceinline__ double2 red_ld2(const double *p) {
 // other wave instructions load -- non-temporal there re-fetches them: N = 1e8, 33 observables: 8.94 -> 9.23 ms)
 __device__ __forceinline__ double red_ld1(const double *p) { return *p; }
 
-// Total weight zero (every w_i = 0): the empty state, all zeros -- what push_vals and resample_data give and what cmomy
-// returns -- instead of the 0 / 0 of the shift.
-template <int K>
-__device__ inline void pivot_sums_to_state_or_empty(const double *S0, const double *S1, double pu, double px, double *state) {
-  if (S0[0] == 0.0) {
-#pragma unroll
-    for (int q = 0; q < 2 * K; ++q) state[q] = 0.0;
-    return;
-  }
-  pivot_sums_to_state<K>(S0, S1, pu, px, state);
-}
+// (total weight zero -> the empty state: pivot_sums_to_state_or_empty, txm_common.h)
 
 // ---------------------------------------------------------------------------
 // Row-major reduction.  Thread layout inside a 256-thread block:

@@ -584,7 +584,7 @@ __global__ __launch_bounds__(256) void resample_finalize_kernel(
       S1[j] += sh[g][eo][K + j];
     }
   double st[2 * K];
-  pivot_sums_to_state<K>(S0, S1, pivot[0], pivot[1 + c_off + c], st);
+  pivot_sums_to_state_or_empty<K>(S0, S1, pivot[0], pivot[1 + c_off + c], st);  // weight sum exactly 0: the empty state
   double *o = out + (r * C_total + c_off + c) * 2 * K;
 #pragma unroll
   for (int q = 0; q < 2 * K; ++q) o[q] = st[q];
@@ -682,7 +682,7 @@ __global__ __launch_bounds__(256) void resample_finalize_i8_kernel(
       }
     }
   double st[2 * K];
-  pivot_sums_to_state<K>(S0, S1, pivot[0], pivot[1 + c_off + c], st);
+  pivot_sums_to_state_or_empty<K>(S0, S1, pivot[0], pivot[1 + c_off + c], st);  // weight sum exactly 0: the empty state
   double *o = out + (r * C_total + c_off + c) * 2 * K;
 #pragma unroll
   for (int q = 0; q < 2 * K; ++q) o[q] = st[q];
@@ -726,7 +726,8 @@ __global__ __launch_bounds__(256) void resample_finalize_y_kernel(
       S0 += fb_u[((size_t)ch * nrep_pad + r) * K];
       S1 += fb_y[((size_t)ch * nrep_pad + r) * fb_cpad + c];
     }
-  out_y[r * C_total + c_off + c] = ypivot[1 + c_off + c] + S1 * (1.0 / S0);  // as pivot_sums_to_state forms a mean
+  // as pivot_sums_to_state forms a mean; a replicate of weight sum exactly 0 has no mean: 0, as in the empty state
+  out_y[r * C_total + c_off + c] = S0 == 0.0 ? 0.0 : ypivot[1 + c_off + c] + S1 * (1.0 / S0);
 }
 
 struct ResamplePlan {
@@ -1460,6 +1461,11 @@ extern "C" int txm_resample_vals(const double *x, int64_t ldx_s, int64_t ldx_c, 
   TXM_REQUIRE(order >= 0 && order <= TXM_MAX_ORDER, "resample_vals: order %d outside [0, %d]", order,
               TXM_MAX_ORDER);
   TXM_REQUIRE(ldx_c == 1 && ldx_s >= C, "resample_vals: x must be (rec, val) row-major (ldx_c == 1)");
+  if (!TXM_RESAMPLE_PITCH_OK(ldx_s, C)) {  // before anything is enqueued: the kernels' 32-bit lane offsets would wrap
+    set_error("resample_vals: row pitch ldx_s = %lld with C = %lld columns exceeds the limit 768 * ldx_s + C <= 2^29 = 536870912 (32-bit byte offsets inside a sampler tile); copy x to a tighter array",
+              (long long)ldx_s, (long long)C);
+    return TXM_ERR_UNSUPPORTED;
+  }
   const bool explicit_ = freq != nullptr;
   TXM_REQUIRE(explicit_ != (spec != nullptr && counts != nullptr),
               "resample_vals: give either freq or (spec, counts)");
@@ -1471,6 +1477,11 @@ extern "C" int txm_resample_vals(const double *x, int64_t ldx_s, int64_t ldx_c, 
               "resample_vals: opts.path %d is not a path", (int)o.path);
   TXM_REQUIRE((o.y == nullptr) == (o.out_y == nullptr), "resample_vals: opts.y and opts.out_y go together");
   TXM_REQUIRE(o.y == nullptr || o.ldy_s >= C, "resample_vals: opts.ldy_s < C");
+  if (o.y != nullptr && !TXM_RESAMPLE_PITCH_OK(o.ldy_s, C)) {
+    set_error("resample_vals: row pitch opts.ldy_s = %lld with C = %lld columns exceeds the limit 768 * ldy_s + C <= 2^29 = 536870912 (32-bit byte offsets inside a sampler tile); copy y to a tighter array",
+              (long long)o.ldy_s, (long long)C);
+    return TXM_ERR_UNSUPPORTED;
+  }
   hipStream_t st = (hipStream_t)stream;
   const size_t main_bytes = txm_resample_vals_ws_bytes_opts(N, C, nrep, order, o.path, o.y != nullptr);
   const size_t avail = ws_bytes < main_bytes ? ws_bytes : main_bytes;
@@ -1777,6 +1788,11 @@ extern "C" int txm_resample_vals_batched_opts(const txm_state_ptrs *states_host,
   TXM_REQUIRE(S >= 1 && S <= 65535 && N >= 1 && C >= 1 && nrep >= 1, "resample_vals_batched: need S, N, C, nrep >= 1");
   TXM_REQUIRE(order >= 0 && order <= TXM_MAX_ORDER, "resample_vals_batched: order %d outside [0, %d]", order, TXM_MAX_ORDER);
   TXM_REQUIRE(ldx_s >= C, "resample_vals_batched: row pitch ldx_s < C");
+  if (!TXM_RESAMPLE_PITCH_OK(ldx_s, C)) {
+    set_error("resample_vals_batched: row pitch ldx_s = %lld with C = %lld columns exceeds the limit 768 * ldx_s + C <= 2^29 = 536870912 (32-bit byte offsets inside a sampler tile); copy x to a tighter array",
+              (long long)ldx_s, (long long)C);
+    return TXM_ERR_UNSUPPORTED;
+  }
   const bool explicit_ = freq != nullptr;
   TXM_REQUIRE(explicit_ != (spec != nullptr && counts != nullptr), "resample_vals_batched: give either freq or (spec, counts)");
   const bool weighted = states_host[0].w != nullptr;

@@ -414,6 +414,12 @@ def _call_path(path) -> int:
     return -1
 
 
+def resample_pitch_ok(ld: int, C: int) -> bool:
+    """include/txmom.h TXM_RESAMPLE_PITCH_OK: the row pitch the bootstrap kernels' 32-bit offsets hold; anything else is copied
+    to a tight array -- which for C > 698140 is itself refused by the library."""
+    return 768 * int(ld) + int(C) <= 1 << 29
+
+
 def _table_operands_ok(x2: torch.Tensor, ls: int, C: int, y: torch.Tensor | None) -> bool:
     """txm_resample_kernel's `aligned` for the operands a call will hand the library (the library's own statement of what the
     count-table kernel's DMA needs: txm_resample_operands_aligned).  A second matrix that resample_vals will have to copy
@@ -422,7 +428,7 @@ def _table_operands_ok(x2: torch.Tensor, ls: int, C: int, y: torch.Tensor | None
     yp, ldy = None, 0
     if y is not None:
         y2 = y.unsqueeze(1) if y.dim() == 1 else y
-        if y2.dim() != 2 or y2.stride(1) != 1 or (y2.shape[0] > 1 and y2.stride(0) < C):
+        if y2.dim() != 2 or y2.stride(1) != 1 or (y2.shape[0] > 1 and (y2.stride(0) < C or not resample_pitch_ok(y2.stride(0), C))):
             yp, ldy = ct.c_void_p(256), C          # (an address with torch's allocation alignment stands in for the copy's)
         else:
             yp, ldy = ct.c_void_p(y2.data_ptr()), max(y2.stride(0) if y2.shape[0] > 1 else C, C)
@@ -469,7 +475,8 @@ def resample_vals(
     src_key = tuple(_tkey(t) for t in src)
     # the kernels want (rec, val) row-major with a row pitch >= C; anything else (transposed views,
     # broadcast rows with stride 0, overlapping pitches) is copied
-    if not (x2.stride(1) == 1 or C == 1) or (N > 1 and x2.stride(0) < C):
+    # (... and a row pitch beyond what the kernels' 32-bit offsets hold, which the library refuses: TXM_RESAMPLE_PITCH_OK)
+    if not (x2.stride(1) == 1 or C == 1) or (N > 1 and (x2.stride(0) < C or not resample_pitch_ok(x2.stride(0), C))):
         x2 = x2.contiguous()
     if C == 1 and x2.stride(1) != 1:
         x2 = x2.contiguous()
@@ -534,7 +541,7 @@ def resample_vals(
         y2 = y.unsqueeze(1) if y.dim() == 1 else y
         if tuple(y2.shape) != (N, C):
             raise ValueError(f"y must have the shape of x, ({N}, {C}); got {tuple(y2.shape)}")
-        if y2.stride(1) != 1 or (N > 1 and y2.stride(0) < C):
+        if y2.stride(1) != 1 or (N > 1 and (y2.stride(0) < C or not resample_pitch_ok(y2.stride(0), C))):
             y2 = y2.contiguous()
         ymean = torch.empty((nrep, C), dtype=F64, device="cuda")
         opts.y, opts.ldy_s, opts.out_y = y2.data_ptr(), max(y2.stride(0) if N > 1 else C, C), ymean.data_ptr()
