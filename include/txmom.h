@@ -618,6 +618,26 @@ int txm_lag_origin_sums(const double *x, int64_t ldx_s, const double *u, int64_t
                         const int32_t *series_host, int32_t n_series, int64_t nskip, int64_t t0, int32_t nlags,
                         double *out, double *mean_out, void *ws, size_t ws_bytes, txm_stream stream);
 
+/* ---- (f-9) delta-method covariance of n_f estimates from their influence polynomials -------------------------- */
+/* For one state of N samples and C observable columns (operands x, ldx_s, ldx_c, u, w as in txm_reduce_vals; w may be
+ * NULL) and, per column, the empirical influence functions of n_f estimates as polynomials in
+ * dx = x[n][c] - center_x[c], du = u[n] - center_u:
+ *     psi_k(n, c)  = sum_{q < n_q} (a[c][k][q] + b[c][k][q] dx) du^q                          k < n_f <= 9, n_q <= 9
+ *     cov[c][i][j] = sum_n w_n^2 psi_i psi_j / (sum_n w_n)^2      (full symmetric n_f x n_f; [i][j] and [j][i] same bits)
+ *     mean[c][k]   = sum_n w_n psi_k / sum_n w_n                  (diagnostic: ~ 0 for a correct coefficient set)
+ * -- the infinitesimal-jackknife (delta-method) covariance of estimates whose influence functions are psi_k: the
+ * first-order term of what a multinomial bootstrap of the samples estimates, for independent samples.  No cmomy /
+ * reference call does this; ExtrapModel.derivs_cov builds a, b from the derivative polynomials (symbolic.influence_coefs).
+ * center_u is a host scalar; center_x [C], a and b [C][n_f][n_q], cov [C][n_f][n_f] and mean [C][n_f] are device arrays.
+ * One pass over x: the kernels accumulate sum w^2 dx^p du^r (p <= 2, r <= 2 (n_q - 1)) and sum w dx^p du^q (p <= 1) per
+ * workgroup, the partials are added in a fixed order and contracted with a, b per column -- no atomics, two calls give the
+ * same bits.  First-order rounding bound: eps * sum_n p_n^2 B_i(n) B_j(n), B_k = sum_q (|a_kq| + |b_kq| |dx|) |du|^q,
+ * p_n = w_n / sum w.  A row of weight zero is skipped and may hold anything; total weight zero gives zeros. */
+size_t txm_influence_cov_ws_bytes(int64_t N, int64_t C, int n_q);
+int txm_influence_cov(const double *x, int64_t ldx_s, int64_t ldx_c, const double *u, const double *w, int64_t N,
+                      int64_t C, int n_f, int n_q, double center_u, const double *center_x, const double *a,
+                      const double *b, double *cov, double *mean, void *ws, size_t ws_bytes, txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,9 @@ SIGNATURES = {
     "txm_lag_origin_sums_ws_bytes": (c_size, [c_i64, c_i64, ct.c_int32, c_i64, ct.c_int32]),
     "txm_lag_origin_sums": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, ct.POINTER(ct.c_int32), ct.c_int32,
                                     c_i64, c_i64, ct.c_int32, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_influence_cov_ws_bytes": (c_size, [c_i64, c_i64, c_int]),
+    "txm_influence_cov": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, ct.c_double, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
 }
 
 ABI_VERSION = 2  # include/txmom.h TXM_ABI_VERSION

@@ -807,6 +807,34 @@ def cov_over_rep(vals: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def influence_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: torch.Tensor, center_u: float,
+                  center_x: torch.Tensor, w: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Delta-method covariance of n_f estimates per column from their influence polynomials (txm_influence_cov):
+    ``psi_k = sum_q (a[c, k, q] + b[c, k, q] dx) du^q`` with ``dx = x[:, c] - center_x[c]``, ``du = u - center_u``.
+    x: (N, C) in either layout of reduce_vals, or (N,); a, b: (C, n_f, n_q); center_x: (C,).
+    Returns ``(cov [C, n_f, n_f], mean [C, n_f])`` on the device: ``sum w^2 psi_i psi_j / (sum w)^2`` and
+    ``sum w psi_k / sum w``.  One pass over x."""
+    L = _L()
+    x2, ls, lc, u, w, N, C, _ = _rowmajor_operands(x, u, w)
+    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
+        _check_f64_cuda(t, name)
+    if a.dim() != 3 or a.shape[0] != C or b.shape != a.shape:
+        raise ValueError(f"a and b must both have shape ({C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
+    if center_x.shape != (C,):
+        raise ValueError(f"center_x must have shape ({C},), got {tuple(center_x.shape)}")
+    _, n_f, n_q = a.shape
+    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
+    cov = torch.empty((C, n_f, n_f), dtype=F64, device="cuda")
+    mean = torch.empty((C, n_f), dtype=F64, device="cuda")
+    ws = workspace(L.txm_influence_cov_ws_bytes(N, C, n_q))
+    check(
+        L.txm_influence_cov(_ptr(x2), ls, lc, _ptr(u), _ptr(w), N, C, n_f, n_q, float(center_u), _ptr(center_x), _ptr(a),
+                            _ptr(b), _ptr(cov), _ptr(mean), _ptr(ws), ws.numel(), _stream()),
+        "txm_influence_cov",
+    )
+    return cov, mean
+
+
 TAYLOR_MODES = {"sum": 0, "cumsum": 1, "terms": 2}
 
 

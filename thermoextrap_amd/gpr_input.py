@@ -43,30 +43,44 @@ def log_scale_matrix(alpha0: float, order: int) -> np.ndarray:
     return T
 
 
-def input_GP_from_state(state, n_rep=100, log_scale=False, sampler=None):  # noqa: N802
+def _check_method(method):
+    if method not in ("bootstrap", "delta"):
+        raise ValueError(f'method must be "bootstrap" or "delta", got {method!r}')
+
+
+def input_GP_from_state(state, n_rep=100, log_scale=False, sampler=None, method="bootstrap"):  # noqa: N802
     """(x_data, y_data, cov_data) for one ExtrapModel state.
 
     ``sampler`` overrides the default ``{"nrep": n_rep}`` (e.g. to fix a seed or
-    force the device sampler)."""
+    force the device sampler).
+
+    ``method="delta"`` (extension): ``cov_data`` is the delta-method covariance ``state.derivs_cov()`` -- one pass over
+    the samples, no sampler drawn, ``n_rep`` and ``sampler`` unused -- instead of the covariance over bootstrap
+    replicates, of which it is the first-order term.  Both assume independent samples."""
+    _check_method(method)
     order = state.order
     alphas = state.alpha0 * np.ones((order + 1, 1))
     if log_scale:
         alphas = np.log10(alphas)
     x_data = np.concatenate([alphas, np.arange(order + 1)[:, None]], axis=1)
 
-    if isinstance(state.data, DataCentralMomentsVals):
+    if method == "delta":
+        derivs = state.derivs(norm=False).values
+        cov = state._derivs_cov_device(order, state.minus_log)[0].cpu().numpy()   # (n_out, order+1, order+1)
+    elif isinstance(state.data, DataCentralMomentsVals):
         derivs = state.derivs(norm=False).values
         boot = state.resample(sampler=sampler if sampler is not None else {"nrep": n_rep})
         vals, src = boot.derivatives.derivs(data=boot.data, order=order, norm=False, minus_log=boot.minus_log,
                                             _device=True)
+        cov = engine.cov_over_rep(vals).cpu().numpy()  # (n_out, order+1, order+1)
     else:
         # pre-computed records: variance along 'rec' without resampling (reference lines 99-107)
         d = state.derivs(norm=False)
         derivs = d.mean("rec").values
         vals, src = state.derivatives.derivs(data=state.data, order=order, norm=False, minus_log=state.minus_log,
                                              _device=True)
+        cov = engine.cov_over_rep(vals).cpu().numpy()
     derivs = derivs.reshape(order + 1, -1)
-    cov = engine.cov_over_rep(vals).cpu().numpy()  # (n_out, order+1, order+1)
     if log_scale:
         T = log_scale_matrix(state.alpha0, order)
         derivs = T @ derivs
@@ -172,7 +186,7 @@ def _input_gp_sharded(coll, n_rep, log_scale, spec, local):
     return _assemble(full[:, 0].copy(), y_s, cov, log_scale, order)
 
 
-def input_GP_from_states(states, n_rep=100, log_scale=False, sampler=None, sharded=False):  # noqa: N802
+def input_GP_from_states(states, n_rep=100, log_scale=False, sampler=None, sharded=False, method="bootstrap"):  # noqa: N802
     """`input_GP_from_state` for a whole StateCollection (BASELINE config 5: 64 state points) with the
     bootstrap, the derivative evaluation and the covariance over replicates each done in ONE launch for all
     states.  The reference loops over the states calling input_GP_from_state and stacks the pieces
@@ -183,11 +197,22 @@ def input_GP_from_states(states, n_rep=100, log_scale=False, sampler=None, shard
 
     ``sharded`` (extension): True -- every rank of the torch.distributed group passes the WHOLE collection and works on
     its contiguous share of the states; "local" -- every rank passes only ITS states (rank order = state order).  One
-    all-gather of the per-state blocks; every rank returns the full tuple (see _input_gp_sharded)."""
+    all-gather of the per-state blocks; every rank returns the full tuple (see _input_gp_sharded).
+
+    ``method="delta"`` (extension): the per-state delta-method covariances (``input_GP_from_state(method="delta")``, a
+    loop over the states, one pass over each state's samples) in the same block-diagonal layout; no sampler is drawn."""
     from .models import StateCollection
 
+    _check_method(method)
     coll = states if isinstance(states, StateCollection) else StateCollection(list(states))
     spec = sampler if sampler is not None else {"nrep": n_rep}
+    if method == "delta":
+        if sharded:
+            raise NotImplementedError('method="delta" with sharded=...')
+        order = coll.order
+        parts = [input_GP_from_state(st, method="delta") for st in coll]
+        return _assemble(np.array([float(st.alpha0) for st in coll]), np.stack([p_[1] for p_ in parts]),
+                         np.stack([p_[2] for p_ in parts]), log_scale, order)
     if sharded:
         if sharded not in (True, "local"):
             raise ValueError('sharded must be False, True or "local"')

@@ -507,6 +507,113 @@ class ExtrapModel(_Params):
             return self._ds(out.cumsum(order_dim))
         return self._ds(out.sum(order_dim))
 
+    # ---- delta-method error bars -----------------------------------------------------------------------
+    def _delta_operands(self):
+        """(x [N, C], u [N], w [N] or None, central state [C, 2, K] on the host, derivative source) for ``derivs_cov`` --
+        or NotImplementedError naming what this model is that the one-pass formula does not cover."""
+        from . import moments as cm
+        from .data import DataCallback, DataCentralMoments, DataCentralMomentsVals, DataValuesBase
+
+        data, what = self.data, "derivs_cov / predict_with_error (delta-method error bars)"
+        if isinstance(data, DataCentralMoments):
+            raise NotImplementedError(f"{what}: DataCentralMoments holds reduced moments only -- there are no samples to pass "
+                                      "over; build the model on DataCentralMomentsVals")
+        if isinstance(data, DataValuesBase):
+            raise NotImplementedError(f"{what}: DataValues / DataValuesCentral are not supported; build the model on "
+                                      "DataCentralMomentsVals")
+        if not isinstance(data, DataCentralMomentsVals):
+            raise NotImplementedError(f"{what}: unsupported data object {type(data).__name__}")
+        if data.xalpha:
+            raise NotImplementedError(f"{what}: observables that depend on alpha (xalpha / deriv_dim) are not supported")
+        if data.x_is_u:
+            raise NotImplementedError(f"{what}: x_is_u data is not supported")
+        if data.rec_dim in data.dxduave.val_dims:
+            raise NotImplementedError(f"{what}: this model holds resampled data; take the error bars of the model it was "
+                                      "resampled from")
+        if type(data.meta) is not DataCallback:
+            raise NotImplementedError(f"{what}: data callbacks (volume, lnPi) are not supported")
+        if self.derivatives.series is None:
+            raise NotImplementedError(f"{what}: the Derivatives object was built from plain callables; the influence "
+                                      "functions need the polynomial series (beta.factory_derivatives, from_sympy)")
+        src = data._derivs_source()
+        state = data.dxduave if data.dxduave.val_dims == tuple(src.out_dims) else data.dxduave.transpose(
+            *src.out_dims, *data.dxduave.mom_dims)
+        xt, xdims = cm._dev_and_dims(data.xv)
+        ut, udims = cm._dev_and_dims(data.uv)
+        if tuple(udims) != (data.rec_dim,) or set(xdims) != {data.rec_dim, *src.out_dims}:
+            raise NotImplementedError(f"{what}: uv must be 1-D along {data.rec_dim!r} and xv ({data.rec_dim!r}, values...)")
+        N = xt.shape[xdims.index(data.rec_dim)]
+        x2 = xt.permute([xdims.index(d) for d in (data.rec_dim, *src.out_dims)]).reshape(N, -1)
+        wt = None
+        if data.weight is not None:
+            wt = cm._dev_and_dims(data.weight)[0] if (is_labelled(data.weight) or isinstance(data.weight, cm.DeviceDataArray)) \
+                else engine.to_device(np.asarray(data.weight))
+            if wt.shape != (N,):
+                raise NotImplementedError(f"{what}: weight must be 1-D along {data.rec_dim!r}")
+        K = state.device_values.shape[-1]
+        return x2, ut, wt, state.device_values.reshape(-1, 2, K).cpu().numpy(), src
+
+    def _derivs_cov_device(self, order, minus_log):
+        key = ("dcov", order, minus_log)
+        if key not in self._cache:
+            x2, ut, wt, st, src = self._delta_operands()
+            if order > st.shape[-1] - 1:
+                raise ValueError(f"order {order} requested, but the data object only holds moments to order {st.shape[-1] - 1}")
+            # the central state: [c][0][1] = <u>, [c][1][0] = <x_c>, [c][0][j] = <du^j>, [c][1][j] = <dx_c du^j>
+            um, xm = float(st[0, 0, 1]), st[:, 1, 0]
+            mom = S.influence_moments(xm, um, [0.0, 0.0] + [float(st[0, 0, j]) for j in range(2, order + 1)],
+                                      [0.0] + [st[:, 1, j] for j in range(1, order + 1)])
+            a, b = S.influence_coefs(self.derivatives.series, order, mom, minus_log=minus_log)
+            cov, _ = engine.influence_cov(x2, ut, engine.to_device(np.ascontiguousarray(a)),
+                                          engine.to_device(np.ascontiguousarray(b)), um, engine.to_device(xm), w=wt)
+            self._cache[key] = (cov, src)
+        return self._cache[key]
+
+    def derivs_cov(self, order=None, norm=False, minus_log=None):
+        """Delta-method (infinitesimal-jackknife) covariance of ``derivs(order)``: dims ``(order, order_2, *val_dims)``.
+
+        ``V_ij = sum_n p_n^2 psi_i(n) psi_j(n)`` with ``p_n`` the normalised sample weights and ``psi_k(n)`` the empirical
+        influence of sample n on the k-th derivative (symbolic.influence_coefs), from ONE pass over the samples
+        (txm_influence_cov) -- no replicates, no sampling noise.  It is the first-order term of what the multinomial
+        bootstrap (``resample``) estimates and, like it, assumes INDEPENDENT samples: decorrelate a time series first
+        (``timeseries.decorrelate``).  It does not replace ``resample`` where the replicates themselves are wanted.
+        ``norm=True`` carries the ``1 / (i! j!)`` factors of ``derivs(norm=True)``.
+
+        Supported: beta-extrapolation models of ``x_ave`` (central or raw, ``minus_log`` on or off, weights) over
+        ``DataCentralMomentsVals``; anything else raises NotImplementedError."""
+        if minus_log is None:
+            minus_log = self.minus_log
+        if order is None:
+            order = self.order
+        cov, src = self._derivs_cov_device(order, bool(minus_log))
+        host = cov.cpu().numpy()                                   # (n_out, order + 1, order + 1)
+        if norm:
+            f = np.array([1.0 / math.factorial(i) for i in range(order + 1)])
+            host = host * f[None, :, None] * f[None, None, :]
+        out = DataArray(np.ascontiguousarray(np.moveaxis(host, 0, -1)).reshape(order + 1, order + 1, *src.out_shape),
+                        ("order", "order_2", *src.out_dims))
+        out._inherit(src.coords)
+        return self._ds(out)
+
+    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None):
+        """``(prediction, std)``: ``predict(alpha)`` and its delta-method standard deviation ``sqrt(t' V t)``,
+        ``t_k = (alpha - alpha0)^k / k!``, ``V = derivs_cov(order)`` (named after ``MBARModel.predict_with_error``; the
+        assumptions of ``derivs_cov`` apply: independent samples, first order)."""
+        if order is None:
+            order = self.order
+        if minus_log is None:
+            minus_log = self.minus_log
+        cov, src = self._derivs_cov_device(order, bool(minus_log))
+        pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name)
+        dalpha = xrwrap_alpha(alpha, name=alpha_name or self.alpha_name) - self.alpha0
+        d = np.asarray(dalpha.values, dtype=np.float64).reshape(-1)
+        t = np.stack([d**k / math.factorial(k) for k in range(order + 1)], axis=1)            # (n_alpha, order + 1)
+        var = np.einsum("ai,cij,aj->ac", t, cov.cpu().numpy(), t)
+        std = DataArray(np.sqrt(np.maximum(var, 0.0)).reshape((*dalpha.shape, *src.out_shape)), (*dalpha.dims, *src.out_dims))
+        std._inherit(dalpha._coords)
+        std._inherit(src.coords)
+        return pred, self._ds(std)
+
     def resample(self, sampler, **kws):
         """New model on resampled data."""
         return self.new_like(order=self.order, alpha0=self.alpha0, derivatives=self.derivatives,

@@ -553,3 +553,149 @@ def to_sympy(p: Poly):
     if p.log_atom is not None:
         expr = expr - sp.log(sym(p.log_atom))
     return expr
+
+
+# ---------------------------------------------------------------------------
+# empirical influence functions of the derivatives (delta-method error bars: ExtrapModel.derivs_cov)
+# ---------------------------------------------------------------------------
+def _atom_influence(atom: Atom, mom: dict, nq: int):
+    """Influence function of one moment atom on a sample, as ``sum_q (al[q] + be[q] dx) du^q`` with ``dx = x - <x>``,
+    ``du = u - <u>`` (weighted means); ``mom`` holds xmean, umean, du[j] = <du^j>, dxdu[j] = <dx du^j> and the raw moments
+    u[j] = <u^j>, xu[j] = <x u^j> derived from them."""
+    import math
+
+    kind = atom[0]
+    if (kind == "x1" and atom[1] is not None) or (kind in ("dxdu", "xu") and atom[2] is not None):
+        raise NotImplementedError(f"influence function of {_atom_str(atom)}: observables that depend on alpha (xalpha) are "
+                                  "not supported")
+    mu, cc, xm, um = mom["du"], mom["dxdu"], mom["xmean"], mom["umean"]
+    zero = 0 * (xm + um)
+    al, be = [zero] * nq, [zero] * nq
+    j = atom[1] if len(atom) > 1 and kind != "x1" else 0
+    need = 1 if kind == "umean" else (0 if kind == "x1" else j)
+    if need >= nq:
+        raise ValueError(f"{_atom_str(atom)} needs powers of du up to {need}: more than the order {nq - 1} asked for")
+    if kind == "x1":
+        be[0] = be[0] + 1
+    elif kind == "umean":
+        al[1] = al[1] + 1
+    elif kind == "du":        # du^j - mu_j - j mu_{j-1} du
+        al[j] = al[j] + 1
+        al[0] = al[0] - mu[j]
+        al[1] = al[1] - j * mu[j - 1]
+    elif kind == "dxdu":      # dx du^j - c_j - j c_{j-1} du - mu_j dx
+        be[j] = be[j] + 1
+        al[0] = al[0] - cc[j]
+        al[1] = al[1] - j * cc[j - 1]
+        be[0] = be[0] - mu[j]
+    elif kind == "u":         # (<u> + du)^j - <u^j>
+        for q in range(j + 1):
+            al[q] = al[q] + math.comb(j, q) * um ** (j - q)
+        al[0] = al[0] - mom["u"][j]
+    elif kind == "xu":        # (<x> + dx)(<u> + du)^j - <x u^j>
+        for q in range(j + 1):
+            f = math.comb(j, q) * um ** (j - q)
+            al[q] = al[q] + xm * f
+            be[q] = be[q] + f
+        al[0] = al[0] - mom["xu"][j]
+    else:
+        raise NotImplementedError(f"no influence function for the symbol family {kind!r}")
+    return al, be
+
+
+def _partials(series, order: int):
+    """[[(atom, d series[k] / d atom), ...] for k <= order]: ``Poly.diff`` with an indicator rule; cached on the series."""
+    cache = getattr(series, "_influence_partials", None)
+    if cache is None:
+        cache = {}
+        try:
+            series._influence_partials = cache
+        except AttributeError:
+            pass
+    out = []
+    for k in range(order + 1):
+        if k not in cache:
+            p = series[k]
+            if not isinstance(p, Poly):
+                raise NotImplementedError("influence functions need a polynomial derivative series, not plain callables")
+            cache[k] = [(a, p.diff(lambda b_, a=a: Poly.const(1 if b_ == a else 0))) for a in p.atoms()]
+        out.append(cache[k])
+    return out
+
+
+def influence_moments(xmean, umean, du, dxdu) -> dict:
+    """The moment values ``influence_coefs`` takes: ``du[j] = <du^j>``, ``dxdu[j] = <dx du^j>`` for j = 0 .. order
+    (``du[0] = 1``, ``du[1] = 0``, ``dxdu[0] = 0`` are imposed), ``xmean`` / ``dxdu[j]`` scalars or arrays over columns; the raw
+    moments about zero follow binomially.  Arithmetic is that of the arguments (float64, or long double in tests)."""
+    import math
+
+    mu = [1 + 0 * umean, 0 * umean] + [du[j] for j in range(2, len(du))]
+    cc = [0 * xmean] + [dxdu[j] for j in range(1, len(dxdu))]
+    K = min(len(mu), len(cc))
+    ru = [sum(math.comb(j, q) * umean ** (j - q) * mu[q] for q in range(j + 1)) for j in range(K)]
+    rxu = [sum(math.comb(j, q) * umean ** (j - q) * (xmean * mu[q] + cc[q]) for q in range(j + 1)) for j in range(K)]
+    return {"xmean": xmean, "umean": umean, "du": mu, "dxdu": cc, "u": ru, "xu": rxu}
+
+
+def influence_coefs(series, order: int, moments: dict, minus_log: bool = False):
+    """Coefficients of the empirical influence functions of the derivatives ``series[0] .. series[order]``:
+
+        psi_k(n) = sum_q (a[..., k, q] + b[..., k, q] dx_n) du_n^q,   dx = x - <x>,  du = u - <u>,   k, q <= order,
+
+    so that ``d_k`` changes by ``sum_n dp_n psi_k(n)`` to first order when the normalised weights change by ``dp``, and the
+    delta-method (infinitesimal-jackknife) covariance of the derivatives is ``V_ij = sum_n p_n^2 psi_i(n) psi_j(n)``.
+    ``psi_k = sum_atoms (d series[k] / d atom) * influence(atom)``: the partial derivatives come from ``Poly.diff`` with an
+    indicator rule (the ``-log`` term included) and are evaluated at ``moments`` (``influence_moments``); the atoms'
+    influence functions are collected by powers of ``du``, with and without ``dx``.  ``minus_log=True`` applies the
+    ``-log`` chain rule to the derivatives afterwards, as ``ExtrapModel(minus_log=True)`` does.
+
+    Returns ``(a, b)``, arrays of shape ``(*cols, order + 1, order + 1)`` where ``cols`` is the shape the moments broadcast
+    to (``()`` for one column).  Supported atoms: x1, umean, du[j], dxdu[j], u[j], xu[j] without a derivative index."""
+    import numpy as np
+
+    nq = order + 1
+    vals = {("x1", None): moments["xmean"], ("umean",): moments["umean"]}
+
+    def resolve(atom):
+        if atom in vals:
+            return vals[atom]
+        kind = atom[0]
+        if kind in ("du", "u") and len(atom) == 2 and atom[1] < len(moments[kind]):
+            return moments[kind][atom[1]]
+        if kind in ("dxdu", "xu") and len(atom) == 3 and atom[2] is None and atom[1] < len(moments[kind]):
+            return moments[kind][atom[1]]
+        _atom_influence(atom, moments, nq)   # raises for what is not supported
+        raise ValueError(f"no moment value for {_atom_str(atom)}")
+
+    rows_a, rows_b = [], []
+    for parts in _partials(series, order):
+        ak = [0 * (moments["xmean"] + moments["umean"])] * nq
+        bk = list(ak)
+        for atom, dpoly in parts:
+            al, be = _atom_influence(atom, moments, nq)
+            g = eval_host(dpoly, resolve)
+            ak = [s + g * t for s, t in zip(ak, al)]
+            bk = [s + g * t for s, t in zip(bk, be)]
+        rows_a.append(ak)
+        rows_b.append(bk)
+    if minus_log:
+        X = [eval_host(series[k], resolve) for k in range(order + 1)]
+        ml = DerivSeries(Poly.atom(("X", 0)), rule=chain_rule, post_func="minus_log")
+        new_a, new_b = [], []
+        for parts in _partials(ml, order):
+            ak = [0 * X[0]] * nq
+            bk = list(ak)
+            for atom, dpoly in parts:
+                g = eval_host(dpoly, lambda at: X[at[1]])
+                ak = [s + g * t for s, t in zip(ak, rows_a[atom[1]])]
+                bk = [s + g * t for s, t in zip(bk, rows_b[atom[1]])]
+            new_a.append(ak)
+            new_b.append(bk)
+        rows_a, rows_b = new_a, new_b
+
+    def pack(rows):
+        flat = np.broadcast_arrays(*[np.asarray(v) for row in rows for v in row])
+        arr = np.stack(flat, axis=-1)
+        return arr.reshape(*arr.shape[:-1], nq, nq)
+
+    return pack(rows_a), pack(rows_b)
