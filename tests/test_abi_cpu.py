@@ -433,6 +433,31 @@ def test_csrc_sha_covers_the_public_header_and_the_build_flags(monkeypatch, tmp_
     assert _build.csrc_sha() != base
 
 
+def test_build_switches_are_the_five_kept_ones():
+    """The kernel sources test no TXM_* build switch but the source hash and the four diagnostic builds (all of which still
+    produce the right sums), the product flags define none, and DESIGN.md's switch table names the four."""
+    from thermoextrap_amd import _build
+
+    tested = set()
+    for f in sorted(_build.CSRC.glob("*.hip")) + sorted(_build.CSRC.glob("*.h")):
+        for line in f.read_text().splitlines():
+            m = re.match(r"\s*#\s*(ifdef|ifndef|if|elif)\b(.*)", line)
+            if not m:
+                continue
+            cond = re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+            if m.group(1) in ("ifdef", "ifndef"):
+                tested.update(re.findall(r"[A-Za-z_]\w*", cond)[:1])
+            else:
+                tested.update(w for w in re.findall(r"[A-Za-z_]\w*", cond) if w != "defined")
+    diagnostic = {"TXM_G_TIMING", "TXM_I8T_TIMING", "TXM_GN_TIMING", "TXM_G_CLOCKS"}
+    assert tested == {"TXM_CSRC_SHA"} | diagnostic, sorted(tested)
+    for flags in [_build.FLAGS, *_build.EXTRA_FLAGS.values()]:
+        assert not any("-DTXM_" in fl for fl in flags), flags
+    table = [ln for ln in (ROOT / "DESIGN.md").read_text().splitlines() if ln.startswith("|")]
+    for sw in diagnostic:
+        assert any(ln.startswith(f"| `{sw}` |") for ln in table), f"{sw} is missing from DESIGN.md's switch table"
+
+
 def test_graft_entry_build_runs(lib):
     """The driver's build check: __graft_entry__.build() compiles (a no-op when the library is current), loads and checks
     the ABI version the binding expects -- it carried a literal 1 into the round that made the ABI 2."""

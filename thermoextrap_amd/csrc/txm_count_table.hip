@@ -45,11 +45,7 @@ __global__ __launch_bounds__(T_BLOCK) void count_table_kernel(const uint32_t *__
     __syncthreads();  // the previous tile's write-out has read the count tile
     for (int e = threadIdx.x; e < T_CNT_BYTES / 16; e += T_BLOCK) reinterpret_cast<uint4 *>(cntw)[e] = make_uint4(0, 0, 0, 0);
     __syncthreads();
-#ifdef TXM_CT_NO_FILL  // (timing build: zeroed tiles written out -- what the write-out path alone costs)
-    if (false) {
-#else
     if (any_live) {
-#endif
       // live replicates of this half group; <= 32 -- the call's last one: 8 of 64 at nrep = 200 -- and FP = fill_pack lanes share
       // a replicate and take FP consecutive Philox calls of it: 1 / FP of the wave instructions of the lane-per-replicate fill for
       // the same draws (which lane runs a call of the stream is free: the count words are atomics).  The fill phase of
@@ -118,15 +114,9 @@ __global__ __launch_bounds__(T_BLOCK) void count_table_kernel(const uint32_t *__
       const uint32_t *src = cntw + (8 * s + 4 * (L >> 5)) * I8_REPS + rl;
       uint4 v = make_uint4(src[0], src[I8_REPS], src[2 * I8_REPS], src[3 * I8_REPS]);
       if (rep0 + rl >= nrep) v = make_uint4(0, 0, 0, 0);
-#ifdef TXM_CT_NO_STORE  // (timing build: the fill alone)
-      if (v.x == 0xdeadbeefu) *reinterpret_cast<uint4 *>(out_t + (size_t)L * 16) = v;
-#elif defined(TXM_CT_PLAIN_STORE)
-      *reinterpret_cast<uint4 *>(out_t + (size_t)s * G_KSTEP_BYTES + (size_t)ql * 1024 + (size_t)L * 16) = v;
-#else
       typedef uint32_t ct_v4u __attribute__((ext_vector_type(4)));
       const ct_v4u vv = {v.x, v.y, v.z, v.w};
       __builtin_nontemporal_store(vv, reinterpret_cast<ct_v4u *>(out_t + (size_t)s * G_KSTEP_BYTES + (size_t)ql * 1024 + (size_t)L * 16));
-#endif
     }
   }
 }
@@ -140,11 +130,9 @@ int launch_count_table(const uint32_t *counts, int64_t nrep, int64_t N, uint32_t
   }
   // runs of tiles per workgroup: enough workgroups to fill the chip several times over, long enough runs to stream
   // the tile counts (32 per cache line)
-#ifndef TXM_CT_ROUNDS  // (A/B builds)
-#define TXM_CT_ROUNDS 4
-#endif
+  constexpr int CT_ROUNDS = 4;
   int tpb = 32;
-  while (tpb > 1 && cdiv(ntiles, tpb) * 2 * n_groups < TXM_CT_ROUNDS * (int64_t)num_cus()) tpb /= 2;
+  while (tpb > 1 && cdiv(ntiles, tpb) * 2 * n_groups < CT_ROUNDS * (int64_t)num_cus()) tpb /= 2;
   const dim3 grid((unsigned)cdiv(ntiles, tpb), (unsigned)(2 * n_groups));
   TXM_SET_MAX_LDS(count_table_kernel, T_CNT_BYTES);
   hipLaunchKernelGGL(count_table_kernel, grid, dim3(T_BLOCK), T_CNT_BYTES, st, counts, nrep, ntiles, N,

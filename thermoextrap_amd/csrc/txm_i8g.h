@@ -23,42 +23,20 @@ static inline size_t count_table_bytes(int64_t ntiles, int64_t nreps) {
 // ---- pieces shared by the table-fed contraction kernels (txm_resample_i8g.hip: wide states; txm_resample_i8gn.hip: narrow states)
 constexpr int G_BS = 4;  // k-steps per block (one barrier per block)
 constexpr int G_RAW = 2 * G_BS * 256;  // one raw buffer: u then w of a block's chunks
-#ifndef TXM_G_LEAD
-#define TXM_G_LEAD 2
-#endif
-constexpr uint32_t G_LEAD = TXM_G_LEAD;  // tiles a replicate group may run ahead of the slowest one of its window
+constexpr uint32_t G_LEAD = 2;  // tiles a replicate group may run ahead of the slowest one of its window
 
 // LDS-DMA: 16 (4) bytes per lane from saddr + voff to the LDS address in M0 + 16 (4) * lane
 __device__ __forceinline__ void g_dma16(const void *sbase, uint32_t voff, uint32_t lds_dst) {
-#ifdef TXM_G_NO_DMA  // ablation build
-  return;
-#endif
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(voff), "s"(lds_dst) : "memory", "m0");
 }
 // ... the same with the non-temporal hint: the count words of the table, which ONE workgroup reads once per pass (x, which the
 // replicate groups of a window share through the L2, keeps the plain form).  Same box, north-star call, three rounds: 159.9 / 160.8 /
-// 161.0 ms plain against 159.4 / 159.0 / 160.2 ms (profiles/r06_table_nt_ab.txt); -DTXM_G_TABLE_PLAIN is the A/B build.
+// 161.0 ms plain against 159.4 / 159.0 / 160.2 ms (profiles/r06_table_nt_ab.txt).
 __device__ __forceinline__ void g_dma16_stream(const void *sbase, uint32_t voff, uint32_t lds_dst) {
-#ifdef TXM_G_NO_DMA
-  return;
-#endif
-#ifdef TXM_G_TABLE_PLAIN  // (A/B build)
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" ::"s"(sbase), "v"(voff), "s"(lds_dst) : "memory", "m0");
-#else
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0 nt" ::"s"(sbase), "v"(voff), "s"(lds_dst) : "memory", "m0");
-#endif
 }
 __device__ __forceinline__ void g_dma4(const void *sbase, uint32_t voff, uint32_t lds_dst) {
-#ifdef TXM_G_NO_DMA
-  return;
-#endif
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, %0" ::"s"(sbase), "v"(voff), "s"(lds_dst) : "memory", "m0");
-}
-// (TXM_G_ADIR experiment) 16 bytes per lane from saddr + voff into registers, as an asm the compiler does not track: it cannot count
-// the DMA pieces above either, and for a load it DOES see across the loop's back edge it falls back to s_waitcnt vmcnt(0) at the top of
-// every block -- the waits are written by hand (g_wait_vm) from the issue order of the block
-__device__ __forceinline__ void g_load16(v4i &dst, const void *sbase, uint32_t voff) {
-  asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(sbase) : "memory");
 }
 // sixteen progress words of a window, read past the scalar cache (glc): SMEM counts on lgkmcnt, so a poll does not touch
 // the wave's vmcnt queue of DMAs

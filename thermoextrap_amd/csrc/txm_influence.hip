@@ -24,9 +24,7 @@
 
 namespace txm {
 
-#ifndef TXM_INF_VEC2_MAXQ  // (A/B builds: the largest n_q that takes two columns per lane)
-#define TXM_INF_VEC2_MAXQ 6
-#endif
+constexpr int INF_VEC2_MAXQ = 6;  // the largest n_q that takes two columns per lane
 constexpr int INF_BLOCK = 256;
 constexpr int INF_CH = 8;  // values per pass of the block reductions (8 * 256 doubles of LDS)
 
@@ -300,7 +298,7 @@ static InfPlan influence_plan(const double *x, int64_t ldx_s, int64_t ldx_c, int
   p.rowmajor = ldx_c == 1 && !(C == 1 && ldx_s == 1);
   if (p.rowmajor) {
     // two columns per lane (16-byte loads) while the sums of both columns fit the register file at two waves per SIMD
-    const bool vec2 = (C % 2 == 0) && (ldx_s % 2 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && n_q <= TXM_INF_VEC2_MAXQ;
+    const bool vec2 = (C % 2 == 0) && (ldx_s % 2 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && n_q <= INF_VEC2_MAXQ;
     p.vec = vec2 ? 2 : 1;
     const int64_t lanes = cdiv(C, p.vec);
     int l2 = 0;
@@ -347,7 +345,7 @@ static int influence_launch(const InfPlan &p, const double *x, int64_t ldx_s, co
   hipLaunchKernelGGL((influence_rowmajor_kernel<NQ, VEC, WT>), grid, block, 0, st, x, ldx_s, u, w, N, C, cu, cx, p.lpr_log2, \
                      partial)
     if (p.vec == 2) {
-      if constexpr (NQ <= TXM_INF_VEC2_MAXQ) {
+      if constexpr (NQ <= INF_VEC2_MAXQ) {
         if (w) TXM_INF_RM(2, true); else TXM_INF_RM(2, false);
       } else {
         set_error("influence_cov: no two-column kernel for n_q=%d", NQ);

@@ -29,17 +29,13 @@ namespace txm {
 
 // Streaming loads of the sample matrix: every element is read exactly once, so the loads are marked non-temporal (no allocation in
 // the caches; what IS re-read -- u, w, the pivots -- keeps its place).  Same box, N = 1e8, 32 observables, order 4: 4.46 - 4.55 ms
-// (5.8 - 5.9 TB/s) -> 4.09 - 4.14 ms (6.4 - 6.5 TB/s = 0.80 of the 8 TB/s peak) -- profiles/r06_reduce_nt_ab.txt; -DTXM_RED_NO_NT is
-// the A/B build; more rows in flight per lane (-DTXM_RED_UNR=8) or fewer (2) are slower (4.76 / 4.69 ms).  The 1-D reduction over
+// (5.8 - 5.9 TB/s) -> 4.09 - 4.14 ms (6.4 - 6.5 TB/s = 0.80 of the 8 TB/s peak) -- profiles/r06_reduce_nt_ab.txt;
+// more rows in flight per lane (UNR = 8) or fewer (2) are slower (4.76 / 4.69 ms).  The 1-D reduction over
 // (state, rec) series (BASELINE config 3): 0.222 -> 0.197 ms (5.8 -> 6.5 TB/s).
 typedef double red_v2d __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double2 red_ld2(const double *p) {
-#ifdef TXM_RED_NO_NT
-  return *reinterpret_cast<const double2 *>(p);
-#else
   const red_v2d t = __builtin_nontemporal_load(reinterpret_cast<const red_v2d *>(p));
   return make_double2(t.x, t.y);
-#endif
 }
 // (the 8-byte path of odd or unaligned row pitches keeps plain loads: its rows share cache lines with their neighbours, which
 // other wave instructions load -- non-temporal there re-fetches them: N = 1e8, 33 observables: 8.94 -> 9.23 ms)
@@ -70,10 +66,7 @@ __global__ __launch_bounds__(RED_BLOCK) void reduce_rowmajor_kernel(
     partial += (size_t)blockIdx.z * gridDim.y * gridDim.x * (LPR * VEC) * 2 * K;
   }
   constexpr int ROWS = RED_BLOCK / LPR;
-#ifndef TXM_RED_UNR  // (A/B builds: rows in flight per lane)
-#define TXM_RED_UNR 4
-#endif
-  constexpr int UNR = TXM_RED_UNR;
+  constexpr int UNR = 4;  // rows in flight per lane
   const int tid = threadIdx.x;
   const int lir = tid & (LPR - 1);
   const int rib = tid >> LPR_LOG2;

@@ -49,13 +49,11 @@ constexpr int RS_QUARTER = SM_T / 4;                  // 256 samples per lane-gr
 constexpr int RS_TILE_BYTES = SM_T * RS_REPS;         // 16384 bytes per wave
 // steps per register-prefetch group: as many as the VGPR budget (2 waves/SIMD,
 // 256 VGPRs) allows next to the K*NBLK accumulator tiles.
+constexpr int RS_EXP_BUDGET = 160;
 constexpr int rs_group(int K, int NBLK, bool weighted, bool explicit_, int pack = 1) {
   const int per_step = 2 + 2 * NBLK + (weighted ? 2 : 0) + (explicit_ ? 10 : 0);
   for (int g = 8; g > 2; g >>= 1)
-#ifndef TXM_EXP_BUDGET
-#define TXM_EXP_BUDGET 160
-#endif
-    if ((K + pack - 1) / pack * NBLK * 8 + 2 * g * per_step <= TXM_EXP_BUDGET) return g;
+    if ((K + pack - 1) / pack * NBLK * 8 + 2 * g * per_step <= RS_EXP_BUDGET) return g;
   return 2;
 }
 
@@ -802,10 +800,8 @@ static I8Plan plan_i8(int64_t N, int64_t C, int64_t nrep, int K) {
   // summation, so a replicate's bits must not depend on nrep / the chunking (txm_sampler_spec.rep0: replicate slabs of
   // a multi-GPU run equal the one-GPU rows bit for bit).
   p.win_tiles = I8_WIN_TILES;
-#ifndef TXM_WIN_MIN  // (A/B builds: fewer, longer windows on short series)
-#define TXM_WIN_MIN 256
-#endif
-  while (p.win_tiles > 4 && p.ntiles < TXM_WIN_MIN * p.win_tiles) p.win_tiles /= 4;  // >= 256 windows where N allows
+  constexpr int WIN_MIN = 256;
+  while (p.win_tiles > 4 && p.ntiles < WIN_MIN * p.win_tiles) p.win_tiles /= 4;  // >= 256 windows where N allows
   p.nwin = cdiv(p.ntiles, p.win_tiles);
   // one workgroup per CU: chunks (whole windows) x replicate groups should fill the CUs once, not 1.1 times
   int64_t nc = (int64_t)num_cus() / p.n_rbg / 8 * 8;
@@ -854,15 +850,6 @@ static I8Plan plan_i8(int64_t N, int64_t C, int64_t nrep, int K) {
 // txm_resample_opts.path does not look at this word either.
 static int g_path_override = -1;
 static int path_override() { return g_path_override; }
-
-// the L2-sharing hint of the bootstrap kernels; an A/B build without it: -DTXM_NO_THROTTLE (tools/build_variant.sh)
-static constexpr bool throttle_on() {
-#ifdef TXM_NO_THROTTLE
-  return false;
-#else
-  return true;
-#endif
-}
 
 // Wide states on the int8 path: which of its two contraction kernels.  They agree bit for bit (the same int32 sums, the same
 // flush), so this is a rule on speed alone -- measured on MI355X, pre-pass block kept, ms per call fused / table
@@ -1117,14 +1104,6 @@ extern "C" int txm_resample_i8_supported(int64_t N, int64_t C, int64_t nrep, int
   }
 
 namespace txm {
-// narrow states: several powers per B-operand column; an A/B build with one power per column: -DTXM_NO_PACK
-static constexpr bool pack_on() {
-#ifdef TXM_NO_PACK
-  return false;
-#else
-  return true;
-#endif
-}
 template <int K>
 static int run_resample(ResampleArgs a, const ResamplePlan &p, bool weighted, bool explicit_,
                         double *out, hipStream_t st, int64_t S = 1) {
@@ -1145,7 +1124,7 @@ static int run_resample(ResampleArgs a, const ResamplePlan &p, bool weighted, bo
   // narrow states (C <= 8, device sampler, full tiles): PACK powers per B column -> ceil(K / PACK) MFMAs per k-step
   bool packed = false;
   if constexpr (K >= 2 && K <= 6) {
-    if (p.nblk == 1 && p.colgroups == 1 && !explicit_ && a.N >= SM_T && a.C <= 8 && pack_on()) {
+    if (p.nblk == 1 && p.colgroups == 1 && !explicit_ && a.N >= SM_T && a.C <= 8) {
       packed = true;
       const bool bat = S > 1 || a.batch != nullptr;
 #define TXM_RS_PACKED(PK)                                                                                      \
@@ -1291,7 +1270,7 @@ static int resample_vals_impl(const double *x, int64_t ldx_s, const double *u, c
     b.ypivot = ypiv;
     b.part_y = (double *)((char *)ws + q.off_py);
     b.part_summed = i8t_wide_summed(with_y) ? 1 : 0;  // (what the wide fused kernel's instances of this call store: the finalize's mode below)
-    b.progress = (throttle_on() && q.n_rbg > 1) ? (uint32_t *)((char *)ws + q.off_prog) : nullptr;
+    b.progress = q.n_rbg > 1 ? (uint32_t *)((char *)ws + q.off_prog) : nullptr;
     // the FP64 kernel in listed mode: contracts the windows the precision guard flags (none on ordinary data)
     ResampleArgs f;
     f.ldx_s = ldx_s; f.u = u; f.w = w; f.N = N; f.nrep = nrep;
@@ -1338,7 +1317,7 @@ static int resample_vals_impl(const double *x, int64_t ldx_s, const double *u, c
           have_table = true;
         }
         I8Args bg = b;
-        bg.progress = (throttle_on() && nrep > G_REPS) ? (uint32_t *)((char *)ws + q.off_gprog) : nullptr;
+        bg.progress = nrep > G_REPS ? (uint32_t *)((char *)ws + q.off_gprog) : nullptr;
         rc = C > 16 ? launch_resample_i8g(bg, K, w != nullptr, table, 0, (int)cdiv(nrep, G_REPS), st)
                     : launch_resample_i8gn(bg, K, w != nullptr, table, 0, (int)cdiv(nrep, G_REPS), 0, st);
       } else {
@@ -1442,7 +1421,7 @@ static int resample_vals_impl(const double *x, int64_t ldx_s, const double *u, c
   a.nrep_pad = p.nrep_pad; a.C_pad = p.C_pad;
   a.list = nullptr; a.n_list = nullptr; a.sub_tiles = 0; a.col_off = 0; a.batch = nullptr;
   a.progress = nullptr;
-  if (throttle_on() && p.n_rbg > 1 && a.N >= SM_T) {
+  if (p.n_rbg > 1 && a.N >= SM_T) {
     a.progress = (uint32_t *)((char *)ws + p.off_prog);
     TXM_HIP(hipMemsetAsync(a.progress, 0, p.prog_bytes, st));
   }

@@ -58,12 +58,7 @@ constexpr int G_WIDE_Q = 6;                                    // ... and the wi
 // x is not shared -- wave w is the only reader of column quad w -- so its trip through the LDS bought nothing and cost the loader
 // waves 8 of their 14 DMA pieces a block.
 template <int JN, bool YS, int NQ>
-constexpr bool G_XDIR =
-#if defined(TXM_G_AB_NO_XDIR) || defined(TXM_G_ADIR)  // (A/B build: x through the LDS ring in every pass)
-    false;
-#else
-    !YS && JN == 2 && NQ == 4;
-#endif
+constexpr bool G_XDIR = !YS && JN == 2 && NQ == 4;
 template <int JN, bool YS, int NQ>
 constexpr int G_XRING = YS ? 2 * G_XR : G_XDIR<JN, YS, NQ> ? 0 : G_XRB;  // 1-KiB x (+ y) ring slots per wave
 
@@ -83,17 +78,8 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
   static_assert(G_BS * NQ % T_WAVES == 0, "count pieces per wave");
   constexpr int OFF_A = T_WAVES * WREG;                           // [2][G_BS][A_STEP] count words
   constexpr bool XBLK = !YS;                                      // x requested per block (8-slot ring) / per step (4 slots, + y)
-#ifdef TXM_G_ADIR
-  // (experiment, round 6) the count words of a two-row-set pass straight from global memory into registers: the table is in
-  // MFMA-A-operand order already, a pass of two row sets has 64 registers to spare -- A[step of the block][quarter], reloaded for
-  // the NEXT block right behind the operand's last MFMA (one block = four k-steps of lead).  No count ring in the LDS (32 of the
-  // 100 KiB a k-step moves through it), no count pieces among the loader waves' DMA (16 of 50 a block).
-  constexpr bool ADIR = XBLK && NS == 2;
-#else
-  constexpr bool ADIR = false;
-#endif
   constexpr bool XDIR = G_XDIR<JN, YS, NQ>;                       // x from global memory into the register ring X (no x ring)
-  static_assert(!XDIR || (XBLK && !ADIR), "x into registers: passes without a second matrix");
+  static_assert(!XDIR || XBLK, "x into registers: passes without a second matrix");
   constexpr int XRN = XDIR ? 0 : XBLK ? G_XRB : G_XR;
   static_assert((YS ? 2 : 1) * XRN == G_XRING<JN, YS, NQ>, "ring slots as the launch sizes them");
   constexpr int OFF_X = OFF_A + 2 * G_BS * A_STEP;                // [wave][XRN][32 samples][4 columns] doubles
@@ -198,9 +184,6 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
   for (int Q = 0; Q < NQ; ++Q) qoff[Q] = q_off(Q);
   auto x_request = [&](int slot) {  // chunk cq -> ring slot; chunks past the window re-read its last one
-#ifdef TXM_G_NO_XDMA  // ablation build
-    if (slot >= 0) { ++cq; return; }
-#endif
     if constexpr (XBLK) {
       if (loader) {
         const uint32_t ln = g_lane_now();
@@ -253,9 +236,6 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // ---- count words of block B -> ring buffer B & 1: the wave's two 1-KiB pieces
   auto a_request = [&](int B, int piece = -1) {
     const int Bc = B < nblk ? B : nblk - 1;
-#ifdef TXM_G_NO_ADMA  // ablation build
-    if (Bc >= 0) return;
-#endif
     if constexpr (XBLK) {  // loader wave w: the NQ 1-KiB pieces of the block's k-step w (piece >= 0: that one only)
       if (!loader) return;
       const unsigned char *src = tab + (size_t)(Bc * G_BS + wave) * G_KSTEP_BYTES;
@@ -292,10 +272,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // ---- factors of block B from raw buffer B % 3 into factor buffer B % 3 (two waves, one sample per lane: waves 0 and 1 where
   // the older waves load, else waves 6 and 7)
   auto stage_factors = [&](int B) {
-#ifndef TXM_G_SW
-#define TXM_G_SW 6
-#endif
-    constexpr int SW = TXM_G_SW;  // first staging wave
+    constexpr int SW = 6;  // first staging wave
     if (wave < SW || wave >= SW + 2) return;  // uniform
     const int e = (int)g_lane_now() + (wave - SW) * 64;  // entry: chunk-in-block e >> 5, sample e & 31
     const double *raw = reinterpret_cast<const double *>(lds + OFF_RAW + (B % 3) * G_RAW);
@@ -322,28 +299,6 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
   // ---- store the fixed-point words of the wave's two units of one row set (as resample_i8t_kernel: four 256-byte runs)
   auto store_x2 = [&](uint32_t lo0, uint32_t hi0, uint32_t lo1, uint32_t hi1, int off) {
-#ifdef TXM_G_PLAIN_STORES  // (experiment: stores the compiler can see and count in its s_waitcnt lgkmcnt values -- the four
-    // ds_write_addtid_b32 of the asm below are invisible to it, so every wait it derives is up to four operations too strict)
-    typedef __attribute__((address_space(3))) uint32_t *lds_u32;
-    const uint32_t base = wreg + g_lane_now() * 4u;
-    *(lds_u32)(lds + base + off) = lo0;
-    *(lds_u32)(lds + base + off + T_PLANE + 128) = hi0;
-    *(lds_u32)(lds + base + off + 256) = lo1;
-    *(lds_u32)(lds + base + off + 256 + T_PLANE + 128) = hi1;
-    return;
-#endif
-#ifdef TXM_G_PLAIN_STORES_ASM  // (experiment, round 6: the SAME two paired stores the compiler makes of TXM_G_PLAIN_STORES, but inside an
-    // asm it cannot count -- the two builds differ only in how strict the s_waitcnt lgkmcnt values behind them are)
-    {
-      const uint32_t base = wreg + g_lane_now() * 4u + (uint32_t)off;
-      asm volatile("ds_write2st64_b32 %0, %1, %2 offset0:0 offset1:1\n\t"
-                   "ds_write2st64_b32 %3, %4, %5 offset0:0 offset1:1"
-                   :
-                   : "v"(base), "v"(lo0), "v"(lo1), "v"(base + (uint32_t)(T_PLANE + 128)), "v"(hi0), "v"(hi1)
-                   : "memory");
-      return;
-    }
-#endif
     asm volatile("s_mov_b32 m0, %4\n\ts_nop 0\n\t"
                  "ds_write_addtid_b32 %0 offset:%5\n\t"
                  "ds_write_addtid_b32 %1 offset:%6\n\t"
@@ -366,11 +321,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
       lo[uu] = (uint32_t)bits ^ 0x80808080u;
       hi[uu] = (uint32_t)(bits >> 32) ^ 0x00008080u;
     }
-#ifdef TXM_G_NO_OVERLAY  // ablation build
-    if (false) {
-#else
     if (fi < JN && ofi == fi) {  // wave-uniform: this wave carries digits of the row set's u-row monomial in byte 7
-#endif
       // (the permute as a volatile asm: the compiler must keep the branch -- if-converted, all eight waves executed the
       // overlay of all three row sets, 30 vector instructions per k-step instead of 10 on six waves)
 #pragma unroll
@@ -418,7 +369,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (nothing of the compiler's is in flight behind the DMAs below)
   raw_request(0);
   raw_request(1);
-  if constexpr (!ADIR) a_request(0);
+  a_request(0);
   if constexpr (XDIR) {  // chunk 0 is in x0; block 0's chunks 1..4 into X[0..3]
     x_advance();
     t_static_for<G_BS>([&](auto ic) { x_load(ic); });
@@ -430,22 +381,6 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
     for (int c = 0; c < G_XR; ++c) x_request(c);
   }
-  v4i AD[
-#ifdef TXM_G_ADIR
-      (XBLK && NS == 2) ? G_BS : 1
-#else
-      1
-#endif
-  ][NQ];  // (ADIR) the count operands of the block's four steps
-#ifdef TXM_G_ADIR
-  if constexpr (XBLK && NS == 2) {
-    const uint32_t l16 = g_lane_now() * 16u;
-#pragma unroll
-    for (int pp = 0; pp < G_BS; ++pp)
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) g_load16(AD[pp][q], tab + (size_t)pp * G_KSTEP_BYTES + qoff[q], l16);
-  }
-#endif
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   stage_factors(0);
   {
@@ -500,9 +435,6 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // one XCD and read the same x -- every tile (8 blocks) wave 0 publishes the tiles this group has finished and sleeps while
   // it is more than G_LEAD tiles ahead of the slowest started group, so that the window's x is streamed from HBM once
   uint32_t *pg = a.progress != nullptr ? a.progress + (size_t)win * 16 : nullptr;
-#ifdef TXM_G_PRIO  // experiment: the younger wave of every SIMD at a higher issue priority
-  if (wave >= 4) __builtin_amdgcn_s_setprio(TXM_G_PRIO);
-#endif
   // ---- what a slot reads one slot AHEAD (see below): the factors of the next row set, the raw x of the next chunk
   auto read_factors = [&](auto pnc, auto finc, uint32_t fb, double (&f)[2]) {
     constexpr int pn = decltype(pnc)::value, fin = decltype(finc)::value;
@@ -538,9 +470,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
   {
     const uint32_t a_va0 = (uint32_t)OFF_A + (uint32_t)lane * 16u;
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      if constexpr (!ADIR) A[q] = *(lds_cv4)(lds + a_va0 + q * 1024);
-    }
+    for (int q = 0; q < NQ; ++q) A[q] = *(lds_cv4)(lds + a_va0 + q * 1024);
     Bt[0][0] = T_TRREAD((lds_v2i)(lds + rd_off));
     Bt[0][1] = T_TRREAD((lds_v2i)(lds + rd_off + 128));
     read_factors(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, f_va, f);
@@ -581,38 +511,21 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
       }
     }
     auto a_piece = [&](int Q) {
-#ifndef TXM_G_NO_ADMA
-      if constexpr (!ADIR)
-        if (loader) g_dma16_stream(blk_asrc + qoff[Q], blk_l16, blk_adst + (uint32_t)(Q * 1024));
-#endif
+      if (loader) g_dma16_stream(blk_asrc + qoff[Q], blk_l16, blk_adst + (uint32_t)(Q * 1024));
     };
-    // (ADIR) the next block's count words: this lane's 16 bytes of every (step, quarter) piece
-    const unsigned char *nb_src = nullptr;
-    uint32_t nb_l16 = 0;
-    if constexpr (ADIR) {
-      const int Bn = B + 1 < nblk ? B + 1 : nblk - 1;
-      nb_src = tab + (size_t)(Bn * G_BS) * G_KSTEP_BYTES;
-      nb_l16 = g_lane_now() * 16u;
-    }
     auto x_chunk = [&](int i) {  // chunk cq -> slot i of the ring half the next block reads: the wave's own columns and its partner's
-#ifndef TXM_G_NO_XDMA
       if (loader) {
         const uint32_t dst = xring + (uint32_t)((4 * ((B + 1) & 1) + i) * 1024);
         g_dma16(xq + xcol1, blk_xrow, dst);
         g_dma16(xq + xcol2, blk_xrow, dst + (uint32_t)(4 * XRN * 1024));
       }
-#endif
       ++cq;
       if (cq < nsteps) {
         if ((cq & 31) == 0) xq = reinterpret_cast<const char *>(a.x + chunk_sample(cq) * a.ldx_s);  // a new tile
         else xq += xstep;
       }
     };
-#ifdef TXM_G_BURST  // (experiment build: the next block's count words and x requested here, 14 pieces per loader wave at once)
-    constexpr bool SPREAD = false;
-#else
     constexpr bool SPREAD = XBLK && NS >= 2;  // (one row set: a step is short, two bursts of 6 cost more than one of 12: 77.7 -> 75.6 ms at order 0)
-#endif
     if constexpr (!SPREAD) {
       if constexpr (XBLK) {  // the next block's count words and x (chunks 4 (B + 1) + 1 .. + 4 into the ring half this block does not read)
 #pragma unroll
@@ -632,10 +545,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
     auto issue_items = [&](auto kc) {
       constexpr int k = decltype(kc)::value;
       if constexpr (SPREAD && k < ISSUE_SLOTS) {
-        if constexpr (ADIR) {  // four x chunks over the four slots of steps 0 and 1
-          static_assert(!ADIR || ISSUE_SLOTS == G_BS, "one x chunk a slot");
-          x_chunk(k);
-        } else if constexpr (XDIR) {  // count pieces only: x goes into registers
+        if constexpr (XDIR) {  // count pieces only: x goes into registers
 #pragma unroll
           for (int j = 0; j < NQ; ++j)
             if (j * ISSUE_SLOTS / NQ == k) a_piece(j);
@@ -667,39 +577,16 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
     // row set; the waits the compiler derives are lgkmcnt(6) and up -- nothing drains but the block's barrier.
     // (An experiment that let the younger wave of a SIMD take the barrier behind the last row set's MFMAs -- the waves of a
     // SIMD out of phase -- was slower: 114.4 against 107.9 ms at order 2.)
-#ifdef TXM_G_NO_PIN
-#define G_PIN() do {} while (0)
-#else
 #define G_PIN() __builtin_amdgcn_sched_barrier(0)
-#endif
     t_static_for<G_BS>([&](auto pc) {
       constexpr int p = decltype(pc)::value;
       double dx[2], dy[2] = {0.0, 0.0};
-      if constexpr (ADIR) {
-        // AD[p][*] were requested behind step p's last MFMAs ONE BLOCK AGO.  Vector-memory operations complete in order; issued
-        // behind AD[p][3] since then: the twelve count loads of the three other steps, and on a loader wave a block's DMA --
-        // R raw pieces at the block's top and the x pieces of steps 0 and 1 (two per slot): of those, four x pieces lie behind
-        // AD[0][3] / AD[1][3] and eight behind AD[2][3] / AD[3][3]
-        constexpr int R = WEIGHTED ? 2 : 1;
-        constexpr int NL = 12 + (p < 2 ? 4 : 8) + R;
-        // (no register operands on the waits: tied through the two branches they made the compiler copy the operands -- in one
-        // branch in FRONT of the wait; the scheduling barriers keep the step's MFMAs behind them instead)
-        G_PIN();
-        if (loader) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");
-        else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        G_PIN();
-      }
       t_static_for<NS>([&](auto fic) {
         constexpr int fi = decltype(fic)::value;
         constexpr bool last = fi == NS - 1;
         if constexpr (p == G_BS - 1 && last) {
           G_TICK(3);
-          if constexpr (ADIR) {
-            // the block's DMA (raw pieces at its top, the x pieces in the slots of steps 0 and 1) has landed when at most the
-            // seven count loads issued behind the last x piece are in flight: A[1] quarters 1..3 and A[2]; waves 4..7 issue no DMA
-            if (loader) asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          } else if constexpr (XDIR) {
+          if constexpr (XDIR) {
             // the block's DMA (raw pieces at its top, count pieces in the slots of steps 0 and 1) has landed when at most the x
             // loads issued behind the last count piece are in flight: X[2] and X[3] (all four when the pieces go out at the top);
             // waves 4..7 issue no DMA
@@ -708,9 +595,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
           } else {
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(XBLK ? 0 : 3 * NX) : "memory");
           }
-#ifndef TXM_G_NO_BARRIER  // (ablation build: no barrier)
           asm volatile("s_barrier" ::: "memory");  // the block's barrier
-#endif
           G_TICK(6);
         }
         auto ahead = [&]() {
@@ -750,13 +635,9 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
         // MFMAs back to back, and a wave that waits for the matrix pipe between two of its own MFMAs issues nothing else).
         auto mfma_q = [&](auto qc) {
           constexpr int q = decltype(qc)::value;
-          if constexpr (ADIR) t_mfma<true>(acc[fi][q], AD[p][q], Bv);
-          else t_mfma<true>(acc[fi][q], A[q], Bv);
+          t_mfma<true>(acc[fi][q], A[q], Bv);
           // quarter q's count operand of the NEXT step into the registers just used for the last time
-#ifndef TXM_G_NO_AREAD  // (ablation build)
-          if constexpr (last && ADIR) {  // step p of the NEXT block into the registers this block's step p has just finished with
-            g_load16(AD[p][q], nb_src + (size_t)p * G_KSTEP_BYTES + qoff[q], nb_l16);
-          } else if constexpr (last) {
+          if constexpr (last) {
             if constexpr (p == G_BS - 1) {  // the other ring buffer: the next block's step 0 (address formed here, not held)
               const uint32_t a_vn = (uint32_t)(OFF_A + ((B + 1) & 1) * (G_BS * A_STEP)) + g_lane_now() * 16u;
               A[q] = *(lds_cv4)(lds + a_vn + q * 1024);
@@ -764,7 +645,6 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
               A[q] = *(lds_cv4)(lds + a_va + (p + 1) * A_STEP + q * 1024);
             }
           }
-#endif
         };
         G_PIN();
         t_static_for<(0 + 1) * NQ / 4 - 0 * NQ / 4>([&](auto jc) { mfma_q(std::integral_constant<int, 0 * NQ / 4 + decltype(jc)::value>{}); });
@@ -814,30 +694,21 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
         uint32_t lo[2], hi[2];
 #pragma unroll
         for (int uu = 0; uu < 2; ++uu) {
-#ifdef TXM_G_NO_SLICE  // (ablation build: constants are stored)
-          lo[uu] = 0x01020304u + uu;
-          hi[uu] = 0x04030201u + uu;
-          asm volatile("" : "+v"(lo[uu]), "+v"(hi[uu]));
-#else
           const double dd = (YS && fi == JN) ? dy[uu] : dx[uu];
           const uint64_t bits = (uint64_t)__double_as_longlong(fma(f[uu], dd, T_MAGIC));
           lo[uu] = (uint32_t)bits;
           hi[uu] = (uint32_t)(bits >> 32);
-#endif
         }
         G_PIN();
         t_static_for<(1 + 1) * NQ / 4 - 1 * NQ / 4>([&](auto jc) { mfma_q(std::integral_constant<int, 1 * NQ / 4 + decltype(jc)::value>{}); });
         G_PIN();
-#ifndef TXM_G_NO_SLICE
 #pragma unroll
         for (int uu = 0; uu < 2; ++uu) {
           lo[uu] ^= 0x80808080u;
           hi[uu] ^= 0x00008080u;
         }
-#endif
         G_PIN();
         // (b) the u-row overlay (wave-uniform branch, kept by the volatile permute), then the reads of the NEXT slot
-#if !defined(TXM_G_NO_OVERLAY) && !defined(TXM_G_NO_SLICE)
         if (fi < JN && ofi == fi) {
           uint32_t osel_l = osel, oxor_l = oxor;
           if constexpr (NQ == G_WIDE_Q) {
@@ -855,30 +726,21 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
             hi[uu] = (hi[uu] & 0x00ffffffu) | (dig ^ oxor_l);
           }
         }
-#endif
         G_PIN();
-#ifndef TXM_G_NO_AHEAD  // (ablation build: no factor / x / y reads)
         ahead();
-#endif
         G_PIN();
         t_static_for<(2 + 1) * NQ / 4 - 2 * NQ / 4>([&](auto jc) { mfma_q(std::integral_constant<int, 2 * NQ / 4 + decltype(jc)::value>{}); });
         G_PIN();
         // (c) the stores
-#ifndef TXM_G_NO_PRODUCE  // (ablation build: no stores)
         store_x2(lo[0], hi[0], lo[1], hi[1], fi * T_PB);
-#else
-        asm volatile("" ::"v"(lo[0]), "v"(hi[0]), "v"(lo[1]), "v"(hi[1]));
-#endif
         G_PIN();
         t_static_for<(3 + 1) * NQ / 4 - 3 * NQ / 4>([&](auto jc) { mfma_q(std::integral_constant<int, 3 * NQ / 4 + decltype(jc)::value>{}); });
         G_PIN();
         // (d) behind the stores, behind the MFMAs that read the old ones: the next step's B operand of the row set
-#ifndef TXM_G_NO_TRREAD  // (ablation build)
         if constexpr (!BT2) {  // one row set: the next step's operand, behind this step's stores
           Bt[0][0] = T_TRREAD((lds_v2i)(lds + rd_off));
           Bt[0][1] = T_TRREAD((lds_v2i)(lds + rd_off + 128));
         }
-#endif
         G_PIN();
       });
       if constexpr (!XBLK) x_request((p + 1) & 3);  // chunk s + 5 (slot of chunk s + 1: x read a step ago, y in this one)
@@ -1026,7 +888,6 @@ template <int J0, int JN, bool WEIGHTED, bool YS>
 static int launch_pass_g(const I8Args &a, int K, const unsigned char *table, int64_t rep_begin, int n_grp, hipStream_t st) {
   constexpr int NS = JN + (YS ? 1 : 0);
   constexpr int NQ = G_QUARTERS<NS>;
-#ifndef TXM_G_AB_NO_SIX  // (A/B build: every workgroup at G_QUARTERS)
   if constexpr (NS == 2 && !YS) {
     // the quarters that hold replicates of the call (rows past nrep are not flushed; their quarters need no workgroup)
     const int64_t reps = a.nrep - rep_begin < (int64_t)n_grp * G_REPS ? a.nrep - rep_begin : (int64_t)n_grp * G_REPS;
@@ -1038,7 +899,6 @@ static int launch_pass_g(const I8Args &a, int K, const unsigned char *table, int
       return launch_quarters_g<J0, JN, WEIGHTED, YS, NQ>(a, K, table, rep_begin, n_grp, G_WIDE_Q * n6, n4, st);
     }
   }
-#endif
   return launch_quarters_g<J0, JN, WEIGHTED, YS, NQ>(a, K, table, rep_begin, n_grp, 0, (int)cdiv(4 * (int64_t)n_grp, NQ), st);
 }
 
@@ -1061,11 +921,7 @@ int launch_resample_i8g(const I8Args &a, int K, bool weighted, const unsigned ch
                         hipStream_t st) {
   const bool ys = a.y != nullptr;
   const int rows = K + (ys ? 1 : 0), np = (rows + 2) / 3;
-#ifdef TXM_G_EVEN_SPLIT  // (A/B build: sizes within one of each other, always)
-  const bool greedy = false;
-#else
   const bool greedy = !ys && rows > 3 && rows % 3 == 1;
-#endif
   int j0 = 0;
   for (int i = 0; i < np; ++i) {
     const int n = greedy ? (i < np - 1 ? 3 : 1) : rows / np + (i < rows % np ? 1 : 0);
@@ -1081,18 +937,8 @@ int launch_resample_i8g(const I8Args &a, int K, bool weighted, const unsigned ch
     } else rc = weighted ? launch_pass_g<J0_, JN_, true, false>(a, K, table, rep_begin, n_grp, st)                \
                        : launch_pass_g<J0_, JN_, false, false>(a, K, table, rep_begin, n_grp, st);              \
   }
-#ifdef TXM_G_ONLY03  // (ablation builds: one instance, seconds to compile)
-    if (j0 == 0 && jn == 3 && !y_here && !weighted) rc = launch_pass_g<0, 3, false, false>(a, K, table, rep_begin, n_grp, st);
-#elif defined(TXM_G_ONLY32)
-    if (j0 == 3 && jn == 2 && !y_here && !weighted) rc = launch_pass_g<3, 2, false, false>(a, K, table, rep_begin, n_grp, st);
-#elif defined(TXM_G_ONLY02)
-    if (j0 == 0 && jn == 2 && !y_here && !weighted) rc = launch_pass_g<0, 2, false, false>(a, K, table, rep_begin, n_grp, st);
-#elif defined(TXM_G_ONLY01)
-    if (j0 == 0 && jn == 1 && !y_here && !weighted) rc = launch_pass_g<0, 1, false, false>(a, K, table, rep_begin, n_grp, st);
-#else
     G_CASE(0, 1) G_CASE(0, 2) G_CASE(0, 3) G_CASE(2, 1) G_CASE(2, 2) G_CASE(3, 1) G_CASE(3, 2) G_CASE(3, 3)
     G_CASE(5, 1) G_CASE(5, 2) G_CASE(6, 1) G_CASE(6, 2)
-#endif
 #undef G_CASE
     if (rc != TXM_OK) {
       if (rc == TXM_ERR_INVALID) set_error("resample_i8g: no pass for powers %d..%d", j0, j0 + jn - 1);

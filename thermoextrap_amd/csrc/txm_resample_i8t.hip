@@ -43,32 +43,19 @@ namespace txm {
 // factors of its two samples (e and e + 16).  The second unit's lines sit 513 lines further on -- out of the reach of a
 // ds_read2_b64 pair and not a multiple of 64 lines (ds_read2st64_b64 would pair them again): two ds_read_b64 (2 LDS
 // cycles each) instead of one paired read (8).  Same-box A/B, round 4: 36.4 -> 35.8 ms at N = 2e7, 165.8 -> 163.2 ms at
-// the north star (-1.6 %); TXM_T_PAIRREAD restores the adjacent layout.
+// the north star (-1.6 %) against the adjacent layout.
 // (PU = the unit stride in lines: 513, or 545 / 577 where a tile stages 33 / 35 chunks -- chunk groups, see the kernel)
-#ifndef TXM_T_PAIRREAD
 #define T_PIDX(e) (((((e) >> 4) & 1) * T_PUNIT) + (((e) >> 5) * 16) + ((e) & 15))
 #define T_PUNIT_OF(cg) ((cg) > 2 ? 577 : (cg) > 1 ? 545 : 513)
 #define T_PLINES_OF(cg) (T_PUNIT_OF(cg) + (31 + (cg)) * 16)
-#else
-#define T_PIDX(e) (e)
-#define T_PUNIT_OF(cg) 16
-#define T_PLINES_OF(cg) (SM_T + 32 * ((cg) - 1))
-#endif
 // chunk groups of a launch: 2 for one-quad states, for two-quad states with at most six powers and for four-quad states with at
 // most four (see the kernel; beyond that the row sets of a wave and the staged tiles of 33 chunks do not fit the LDS -- with four
 // quads a wave of a group holds every power of its quad), else 1.  One-quad states with at most four powers (orders 1-3; BASELINE
 // config 5's states): FOUR groups of two waves (round 6) -- a wave then holds two row sets and walks 8 k-steps per tile instead of
 // one row set over 16: the same work per wave in half as many latency chains, each with two independent row sets in flight
 // (five and more powers need four u-row waves per group, and from seven on the staged tiles do not fit next to the regions)
-#ifndef TXM_T_CG1
-#define TXM_T_CG1 4
-#endif
-#ifdef TXM_T_FLUSH_SERIAL  // (A/B build: the chunk groups' first flush, see the end of the window loop)
-constexpr bool T_FLUSH_SERIAL = true;
-#else
-constexpr bool T_FLUSH_SERIAL = false;
-#endif
-#define T_CG_OF(nq, jn) (((nq) == 1 && (jn) <= 4) ? TXM_T_CG1 : ((nq) == 1 || ((nq) == 2 && (jn) <= 6) || ((nq) == 4 && (jn) <= 4)) ? 2 : 1)
+constexpr int T_CG1 = 4;
+#define T_CG_OF(nq, jn) (((nq) == 1 && (jn) <= 4) ? T_CG1 : ((nq) == 1 || ((nq) == 2 && (jn) <= 6) || ((nq) == 4 && (jn) <= 4)) ? 2 : 1)
 
 // K = order + 1 is a run-time argument (it only enters the flush addresses); one launch slices the JN powers
 // J0 .. J0 + JN - 1.
@@ -251,9 +238,6 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
     auto store_x2 = [&](uint64_t bits0, uint64_t bits1, int off) {
       const uint32_t lo0 = (uint32_t)bits0 ^ 0x80808080u, hi0 = (uint32_t)(bits0 >> 32) ^ 0x00008080u;
       const uint32_t lo1 = (uint32_t)bits1 ^ 0x80808080u, hi1 = (uint32_t)(bits1 >> 32) ^ 0x00008080u;
-#ifdef TXM_T_NO_WRITE  // ablation build: the values stay live, nothing is stored
-      asm volatile("" ::"v"(lo0), "v"(hi0), "v"(lo1), "v"(hi1));
-#else
       // (s_nop: one wait state between an SALU write of M0 and an add-TID LDS instruction.  M0 as a tracked "{m0}" operand,
       // set once per window, saves the twelve scalar instructions per k-step and buys nothing: 37.2 vs 36.9 ms, same box --
       // the scalar unit is not what the k-steps wait for)
@@ -266,7 +250,6 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
                    : "v"(lo0), "v"(hi0), "v"(lo1), "v"(hi1), "s"(wreg), "n"(off), "n"(off + T_PLANE + 128), "n"(off + 256),
                      "n"(off + 256 + T_PLANE + 128)
                    : "memory", "m0");  // (M0 is written: the compiler must not keep a value of its own there)
-#endif
     };
 
     // ---- one k-step of a wave: chunk s of the tile on the matrix pipe, the X words of chunk s + 1 sliced in between.
@@ -274,11 +257,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
     // chunk -- du / w of this lane's two samples come in d_du / d_w)
     auto kstep = [&](auto produce_c, auto consume_c, int s, const XIn &R, int e0, const double (&d_du)[2],
                      const double (&d_w)[2]) {
-#ifdef TXM_T_NO_PRODUCE  // ablation build
-      constexpr bool produce = false;
-#else
       constexpr bool produce = decltype(produce_c)::value;
-#endif
       constexpr bool consume = decltype(consume_c)::value;
       v4i A0 = (v4i)(0), A1 = (v4i)(0);
       v2i Ba = (v2i)(0), Bb = (v2i)(0);
@@ -431,11 +410,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
       }
       dsc *= (double)((int64_t)1 << (8 * (tdg < I8_NSL ? tdg : 0)));
       const int bias = tdg == I8_NSL - 1 ? T_D6_BIAS : 0;
-#ifdef TXM_T_NO_FLUSH_STORE  // (ablation build: one row of a tile is written)
-      if (valid && tdg == 0) {
-#else
       if (valid) {
-#endif
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int m = (r >> 2) * 8 + (r & 3);
@@ -459,17 +434,12 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
     int64_t xq_step = 0, yq_step = 0;
     const int64_t xq_u1 = 16 * a.ldx_s * 8, yq_u1 = YS ? 16 * a.ldy_s * 8 : 0;  // second 16-sample unit of a chunk
     auto load_q = [&](XIn &r) {
-#ifdef TXM_T_NO_LOAD
-      r.x[0] = px + 1e-3; r.x[1] = px - 1e-3;
-      if constexpr (YS) { r.y[0] = py + 1e-3; r.y[1] = py - 1e-3; }
-#else
       r.x[0] = *reinterpret_cast<const double *>(xq + xo);
       r.x[1] = *reinterpret_cast<const double *>(xq + xq_u1 + xo);
       if constexpr (YS) {
         r.y[0] = *reinterpret_cast<const double *>(yq + yo);
         r.y[1] = *reinterpret_cast<const double *>(yq + yq_u1 + yo);
       }
-#endif
     };
     auto set_q = [&](int64_t i0) {  // the running pointers at sample i0 (a chunk's first)
       xq = reinterpret_cast<const char *>(a.x + i0 * a.ldx_s + a.col0);
@@ -547,9 +517,6 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
       {
         uint32_t n = cnt_cur[lane];
         if (wave == 0) fdraws += n;
-#ifdef TXM_T_NO_FILL  // ablation build
-        if (tsize == 0u) {
-#else
         // live replicates of this group (re-derived per tile: two scalar registers fewer across the k-steps); <= 32 -- a short
         // last group -- and the fill packs several calls of a replicate into one wave instruction
         // (narrow-state instances only: in the wide ones the extra code costs the register allocator 6 more spilled
@@ -575,7 +542,6 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
           for (uint32_t c0 = (uint32_t)wave * (uint32_t)fill_pack; c0 * 12u < nmx; c0 += (uint32_t)(T_WAVES * fill_pack))
             t_fill_call<false>(cntw, a.k0, a.k1, rsp, (uint32_t)t, c0 + (uint32_t)slot, np, (uint32_t)rp * 4u);
         } else if (tsize == (uint32_t)SM_T) {
-#endif
           // dead lanes (replicates past nrep) draw like the smallest live lane: their columns are never flushed
           uint32_t nmin = rep_live ? n : 0xffffffffu, nmax = rep_live ? n : 0u;
 #pragma unroll
@@ -734,7 +700,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
       }
     };
-    if constexpr (CG > 1 && !T_FLUSH_SERIAL) {
+    if constexpr (CG > 1) {
       // chunk groups: the groups' int32 accumulators are added up in the (now idle) count tile -- group 0 stores its tiles, the
       // others add theirs with LDS atomics (exact, whatever the order: what is flushed is what one group contracting all 32 chunks
       // would have flushed) -- and the CG waves that share a role (wave % WPG: same quad, same powers, same u-row half) then SPLIT
@@ -792,43 +758,10 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
       for (int fi = 0; fi < NS; ++fi) acc[fi][0] = acc[fi][1] = (v16i)(0);
     } else {
-      if constexpr (CG > 1) {
-        // (A/B build -DTXM_T_FLUSH_SERIAL: the first cut -- group after group into group 0's registers, which flushes alone)
-        constexpr int NT = 2 * NS + 1;
-        uint32_t *xch = cntw + (size_t)((wave % WPG) * 4) * 16 * 64 + lane;
-        auto tile_of = [&](int tt) -> v16i & { return tt < 2 * NS ? acc[tt >> 1][tt & 1] : accu; };
-#pragma unroll 1
-        for (int src = 1; src < CG; ++src) {  // group src -> group 0, wave for wave (same quad, same powers)
-#pragma unroll
-          for (int t0 = 0; t0 < NT; t0 += 4) {
-            if (cgrp == src) {
-#pragma unroll
-              for (int k = 0; k < 4; ++k)
-                if (t0 + k < NT) {
-                  v16i &T = tile_of(t0 + k);
-#pragma unroll
-                  for (int r = 0; r < 16; ++r) xch[(k * 16 + r) * 64] = (uint32_t)T[r];
-                  T = (v16i)(0);
-                }
-            }
-            __syncthreads();
-            if (cgrp == 0) {
-#pragma unroll
-              for (int k = 0; k < 4; ++k)
-                if (t0 + k < NT) {
-                  v16i &T = tile_of(t0 + k);
-#pragma unroll
-                  for (int r = 0; r < 16; ++r) T[r] += (int)xch[(k * 16 + r) * 64];
-                }
-            }
-            if (t0 + 4 < NT || src + 1 < CG) __syncthreads();  // (the next round overwrites the slots)
-          }
-        }
-      }
       // instances without chunk groups: every wave writes its own tiles out -- digit-summed as above, a tile at a time through a
       // wave-private scratch in the idle count tile (narrow instances always; the wide instance unless the CALL carries a second
       // matrix, whose finalize reads per-digit u slots: YS launches, and PD = the first pass of such a call)
-      constexpr bool summed1 = CG == 1 && !T_FLUSH_SERIAL && (NQ < 8 || (!YS && !PD));
+      constexpr bool summed1 = NQ < 8 || (!YS && !PD);
       if constexpr (summed1) {
         uint32_t *xw = cntw + (size_t)wave * XT;
         auto via_lds = [&](v16i &T, int h, int rs, int ufrag) {
@@ -843,7 +776,7 @@ __global__ __launch_bounds__(T_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
           via_lds(acc[fi][1], 1 - hswap, fi, -1);
         }
         if (has_ut) via_lds(accu, uh, 0, fu);  // wave-uniform
-      } else if (CG == 1 || cgrp == 0) {  // wave-uniform
+      } else {
 #pragma unroll
         for (int fi = 0; fi < NS; ++fi) {
           flush_tile(acc[fi][0], hswap, fi, -1);
@@ -922,14 +855,14 @@ int i8_cpad(int64_t C_call, int K) {
 }
 
 // Which layout the launches of launch_resample_i8t leave in I8Args::part_x / part_u for a NARROW shape: every narrow instance adds
-// the digit sums up in its flush and stores [window][replicate][power][column] (u-row: [window][replicate][power]) -- the per-digit
-// slots [...][power][8 digit slots][column] only in the A/B build of the serial flush.  The wide instance does what
+// the digit sums up in its flush and stores [window][replicate][power][column] (u-row: [window][replicate][power]) -- never the
+// per-digit slots [...][power][8 digit slots][column].  The wide instance does what
 // I8Args::part_summed says (0 when the call carries a second matrix).  The finalize is told which (its `summed` argument).
 bool i8t_partials_summed(int64_t C_call, int K) {
-  return i8t_narrow_nq(C_call, K) != 0 && !T_FLUSH_SERIAL;   // (wide states: i8t_wide_summed)
+  return i8t_narrow_nq(C_call, K) != 0;   // (wide states: i8t_wide_summed)
 }
 // ... and the wide instance: digit-summed slots unless the CALL carries a second matrix (whose finalize reads per-digit u slots)
-bool i8t_wide_summed(bool call_carries_y) { return !call_carries_y && !T_FLUSH_SERIAL; }
+bool i8t_wide_summed(bool call_carries_y) { return !call_carries_y; }
 
 template <int NQ>
 static int launch_narrow_t(const I8Args &a, int K, bool weighted, size_t prog_bytes, hipStream_t st) {

@@ -1,6 +1,6 @@
 """Phase timing of the transposing-read int8 kernel (diagnostic build: -DTXM_I8T_TIMING; GPU box):
 TXM_LIBRARY=tools/build/libtxmom_timing.so python tools/i8t_timing.py [N] [order] [nrep]"""
-import os, sys
+import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
@@ -23,7 +23,7 @@ with eng.forced_path("int8"):
 print(f"call {e0.elapsed_time(e1):.3f} ms", eng.resample_info())
 ntiles = -(-N // 1024)
 win = 256
-WMIN = int(os.environ.get("TXM_WIN_MIN", 256))  # the variant's -DTXM_WIN_MIN
+WMIN = 256  # WIN_MIN of plan_i8 (txm_resample.hip)
 while win > 4 and ntiles < WMIN * win: win //= 4
 nwin = -(-ntiles // win)
 g0 = -(-(1 + C) * 8 // 256) * 256
