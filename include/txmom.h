@@ -638,6 +638,35 @@ int txm_influence_cov(const double *x, int64_t ldx_s, int64_t ldx_c, const doubl
                       int64_t C, int n_f, int n_q, double center_u, const double *center_x, const double *a,
                       const double *b, double *cov, double *mean, void *ws, size_t ws_bytes, txm_stream stream);
 
+/* ---- (f-10) the same for S independent states in one set of launches ------------------------------------------- */
+/* S states of C columns each, x row-major with ONE pitch ldx_s (ldx_c == 1) and a sample count PER STATE -- decorrelated
+ * time series have different lengths.  `states_host` is a HOST array of S records (w NULL for all states or for none);
+ * it is copied into the workspace by the call (not stream-capturable).  center_u [S], center_x [S][C], a and b
+ * [S][C][n_f][n_q], cov [S][C][n_f][n_f] and mean [S][C][n_f] are device arrays.  Two launches for all states: the
+ * state rides a grid axis of the sample kernel and of the finalize kernel.
+ * BITS: state s is computed under the plan txm_influence_cov makes for n_s alone -- its own number of workgroups, row
+ * stride and fixed-order sum of the partials inside a launch as wide as the widest state (workgroups a state does not
+ * use leave at once).  The batch reads two columns per lane only if EVERY state qualifies (C even, ldx_s even, x
+ * 16-byte aligned, n_q <= 6), one column per lane otherwise; C == 1 with ldx_s == 1 takes the series kernel, as the
+ * single call does.  State s of the batch therefore equals txm_influence_cov(x_s, ldx_s, 1, u_s, w_s, n_s, ...) BIT FOR
+ * BIT whenever that call picks the instantiation the batch picked -- always, unless the states' x pointers differ in
+ * 16-byte alignment while C and ldx_s are even and n_q <= 6 (then the aligned states' single calls read two columns
+ * per lane and the batch one: same sums, another order).
+ * Zero-weight rows are skipped; a state of total weight zero gives zeros for that state only; no floating-point
+ * atomics, two calls give the same bits, cov is bitwise symmetric.  S <= 65535, C <= 65535, n >= 1 per state,
+ * ldx_s >= C; null pointers, mixed NULL / non-NULL w and a short workspace are refused before anything is enqueued.
+ * txm_influence_cov_batched_ws_bytes(S, n_max, C, n_q), n_max = max_s n_s, is host logic: 0 for bad arguments. */
+typedef struct txm_inf_state {
+  const double *x; /* [n][ldx_s] */
+  const double *u; /* [n] */
+  const double *w; /* [n] or NULL (for all states or for none) */
+  int64_t n;       /* >= 1, may differ from state to state */
+} txm_inf_state;
+size_t txm_influence_cov_batched_ws_bytes(int64_t S, int64_t n_max, int64_t C, int n_q);
+int txm_influence_cov_batched(const txm_inf_state *states_host, int64_t S, int64_t ldx_s, int64_t C, int n_f, int n_q,
+                              const double *center_u, const double *center_x, const double *a, const double *b,
+                              double *cov, double *mean, void *ws, size_t ws_bytes, txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

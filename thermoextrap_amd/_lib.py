@@ -35,6 +35,12 @@ class StatePtrs(ct.Structure):
     _fields_ = [("x", c_void_p), ("u", c_void_p), ("w", c_void_p)]
 
 
+class InfState(ct.Structure):
+    """txm_inf_state (include/txmom.h): one state's samples for txm_influence_cov_batched."""
+
+    _fields_ = [("x", c_void_p), ("u", c_void_p), ("w", c_void_p), ("n", c_i64)]
+
+
 class MbarState(ct.Structure):
     """txm_mbar_state (include/txmom.h): one state's samples for the MBAR entry points."""
 
@@ -155,6 +161,9 @@ SIGNATURES = {
     "txm_influence_cov_ws_bytes": (c_size, [c_i64, c_i64, c_int]),
     "txm_influence_cov": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, ct.c_double, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_influence_cov_batched_ws_bytes": (c_size, [c_i64, c_i64, c_i64, c_int]),
+    "txm_influence_cov_batched": (c_int, [ct.POINTER(InfState), c_i64, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
 }
 
 ABI_VERSION = 2  # include/txmom.h TXM_ABI_VERSION

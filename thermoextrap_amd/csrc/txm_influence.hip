@@ -20,6 +20,13 @@
 //   influence_colmajor_kernel : every series contiguous along the samples; lanes <-> samples, blockIdx.y = series.
 //   influence_finalize_kernel : block per column: fixed-order sum of the partials, then the contraction above.
 // A row of weight zero is skipped (selected out, not multiplied by zero): it may hold anything.
+//
+// txm_influence_cov_batched runs the same three bodies for S states in ONE launch each, the state on a grid
+// axis (influence_*_batch_kernel).  Every state keeps the plan of its own n -- grid_x_s workgroups, row stride
+// grid_x_s * ROWS, partials added over grid_x_s records -- inside a launch as wide as the widest state; the workgroups a
+// state does not use leave at once.  So state s gets the bits of the single call on state s.
+#include <vector>
+
 #include "txm_common.h"
 
 namespace txm {
@@ -73,10 +80,12 @@ __device__ __forceinline__ void inf_body(double ui, double wi, const double (&xv
 // Thread layout of txm_reduce.hip's row-major kernel: lane_in_row = tid & (LPR - 1) owns columns col0 + {0 .. VEC-1},
 // row_in_blk = tid >> lpr_log2; blockIdx.y selects a chunk of LPR * VEC columns; rows are grid-strided, UNR loads in flight.
 // partial: [blockIdx.y][blockIdx.x][LPR * VEC columns][NS]
+// grid_x: the workgroups along x that work on THIS state (gridDim.x of the single call; the state's own plan in a batch,
+// whose launch is as wide as its widest state) -- the row stride and the partials' layout follow it, not the launch.
 template <int NQ, int VEC, bool WEIGHTED>
-__global__ __launch_bounds__(INF_BLOCK) void influence_rowmajor_kernel(
+__device__ __forceinline__ void influence_rowmajor_body(
     const double *__restrict__ x, int64_t ldx_s, const double *__restrict__ u, const double *__restrict__ w, int64_t N,
-    int64_t C, double cu, const double *__restrict__ cx, int lpr_log2, double *__restrict__ partial) {
+    int64_t C, double cu, const double *__restrict__ cx, int lpr_log2, int grid_x, double *__restrict__ partial) {
   using LY = inf_layout<NQ>;
   constexpr int SH = LY::SH, PC = LY::PC, NS = LY::NS, NV = SH + VEC * PC, UNR = 4;
   const int LPR = 1 << lpr_log2, ROWS = INF_BLOCK >> lpr_log2;
@@ -107,7 +116,7 @@ __global__ __launch_bounds__(INF_BLOCK) void influence_rowmajor_kernel(
   };
 
   if (col_ok) {
-    const int64_t stride = (int64_t)gridDim.x * ROWS;
+    const int64_t stride = (int64_t)grid_x * ROWS;
     int64_t i = (int64_t)blockIdx.x * ROWS + rib;
     for (; i + (UNR - 1) * stride < N; i += UNR * stride) {
       double xv[UNR][VEC], ui[UNR], wi[UNR];
@@ -130,7 +139,7 @@ __global__ __launch_bounds__(INF_BLOCK) void influence_rowmajor_kernel(
 
   // fixed-order sum over the ROWS row slots that share a lane_in_row, INF_CH of the lane's NV values per pass
   __shared__ double lds[INF_CH][INF_BLOCK];
-  double *dst = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * ((size_t)LPR * VEC) * NS;
+  double *dst = partial + ((size_t)blockIdx.y * grid_x + blockIdx.x) * ((size_t)LPR * VEC) * NS;
 #pragma unroll
   for (int c0 = 0; c0 < NV; c0 += INF_CH) {
 #pragma unroll
@@ -160,6 +169,31 @@ __global__ __launch_bounds__(INF_BLOCK) void influence_rowmajor_kernel(
   }
 }
 
+// One state of a batched call as the kernels read it (built on the host from txm_inf_state and the state's own plan).
+struct inf_dev_state {
+  const double *x, *u, *w;
+  int64_t n;
+  int64_t grid_x;
+};
+
+template <int NQ, int VEC, bool WEIGHTED>
+__global__ __launch_bounds__(INF_BLOCK) void influence_rowmajor_kernel(
+    const double *__restrict__ x, int64_t ldx_s, const double *__restrict__ u, const double *__restrict__ w, int64_t N,
+    int64_t C, double cu, const double *__restrict__ cx, int lpr_log2, double *__restrict__ partial) {
+  influence_rowmajor_body<NQ, VEC, WEIGHTED>(x, ldx_s, u, w, N, C, cu, cx, lpr_log2, (int)gridDim.x, partial);
+}
+
+// blockIdx.z = state; a workgroup beyond the state's own grid leaves at once.  partial: [state][per_state doubles]
+template <int NQ, int VEC, bool WEIGHTED>
+__global__ __launch_bounds__(INF_BLOCK) void influence_rowmajor_batch_kernel(
+    const inf_dev_state *__restrict__ tab, int64_t ldx_s, int64_t C, const double *__restrict__ cu,
+    const double *__restrict__ cx, int lpr_log2, double *__restrict__ partial, size_t per_state) {
+  const inf_dev_state s = tab[blockIdx.z];
+  if ((int64_t)blockIdx.x >= s.grid_x) return;
+  influence_rowmajor_body<NQ, VEC, WEIGHTED>(s.x, ldx_s, s.u, s.w, s.n, C, cu[blockIdx.z], cx + (size_t)blockIdx.z * C,
+                                             lpr_log2, (int)s.grid_x, partial + (size_t)blockIdx.z * per_state);
+}
+
 // sum of lds[k][0 .. 255] for k < INF_CH in a fixed order: thread (k = tid >> 5, j = tid & 31) adds its eight strided
 // entries, then the 32 lanes fold downwards; valid in the threads with (tid & 31) == 0
 __device__ __forceinline__ double inf_block_sum(const double (*lds)[INF_BLOCK], int tid) {
@@ -172,23 +206,22 @@ __device__ __forceinline__ double inf_block_sum(const double (*lds)[INF_BLOCK], 
   return acc;
 }
 
-// partial: [series][gridDim.x][NS]
+// one series xs[0 .. N) over grid_x workgroups (see influence_rowmajor_body); dst: this workgroup's record [NS]
 template <int NQ, bool WEIGHTED>
-__global__ __launch_bounds__(INF_BLOCK) void influence_colmajor_kernel(
-    const double *__restrict__ x, int64_t ld_series, const double *__restrict__ u, const double *__restrict__ w, int64_t N,
-    double cu, const double *__restrict__ cx, double *__restrict__ partial) {
+__device__ __forceinline__ void influence_series_body(const double *__restrict__ xs, const double *__restrict__ u,
+                                                      const double *__restrict__ w, int64_t N, double cu, double cxs,
+                                                      int grid_x, double *__restrict__ dst) {
   using LY = inf_layout<NQ>;
   constexpr int SH = LY::SH, PC = LY::PC, NS = LY::NS;
-  const int s = blockIdx.y, tid = threadIdx.x;
-  const double *xs = x + (int64_t)s * ld_series;
-  const double px[1] = {cx[s]};
+  const int tid = threadIdx.x;
+  const double px[1] = {cxs};
   double sh[SH], pc[1][PC];
 #pragma unroll
   for (int q = 0; q < SH; ++q) sh[q] = 0.0;
 #pragma unroll
   for (int q = 0; q < PC; ++q) pc[0][q] = 0.0;
 
-  const int64_t nthreads = (int64_t)gridDim.x * INF_BLOCK;
+  const int64_t nthreads = (int64_t)grid_x * INF_BLOCK;
   constexpr int UNR = 4;
   int64_t i = (int64_t)blockIdx.x * INF_BLOCK + tid;
   for (; i + (UNR - 1) * nthreads < N; i += UNR * nthreads) {
@@ -209,7 +242,6 @@ __global__ __launch_bounds__(INF_BLOCK) void influence_colmajor_kernel(
   }
 
   __shared__ double lds[INF_CH][INF_BLOCK];
-  double *dst = partial + ((size_t)s * gridDim.x + blockIdx.x) * NS;
 #pragma unroll
   for (int c0 = 0; c0 < NS; c0 += INF_CH) {
 #pragma unroll
@@ -227,12 +259,33 @@ __global__ __launch_bounds__(INF_BLOCK) void influence_colmajor_kernel(
   }
 }
 
+// partial: [series][gridDim.x][NS]
+template <int NQ, bool WEIGHTED>
+__global__ __launch_bounds__(INF_BLOCK) void influence_colmajor_kernel(
+    const double *__restrict__ x, int64_t ld_series, const double *__restrict__ u, const double *__restrict__ w, int64_t N,
+    double cu, const double *__restrict__ cx, double *__restrict__ partial) {
+  const int s = blockIdx.y;
+  influence_series_body<NQ, WEIGHTED>(x + (int64_t)s * ld_series, u, w, N, cu, cx[s], (int)gridDim.x,
+                                      partial + ((size_t)s * gridDim.x + blockIdx.x) * inf_layout<NQ>::NS);
+}
+
+// states of ONE contiguous series each (C == 1, pitch 1): blockIdx.y = state
+template <int NQ, bool WEIGHTED>
+__global__ __launch_bounds__(INF_BLOCK) void influence_series_batch_kernel(
+    const inf_dev_state *__restrict__ tab, const double *__restrict__ cu, const double *__restrict__ cx,
+    double *__restrict__ partial, size_t per_state) {
+  const inf_dev_state s = tab[blockIdx.y];
+  if ((int64_t)blockIdx.x >= s.grid_x) return;
+  influence_series_body<NQ, WEIGHTED>(s.x, s.u, s.w, s.n, cu[blockIdx.y], cx[blockIdx.y], (int)s.grid_x,
+                                      partial + (size_t)blockIdx.y * per_state + (size_t)blockIdx.x * inf_layout<NQ>::NS);
+}
+
 // block per column: sums[NS] = the column's records added over the nblk workgroups in a fixed order, then
 // cov[c][i][j], mean[c][k] from the coefficients.  Total weight zero: zeros.
 template <int NQ>
-__global__ __launch_bounds__(INF_BLOCK) void influence_finalize_kernel(
-    const double *__restrict__ partial, int nblk, int cols_per_chunk, int n_f, const double *__restrict__ a,
-    const double *__restrict__ b, double *__restrict__ cov, double *__restrict__ mean) {
+__device__ __forceinline__ void influence_finalize_body(const double *__restrict__ partial, int nblk, int cols_per_chunk,
+                                                        int n_f, const double *__restrict__ a, const double *__restrict__ b,
+                                                        double *__restrict__ cov, double *__restrict__ mean) {
   using LY = inf_layout<NQ>;
   constexpr int NT = LY::NT, NS = LY::NS;
   const int64_t c = blockIdx.x;
@@ -281,6 +334,24 @@ __global__ __launch_bounds__(INF_BLOCK) void influence_finalize_kernel(
   }
 }
 
+template <int NQ>
+__global__ __launch_bounds__(INF_BLOCK) void influence_finalize_kernel(
+    const double *__restrict__ partial, int nblk, int cols_per_chunk, int n_f, const double *__restrict__ a,
+    const double *__restrict__ b, double *__restrict__ cov, double *__restrict__ mean) {
+  influence_finalize_body<NQ>(partial, nblk, cols_per_chunk, n_f, a, b, cov, mean);
+}
+
+// blockIdx.y = state: its partials over its own grid_x workgroups, its slices of a, b, cov, mean
+template <int NQ>
+__global__ __launch_bounds__(INF_BLOCK) void influence_finalize_batch_kernel(
+    const inf_dev_state *__restrict__ tab, const double *__restrict__ partial, size_t per_state, int cols_per_chunk,
+    int64_t C, int n_f, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ cov,
+    double *__restrict__ mean) {
+  const size_t s = blockIdx.y, sc = s * (size_t)C;
+  influence_finalize_body<NQ>(partial + s * per_state, (int)tab[s].grid_x, cols_per_chunk, n_f, a + sc * n_f * NQ,
+                              b + sc * n_f * NQ, cov + sc * n_f * n_f, mean + sc * n_f);
+}
+
 // ---------------------------------------------------------------------------
 // host side
 
@@ -292,13 +363,16 @@ struct InfPlan {
 
 // One workgroup's share is 4 row slots: 4 * (256 >> lpr_log2) rows (row-major), 4 * 256 samples (series layout); the grid
 // grows by a workgroup per share up to 8 per CU and strides the rest.
-static InfPlan influence_plan(const double *x, int64_t ldx_s, int64_t ldx_c, int64_t N, int64_t C, int n_q) {
+// two columns per lane (16-byte loads) while the sums of both columns fit the register file at two waves per SIMD
+static bool influence_vec2_ok(const double *x, int64_t ldx_s, int64_t C, int n_q) {
+  return (C % 2 == 0) && (ldx_s % 2 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && n_q <= INF_VEC2_MAXQ;
+}
+
+static InfPlan influence_plan_vec(bool vec2, int64_t ldx_s, int64_t ldx_c, int64_t N, int64_t C) {
   InfPlan p{};
   const int64_t cap = (int64_t)num_cus() * 8;
   p.rowmajor = ldx_c == 1 && !(C == 1 && ldx_s == 1);
   if (p.rowmajor) {
-    // two columns per lane (16-byte loads) while the sums of both columns fit the register file at two waves per SIMD
-    const bool vec2 = (C % 2 == 0) && (ldx_s % 2 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && n_q <= INF_VEC2_MAXQ;
     p.vec = vec2 ? 2 : 1;
     const int64_t lanes = cdiv(C, p.vec);
     int l2 = 0;
@@ -320,6 +394,10 @@ static InfPlan influence_plan(const double *x, int64_t ldx_s, int64_t ldx_c, int
   }
   if (p.grid_x < 1) p.grid_x = 1;
   return p;
+}
+
+static InfPlan influence_plan(const double *x, int64_t ldx_s, int64_t ldx_c, int64_t N, int64_t C, int n_q) {
+  return influence_plan_vec(influence_vec2_ok(x, ldx_s, C, n_q), ldx_s, ldx_c, N, C);
 }
 
 static size_t influence_ws_bytes_impl(int64_t C, int n_q) {
@@ -369,6 +447,53 @@ static int influence_launch(const InfPlan &p, const double *x, int64_t ldx_s, co
   return TXM_OK;
 }
 
+// p: the plan of the batch's WIDEST state (its grid_x is the launch's); every state's own grid_x sits in tab
+template <int NQ>
+static int influence_launch_batched(const InfPlan &p, const inf_dev_state *tab, int64_t S, bool weighted, int64_t ldx_s,
+                                    int64_t C, int n_f, const double *cu, const double *cx, const double *a, const double *b,
+                                    double *cov, double *mean, double *partial, size_t per_state, hipStream_t st) {
+  const dim3 block(INF_BLOCK);
+  if (p.rowmajor) {
+    const dim3 grid(p.grid_x, p.chunks, (unsigned)S);
+#define TXM_INF_RMB(VEC, WT)                                                                                               \
+  hipLaunchKernelGGL((influence_rowmajor_batch_kernel<NQ, VEC, WT>), grid, block, 0, st, tab, ldx_s, C, cu, cx, p.lpr_log2, \
+                     partial, per_state)
+    if (p.vec == 2) {
+      if constexpr (NQ <= INF_VEC2_MAXQ) {
+        if (weighted) TXM_INF_RMB(2, true); else TXM_INF_RMB(2, false);
+      } else {
+        set_error("influence_cov_batched: no two-column kernel for n_q=%d", NQ);
+        return TXM_ERR_UNSUPPORTED;
+      }
+    } else {
+      if (weighted) TXM_INF_RMB(1, true); else TXM_INF_RMB(1, false);
+    }
+#undef TXM_INF_RMB
+  } else {
+    const dim3 grid(p.grid_x, (unsigned)S);
+    if (weighted)
+      hipLaunchKernelGGL((influence_series_batch_kernel<NQ, true>), grid, block, 0, st, tab, cu, cx, partial, per_state);
+    else
+      hipLaunchKernelGGL((influence_series_batch_kernel<NQ, false>), grid, block, 0, st, tab, cu, cx, partial, per_state);
+  }
+  TXM_LAUNCH_CHECK();
+  hipLaunchKernelGGL((influence_finalize_batch_kernel<NQ>), dim3((unsigned)C, (unsigned)S), block, 0, st, tab, partial,
+                     per_state, p.cols_per_chunk, C, n_f, a, b, cov, mean);
+  TXM_LAUNCH_CHECK();
+  return TXM_OK;
+}
+
+// doubles of partials one state of at most n_max samples can need under either column width: the one-column plan has
+// the smaller share (so the wider grid) and chunks * cols_per_chunk <= cols_pad for both (influence_ws_bytes_impl)
+static size_t influence_batched_state_doubles(int64_t n_max, int64_t C, int n_q) {
+  const size_t NS = (size_t)(3 * (2 * n_q - 1) + 2 * n_q);
+  int64_t cols_pad = 1;
+  while (cols_pad < C) cols_pad <<= 1;
+  if (cols_pad > 512) cols_pad = cdiv(C, 512) * 512;
+  const InfPlan p1 = influence_plan_vec(false, C, 1, n_max, C);
+  return (size_t)p1.grid_x * (size_t)cols_pad * NS;
+}
+
 }  // namespace txm
 
 using namespace txm;
@@ -405,5 +530,67 @@ extern "C" int txm_influence_cov(const double *x, int64_t ldx_s, int64_t ldx_c, 
 #undef TXM_INF_CASE
   }
   set_error("influence_cov: n_q out of range");
+  return TXM_ERR_INVALID;
+}
+
+extern "C" size_t txm_influence_cov_batched_ws_bytes(int64_t S, int64_t n_max, int64_t C, int n_q) {
+  if (S < 1 || S > 65535 || n_max < 1 || C < 1 || C > 65535 || n_q < 1 || n_q > TXM_MAXK) return 0;
+  return align_up((size_t)S * sizeof(inf_dev_state), 256) +
+         (size_t)S * influence_batched_state_doubles(n_max, C, n_q) * sizeof(double) + 256;
+}
+
+extern "C" int txm_influence_cov_batched(const txm_inf_state *states_host, int64_t S, int64_t ldx_s, int64_t C, int n_f,
+                                         int n_q, const double *center_u, const double *center_x, const double *a,
+                                         const double *b, double *cov, double *mean, void *ws, size_t ws_bytes,
+                                         txm_stream stream) {
+  TXM_REQUIRE(states_host && center_u && center_x && a && b && cov && mean && ws, "influence_cov_batched: null pointer");
+  TXM_REQUIRE(S >= 1 && S <= 65535, "influence_cov_batched: S=%lld outside [1, 65535]", (long long)S);
+  TXM_REQUIRE(C >= 1 && C <= 65535, "influence_cov_batched: C=%lld outside [1, 65535]", (long long)C);
+  TXM_REQUIRE(n_f >= 1 && n_f <= TXM_MAXK, "influence_cov_batched: n_f=%d outside [1, %d]", n_f, TXM_MAXK);
+  TXM_REQUIRE(n_q >= 1 && n_q <= TXM_MAXK, "influence_cov_batched: n_q=%d outside [1, %d]", n_q, TXM_MAXK);
+  TXM_REQUIRE(ldx_s >= C, "influence_cov_batched: row pitch ldx_s < C");
+  const bool weighted = states_host[0].w != nullptr;
+  bool vec2 = true;
+  int64_t n_max = 0;
+  for (int64_t s = 0; s < S; ++s) {
+    const txm_inf_state &h = states_host[s];
+    TXM_REQUIRE(h.x && h.u, "influence_cov_batched: state %lld has a null pointer", (long long)s);
+    TXM_REQUIRE((h.w != nullptr) == weighted, "influence_cov_batched: weights for all states or for none");
+    TXM_REQUIRE(h.n >= 1, "influence_cov_batched: state %lld has n=%lld < 1", (long long)s, (long long)h.n);
+    vec2 = vec2 && influence_vec2_ok(h.x, ldx_s, C, n_q);
+    if (h.n > n_max) n_max = h.n;
+  }
+  // every state under the plan the single call makes for its own n (with the batch's column width); the launch takes
+  // the widest state's grid
+  static thread_local std::vector<inf_dev_state> tab_host;
+  tab_host.resize((size_t)S);
+  InfPlan pmax{};
+  for (int64_t s = 0; s < S; ++s) {
+    const txm_inf_state &h = states_host[s];
+    const InfPlan p = influence_plan_vec(vec2, ldx_s, 1, h.n, C);
+    tab_host[(size_t)s] = inf_dev_state{h.x, h.u, h.w, h.n, (int64_t)p.grid_x};
+    if (s == 0 || p.grid_x > pmax.grid_x) pmax = p;
+  }
+  const size_t NS = (size_t)(3 * (2 * n_q - 1) + 2 * n_q);
+  const size_t per_state = (size_t)pmax.chunks * pmax.grid_x * pmax.cols_per_chunk * NS;
+  const size_t tab_bytes = align_up((size_t)S * sizeof(inf_dev_state), 256);
+  if (ws_bytes < txm_influence_cov_batched_ws_bytes(S, n_max, C, n_q) || ws_bytes < tab_bytes + (size_t)S * per_state * sizeof(double)) {
+    set_error("influence_cov_batched: workspace too small");
+    return TXM_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  inf_dev_state *tab = (inf_dev_state *)ws;
+  TXM_HIP(hipMemcpyAsync(tab, tab_host.data(), (size_t)S * sizeof(inf_dev_state), hipMemcpyHostToDevice, st));
+  double *partial = (double *)((char *)ws + tab_bytes);
+  switch (n_q) {
+#define TXM_INF_CASE(Q)                                                                                                  \
+  case Q:                                                                                                                \
+    return influence_launch_batched<Q>(pmax, tab, S, weighted, ldx_s, C, n_f, center_u, center_x, a, b, cov, mean, partial, \
+                                       per_state, st);
+    TXM_INF_CASE(1) TXM_INF_CASE(2) TXM_INF_CASE(3) TXM_INF_CASE(4) TXM_INF_CASE(5)
+    TXM_INF_CASE(6) TXM_INF_CASE(7) TXM_INF_CASE(8) TXM_INF_CASE(9)
+#undef TXM_INF_CASE
+  }
+  set_error("influence_cov_batched: n_q out of range");
   return TXM_ERR_INVALID;
 }

@@ -835,7 +835,69 @@ def influence_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: torch.Te
     return cov, mean
 
 
-TAYLOR_MODES = {"sum": 0, "cumsum": 1, "terms": 2}
+def influence_cov_batched(xs, us, a: torch.Tensor, b: torch.Tensor, center_u, center_x: torch.Tensor,
+                          ws=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``influence_cov`` of S independent states in ONE launch per kernel (txm_influence_cov_batched): state s of the
+    result is, bit for bit, ``influence_cov(xs[s], us[s], a[s], b[s], center_u[s], center_x[s], w=ws[s])``.
+    xs[s]: (n_s, C) or (n_s,), us[s] (and ws[s]): (n_s,) -- the sample count may differ from state to state; a, b:
+    (S, C, n_f, n_q); center_u: S host floats or an (S,) tensor; center_x: (S, C).
+    Returns ``(cov [S, C, n_f, n_f], mean [S, C, n_f])`` on the device.
+
+    The one launch needs every x row-major with one pitch (a single series each when C == 1) and all x alike in 16-byte
+    alignment; otherwise the single call would pick another kernel for some state, and this loops over ``influence_cov``
+    so that the promise above holds."""
+    L = _L()
+    S = len(xs)
+    if S < 1 or len(us) != S or (ws is not None and len(ws) != S):
+        raise ValueError("need the same number (>= 1) of x, u (and w) tensors")
+    if ws is not None and any(w is None for w in ws) and not all(w is None for w in ws):
+        raise ValueError("weights for all states or for none")
+    if ws is not None and ws[0] is None:
+        ws = None
+    ops = [_rowmajor_operands(xs[s], us[s], None if ws is None else ws[s]) for s in range(S)]
+    C = ops[0][6]
+    if any(o[6] != C for o in ops):
+        raise ValueError("every x must have the same number of columns")
+    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
+        _check_f64_cuda(t, name)
+    if a.dim() != 4 or tuple(a.shape[:2]) != (S, C) or b.shape != a.shape:
+        raise ValueError(f"a and b must both have shape ({S}, {C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
+    if tuple(center_x.shape) != (S, C):
+        raise ValueError(f"center_x must have shape ({S}, {C}), got {tuple(center_x.shape)}")
+    cu_dev = center_u.contiguous() if isinstance(center_u, torch.Tensor) else to_device(np.asarray(center_u, dtype=np.float64))
+    _check_f64_cuda(cu_dev, "center_u")
+    if tuple(cu_dev.shape) != (S,):
+        raise ValueError(f"center_u must hold {S} values, got shape {tuple(cu_dev.shape)}")
+    _, _, n_f, n_q = a.shape
+    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
+
+    # (x2, ls, lc, u, w, N, C, squeeze) per state: a one-row state has no pitch of its own
+    pitches = {o[1] for o in ops if o[5] > 1} or {ops[0][1]}
+    one_launch = (all(o[2] == 1 for o in ops) and len(pitches) == 1
+                  and len({o[0].data_ptr() & 15 == 0 for o in ops}) == 1)
+    if not one_launch:
+        cu_host = center_u.cpu().numpy() if isinstance(center_u, torch.Tensor) else np.asarray(center_u, dtype=np.float64)
+        parts = [influence_cov(xs[s], us[s], a[s], b[s], float(cu_host[s]), center_x[s], w=None if ws is None else ws[s])
+                 for s in range(S)]
+        return torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts])
+
+    tab = (_lib.InfState * S)()
+    for s, (x2, _, _, u, w, N, _, _) in enumerate(ops):
+        tab[s].x, tab[s].u, tab[s].n = x2.data_ptr(), u.data_ptr(), N
+        tab[s].w = w.data_ptr() if w is not None else None
+    cov = torch.empty((S, C, n_f, n_f), dtype=F64, device="cuda")
+    mean = torch.empty((S, C, n_f), dtype=F64, device="cuda")
+    wsb = workspace(L.txm_influence_cov_batched_ws_bytes(S, max(o[5] for o in ops), C, n_q))
+    check(
+        L.txm_influence_cov_batched(tab, S, pitches.pop(), C, n_f, n_q, _ptr(cu_dev), _ptr(center_x), _ptr(a), _ptr(b),
+                                    _ptr(cov), _ptr(mean), _ptr(wsb), wsb.numel(), _stream()),
+        "txm_influence_cov_batched",
+    )
+    del ops
+    return cov, mean
+
+
+TAYLOR_MODES ={"sum": 0, "cumsum": 1, "terms": 2}
 
 
 def predict_taylor(derivs: torch.Tensor, dalphas, mode: str = "sum") -> torch.Tensor:

@@ -199,8 +199,10 @@ def input_GP_from_states(states, n_rep=100, log_scale=False, sampler=None, shard
     its contiguous share of the states; "local" -- every rank passes only ITS states (rank order = state order).  One
     all-gather of the per-state blocks; every rank returns the full tuple (see _input_gp_sharded).
 
-    ``method="delta"`` (extension): the per-state delta-method covariances (``input_GP_from_state(method="delta")``, a
-    loop over the states, one pass over each state's samples) in the same block-diagonal layout; no sampler is drawn."""
+    ``method="delta"`` (extension): the per-state delta-method covariances (``input_GP_from_state(method="delta")``, one
+    pass over each state's samples) in the same block-diagonal layout; no sampler is drawn.  States of one column shape
+    and order -- of ANY length each -- take one launch per kernel for the whole collection
+    (``StateCollection.derivs_cov``, txm_influence_cov_batched); other collections loop over the states."""
     from .models import StateCollection
 
     _check_method(method)
@@ -210,6 +212,21 @@ def input_GP_from_states(states, n_rep=100, log_scale=False, sampler=None, shard
         if sharded:
             raise NotImplementedError('method="delta" with sharded=...')
         order = coll.order
+        if coll._delta_batch_eligible() is not None:
+            # every state's covariance from one launch per kernel whatever the states' lengths, the states' own
+            # derivatives from one evaluation over the stacked states (as _batched_blocks does): two copies back
+            import torch
+
+            from . import moments as cm
+
+            st0 = coll[0]
+            cov_d, _, _ = coll._derivs_cov_fill(order, st0.minus_log)
+            d0 = st0.data
+            stack = torch.stack([st.data.dxduave.device_values for st in coll])
+            one = d0.new_like(dxduave=cm.CentralMomentsData(stack, mom_ndim=2, dims=("rep", *d0.dxduave.dims)), rec_dim="rep")
+            dv_d, _ = st0.derivatives.derivs(data=one, order=order, norm=False, minus_log=st0.minus_log, _device=True)
+            return _assemble(np.array([float(st.alpha0) for st in coll]), dv_d.permute(1, 0, 2).contiguous().cpu().numpy(),
+                             cov_d.cpu().numpy(), log_scale, order)
         parts = [input_GP_from_state(st, method="delta") for st in coll]
         return _assemble(np.array([float(st.alpha0) for st in coll]), np.stack([p_[1] for p_ in parts]),
                          np.stack([p_[2] for p_ in parts]), log_scale, order)

@@ -508,9 +508,10 @@ class ExtrapModel(_Params):
         return self._ds(out.sum(order_dim))
 
     # ---- delta-method error bars -----------------------------------------------------------------------
-    def _delta_operands(self):
+    def _delta_operands(self, device_state=False):
         """(x [N, C], u [N], w [N] or None, central state [C, 2, K] on the host, derivative source) for ``derivs_cov`` --
-        or NotImplementedError naming what this model is that the one-pass formula does not cover."""
+        or NotImplementedError naming what this model is that the one-pass formula does not cover.
+        ``device_state``: leave the central state on the device (a collection copies all its states' at once)."""
         from . import moments as cm
         from .data import DataCallback, DataCentralMoments, DataCentralMomentsVals, DataValuesBase
 
@@ -551,23 +552,40 @@ class ExtrapModel(_Params):
             if wt.shape != (N,):
                 raise NotImplementedError(f"{what}: weight must be 1-D along {data.rec_dim!r}")
         K = state.device_values.shape[-1]
-        return x2, ut, wt, state.device_values.reshape(-1, 2, K).cpu().numpy(), src
+        sd = state.device_values.reshape(-1, 2, K)
+        return x2, ut, wt, (sd if device_state else sd.cpu().numpy()), src
+
+    def _delta_coefs(self, st, order, minus_log):
+        """(a, b [C, order + 1, order + 1], <u>, <x> [C]) on the host: the influence polynomials of ``derivs(order)`` from
+        the central state ``st`` [C, 2, K] (symbolic.influence_coefs)."""
+        if order > st.shape[-1] - 1:
+            raise ValueError(f"order {order} requested, but the data object only holds moments to order {st.shape[-1] - 1}")
+        # the central state: [c][0][1] = <u>, [c][1][0] = <x_c>, [c][0][j] = <du^j>, [c][1][j] = <dx_c du^j>
+        um, xm = float(st[0, 0, 1]), st[:, 1, 0]
+        mom = S.influence_moments(xm, um, [0.0, 0.0] + [float(st[0, 0, j]) for j in range(2, order + 1)],
+                                  [0.0] + [st[:, 1, j] for j in range(1, order + 1)])
+        a, b = S.influence_coefs(self.derivatives.series, order, mom, minus_log=minus_log)
+        return np.ascontiguousarray(a), np.ascontiguousarray(b), um, xm
 
     def _derivs_cov_device(self, order, minus_log):
         key = ("dcov", order, minus_log)
         if key not in self._cache:
             x2, ut, wt, st, src = self._delta_operands()
-            if order > st.shape[-1] - 1:
-                raise ValueError(f"order {order} requested, but the data object only holds moments to order {st.shape[-1] - 1}")
-            # the central state: [c][0][1] = <u>, [c][1][0] = <x_c>, [c][0][j] = <du^j>, [c][1][j] = <dx_c du^j>
-            um, xm = float(st[0, 0, 1]), st[:, 1, 0]
-            mom = S.influence_moments(xm, um, [0.0, 0.0] + [float(st[0, 0, j]) for j in range(2, order + 1)],
-                                      [0.0] + [st[:, 1, j] for j in range(1, order + 1)])
-            a, b = S.influence_coefs(self.derivatives.series, order, mom, minus_log=minus_log)
-            cov, _ = engine.influence_cov(x2, ut, engine.to_device(np.ascontiguousarray(a)),
-                                          engine.to_device(np.ascontiguousarray(b)), um, engine.to_device(xm), w=wt)
+            a, b, um, xm = self._delta_coefs(st, order, minus_log)
+            cov, _ = engine.influence_cov(x2, ut, engine.to_device(a), engine.to_device(b), um, engine.to_device(xm), w=wt)
             self._cache[key] = (cov, src)
         return self._cache[key]
+
+    @staticmethod
+    def _derivs_cov_labelled(host, src, order, norm):
+        """The host copy of a ``_derivs_cov_device`` table (n_out, order + 1, order + 1) as ``derivs_cov`` returns it."""
+        if norm:
+            f = np.array([1.0 / math.factorial(i) for i in range(order + 1)])
+            host = host * f[None, :, None] * f[None, None, :]
+        out = DataArray(np.ascontiguousarray(np.moveaxis(host, 0, -1)).reshape(order + 1, order + 1, *src.out_shape),
+                        ("order", "order_2", *src.out_dims))
+        out._inherit(src.coords)
+        return out
 
     def derivs_cov(self, order=None, norm=False, minus_log=None):
         """Delta-method (infinitesimal-jackknife) covariance of ``derivs(order)``: dims ``(order, order_2, *val_dims)``.
@@ -586,14 +604,7 @@ class ExtrapModel(_Params):
         if order is None:
             order = self.order
         cov, src = self._derivs_cov_device(order, bool(minus_log))
-        host = cov.cpu().numpy()                                   # (n_out, order + 1, order + 1)
-        if norm:
-            f = np.array([1.0 / math.factorial(i) for i in range(order + 1)])
-            host = host * f[None, :, None] * f[None, None, :]
-        out = DataArray(np.ascontiguousarray(np.moveaxis(host, 0, -1)).reshape(order + 1, order + 1, *src.out_shape),
-                        ("order", "order_2", *src.out_dims))
-        out._inherit(src.coords)
-        return self._ds(out)
+        return self._ds(self._derivs_cov_labelled(cov.cpu().numpy(), src, order, norm))     # (n_out, order + 1, order + 1)
 
     def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None):
         """``(prediction, std)``: ``predict(alpha)`` and its delta-method standard deviation ``sqrt(t' V t)``,
@@ -671,6 +682,100 @@ class StateCollection(_Params):
             elif k != key:
                 return None
         return key
+
+    # ---- delta-method error bars of all states from one set of launches ---------------------------------
+    def _delta_batch_eligible(self):
+        """The states' shared key when every state is an ExtrapModel over DataCentralMomentsVals with one column shape /
+        order / central / minus_log / derivatives object, all weighted or none -- and ANY number of samples per state
+        (txm_influence_cov_batched takes a count per state; ``_batch_eligible`` asks for one N).  Else None: the caller
+        loops.  Whether ``ExtrapModel._delta_operands`` accepts the states shows when their operands are gathered: on
+        either path a state it refuses raises its NotImplementedError through the collection."""
+        from .data import DataCentralMomentsVals
+
+        key = None
+        for st in self.states:
+            d = getattr(st, "data", None)
+            if not isinstance(st, ExtrapModel) or type(d) is not DataCentralMomentsVals:
+                return None
+            try:
+                rec = d.xv.dims.index(d.rec_dim)
+                cols = tuple(n for i, n in enumerate(d.xv.shape) if i != rec)
+                dims = tuple(n for i, n in enumerate(d.xv.dims) if i != rec)
+            except (AttributeError, ValueError):
+                return None
+            k = (cols, dims, d.order, d.weight is None, d.central, st.order, st.minus_log, id(st.derivatives))
+            if key is None:
+                key = k
+            elif k != key:
+                return None
+        return key
+
+    def _derivs_cov_fill(self, order=None, minus_log=None):
+        """Fill every state's ``("dcov", order, minus_log)`` cache -- what ``ExtrapModel._derivs_cov_device`` computes,
+        bit for bit -- and return ``(cov [S, n_out, order + 1, order + 1] on the device, sources, order)``.
+        Eligible states (``_delta_batch_eligible``): ONE copy of the stacked central states to the host, the
+        coefficient algebra there, ONE ``engine.influence_cov_batched``.  Otherwise a loop over the states.
+
+        The host algebra runs state by state although symbolic.influence_coefs broadcasts: the single path hands it
+        ``<u>`` as a Python float, and ``float ** int`` need not round like ``ndarray ** int`` (it matters in the raw
+        form, which expands about zero), so only the per-state call is certain to give the single call's coefficients."""
+        sts = self.states
+        if self._delta_batch_eligible() is not None:
+            o = sts[0].order if order is None else order
+            ml = bool(sts[0].minus_log if minus_log is None else minus_log)
+            key = ("dcov", o, ml)
+            todo = [st for st in sts if key not in st._cache]
+            if todo and o <= todo[0].data.order:
+                ops = [st._delta_operands(device_state=True) for st in todo]       # raises what a state raises
+                host = torch.stack([op[3] for op in ops]).cpu().numpy()            # [S, C, 2, K]: one copy
+                co = [st._delta_coefs(host[s], o, ml) for s, st in enumerate(todo)]
+                cov, _ = engine.influence_cov_batched(
+                    [op[0] for op in ops], [op[1] for op in ops],
+                    engine.to_device(np.stack([c[0] for c in co])), engine.to_device(np.stack([c[1] for c in co])),
+                    np.array([c[2] for c in co]), engine.to_device(np.stack([c[3] for c in co])),
+                    ws=None if ops[0][2] is None else [op[2] for op in ops])
+                for s, st in enumerate(todo):
+                    st._cache[key] = (cov[s], ops[s][4])
+                if len(todo) == len(sts):
+                    return cov, [op[4] for op in ops], o
+            parts = [st._derivs_cov_device(o, ml) for st in sts]
+            return torch.stack([p_[0] for p_ in parts]), [p_[1] for p_ in parts], o
+        parts, orders = [], []
+        for st in sts:
+            if not hasattr(st, "_derivs_cov_device"):
+                raise NotImplementedError(f"derivs_cov / predict_with_error (delta-method error bars): unsupported state "
+                                          f"{type(st).__name__}")
+            o = st.order if order is None else order
+            parts.append(st._derivs_cov_device(o, bool(st.minus_log if minus_log is None else minus_log)))
+            orders.append(o)
+        same = len(set(orders)) == 1 and len({tuple(p_[0].shape) for p_ in parts}) == 1
+        return (torch.stack([p_[0] for p_ in parts]) if same else None), [p_[1] for p_ in parts], orders[0]
+
+    def derivs_cov(self, order=None, norm=False, minus_log=None):
+        """Every state's ``derivs_cov`` joined along the states: bit for bit
+        ``map_concat(lambda m: m.derivs_cov(order, norm, minus_log))``.  The states are independent simulations, so the
+        covariance of anything linear in their derivatives is block diagonal in these per-state blocks.
+
+        States that share a column shape, order and derivatives object -- with ANY number of samples each, as
+        ``timeseries.decorrelate`` leaves them -- are served by one launch per kernel (txm_influence_cov_batched) after one
+        copy of their moments to the host; other collections loop.  Either way every state's own ``derivs_cov()`` is
+        answered from its cache afterwards.  Assumptions: those of ``ExtrapModel.derivs_cov``."""
+        cov, srcs, o = self._derivs_cov_fill(order, minus_log)
+        if cov is None:
+            return self.map_concat(lambda m: m.derivs_cov(order=order, norm=norm, minus_log=minus_log))
+        host = cov.cpu().numpy()
+        out = [st._ds(ExtrapModel._derivs_cov_labelled(host[s], srcs[s], o, norm)) for s, st in enumerate(self.states)]
+        if is_labelled(out[0]):
+            out = concat(out, dim=DataArray(np.asarray(self.alpha0), self.alpha_name))
+        return out
+
+    def _state_covs(self, order, minus_log):
+        """Host copies of the states' delta-method covariances, [S][n_out, order + 1, order + 1], and their sources."""
+        cov, srcs, _ = self._derivs_cov_fill(order, minus_log)
+        if cov is None:
+            return [st._derivs_cov_device(order, bool(st.minus_log if minus_log is None else minus_log))[0].cpu().numpy()
+                    for st in self.states], srcs
+        return list(cov.cpu().numpy()), srcs
 
     # states per launch of the batched path: the sampler table is [S * nrep][ntiles] and the grid carries the state on z
     _BATCH_MAX_REPS = 1 << 22
@@ -1067,6 +1172,43 @@ class ExtrapWeightedModel(StateCollection, PiecewiseMixin):
         num = sum(p * w.isel(state=i) for i, p in enumerate(preds))
         return num / w.sum("state")
 
+    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None, method=None, bounded=False):
+        """``(predict(alpha, ...), std)``: the blended prediction, bit for bit ``predict``'s, and its delta-method
+        standard deviation.  The blend is ``sum_i w_i T_i(alpha) / sum_i w_i`` over the two states ``predict`` picks
+        (``method``, ``bounded`` as there), with the Minkowski weights ``w_i`` a function of alpha alone, so
+
+            var = sum_i (w_i / sum w)^2 t_i' V_i t_i,    t_ik = (alpha - alpha0_i)^k / k!,  V_i = states[i].derivs_cov(order)
+
+        Assumptions: independent samples within a state (``ExtrapModel.derivs_cov``), independent states (no cross
+        terms), first order.  All states' ``V_i`` come from one launch per kernel (``StateCollection.derivs_cov``); a state
+        that ``derivs_cov`` refuses raises its NotImplementedError."""
+        self._check_alpha(alpha, bounded)
+        if order is None:
+            order = self.order
+        if alpha_name is None:
+            alpha_name = self.alpha_name
+        covs, srcs = self._state_covs(order, minus_log)                # (first: an unsupported state says so)
+        pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name, method=method, bounded=bounded)
+        al = xrwrap_alpha(alpha, name=alpha_name)
+        a0 = np.asarray(self.alpha0, dtype=np.float64)
+        fact = np.array([math.factorial(k) for k in range(order + 1)], dtype=np.float64)
+        var = []
+        for a in np.asarray(al.values, dtype=np.float64).reshape(-1):
+            idx = [0, 1] if len(self) == 2 else self._indices_alpha(float(a), method)
+            dm = np.abs(a - a0[idx]) ** 20                                        # xr_weights_minkowski, m = 20
+            w = 1.0 - dm / dm.sum()
+            wn = w / w.sum()
+            v = 0.0
+            for wi, i in zip(wn, idx):
+                t = (a - a0[i]) ** np.arange(order + 1) / fact
+                v = v + wi * wi * np.einsum("i,cij,j->c", t, covs[i], t)
+            var.append(v)
+        src = srcs[0]
+        std = DataArray(np.sqrt(np.maximum(np.array(var), 0.0)).reshape((*al.shape, *src.out_shape)), (*al.dims, *src.out_dims))
+        std._inherit(al._coords)
+        std._inherit(src.coords)
+        return pred, self[0]._ds(std)
+
 
 class InterpModel(StateCollection):
     """One polynomial through the value and the first ``order`` derivatives at
@@ -1110,6 +1252,38 @@ class InterpModel(StateCollection):
         p = DataArray(np.arange(coefs.sizes[order_dim]), order_dim)
         return ((alpha**p) * coefs).sum(order_dim)
 
+    def _predict_std(self, alpha, order, minus_log, alpha_name):
+        """Delta-method standard deviation of ``predict(alpha)`` (see ``predict_with_error``)."""
+        covs, srcs = self._state_covs(order, minus_log)                # [S][n_out, order + 1, order + 1]
+        inv = self._hermite_inverse(order)                              # [porder, state * (order + 1)]
+        al = xrwrap_alpha(alpha, name=alpha_name)
+        av = np.asarray(al.values, dtype=np.float64).reshape(-1)
+        g = (av[:, None] ** np.arange(inv.shape[0])[None, :]) @ inv     # (n_alpha, S (order + 1))
+        g = g.reshape(len(av), len(self), order + 1)
+        var = sum(np.einsum("ai,cij,aj->ac", g[:, s], covs[s], g[:, s]) for s in range(len(self)))
+        src = srcs[0]
+        std = DataArray(np.sqrt(np.maximum(var, 0.0)).reshape((*al.shape, *src.out_shape)), (*al.dims, *src.out_dims))
+        std._inherit(al._coords)
+        std._inherit(src.coords)
+        return self[0]._ds(std)
+
+    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None):
+        """``(predict(alpha), std)``: the interpolation, bit for bit ``predict``'s, and its delta-method standard
+        deviation.  ``predict`` is linear in the states' un-normalised derivatives D (stacked state by state):
+        ``g(alpha)' D`` with ``g = (alpha^p) . hermite_inverse``, so
+
+            var = sum_s g_s' V_s g_s,      V_s = states[s].derivs_cov(order)
+
+        Assumptions: independent samples within a state (``ExtrapModel.derivs_cov``: decorrelate time series first),
+        independent states (the covariance of D is block diagonal), first order.  All ``V_s`` come from one launch per
+        kernel (``StateCollection.derivs_cov``); a state that ``derivs_cov`` refuses raises its NotImplementedError."""
+        if order is None:
+            order = self.order
+        if alpha_name is None:
+            alpha_name = self.alpha_name
+        std = self._predict_std(alpha, order, minus_log, alpha_name)    # (first: an unsupported state says so)
+        return self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name), std
+
 
 class InterpModelPiecewise(StateCollection, PiecewiseMixin):
     """Two-state Hermite interpolation chosen per alpha (reference models.py:949-1006)."""
@@ -1134,6 +1308,28 @@ class InterpModelPiecewise(StateCollection, PiecewiseMixin):
         if len(outs) == 1:
             return outs[0]
         return concat(outs, dim=DataArray(np.asarray(seq), alpha_name))
+
+    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None, method=None, bounded=False):
+        """``(predict(alpha, ...), std)``: for every alpha the two-state ``InterpModel`` that ``predict`` chooses
+        (``method``, ``bounded`` as there) and that model's ``predict_with_error`` -- its assumptions apply: independent
+        samples within a state, independent states, first order.  The covariances of ALL states are taken first, in one
+        launch per kernel, so the pairs find them in their states' caches."""
+        self._check_alpha(alpha, bounded)
+        self._derivs_cov_fill(order, minus_log)                         # (first: an unsupported state says so)
+        pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name, method=method, bounded=bounded)
+        if alpha_name is None:
+            alpha_name = self.alpha_name
+
+        def std_of(pair, a):
+            return pair._predict_std(a, pair.order if order is None else order, minus_log, alpha_name)
+
+        if len(self) == 2:
+            return pred, std_of(self.single_interpmodel(0, 1), alpha)
+        seq = [float(a) for a in _alpha_seq(alpha)]
+        outs = [std_of(self.single_interpmodel(*self._indices_alpha(a, method)), a) for a in seq]
+        if len(outs) == 1:
+            return pred, outs[0]
+        return pred, concat(outs, dim=DataArray(np.asarray(seq), alpha_name))
 
 
 class MBAROverlap(NamedTuple):
@@ -1252,6 +1448,10 @@ class MBARModel(StateCollection):
         if avals.ndim != 1:
             raise ValueError("alpha must be a scalar or 1-D")
         return avals, alpha_name
+
+    def derivs_cov(self, order=None, norm=False, minus_log=None):
+        raise NotImplementedError("derivs_cov (delta-method error bars of the states' derivatives): MBARModel predicts "
+                                  "from the pooled samples, not from derivatives; its error bars are predict_with_error")
 
     def predict_with_error(self, alpha, alpha_name=None):
         """(mean, err): ``predict(alpha)`` bit for bit and its asymptotic standard deviation (pymbar's ``dA`` of
