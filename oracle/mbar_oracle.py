@@ -1,14 +1,16 @@
 """
 oracle/mbar_oracle.py -- TEST INFRASTRUCTURE, NOT PRODUCT.
 
-Plain restatements, in ``numpy.longdouble`` (x87 80-bit, eps = 1.08e-19), of what the four MBAR entry points sum
-(txm_mbar.hip, txm_mbar_boot.hip), from the same float64 inputs the kernels get: the energies ``us`` of the K states,
+Plain restatements, in ``numpy.longdouble`` (x87 80-bit, eps = 1.08e-19), of what the four MBAR entry points
+(txm_mbar.hip, txm_mbar_boot.hip) and the covariance pass (txm_mbar_cov.hip) sum, from the same float64 inputs the kernels get: the energies ``us`` of the K states,
 ``alpha0``, the shifted log-weights ``g``, the pivot ``upiv`` and, for a bootstrap replicate, the integer count ``c_n`` of
 every pooled sample.  ``ut = u - upiv`` and every exponent are formed in long double.
 
     p_kn   = softmax_k(g_k - alpha0_k ut_n)          logD_n = ln sum_k e^{g_k - alpha0_k ut_n}
     S_k    = sum_n c_n p_kn      H_jk = sum_n c_n p_jn p_kn      obj = sum_n c_n logD_n
     <x>(a) = sum_n c_n w_an x_n / sum_n c_n w_an,     w_an = e^{-a ut_n - logD_n}
+    W_nk = p_kn / N_k     W_na = w_an / sum_n w_an     d_nc = x_nc - mean_ac
+    Q_a = sum_n W_na^2    B_ak = sum_n W_nk W_na       yy_ac = sum_n W_na^2 d_nc^2     b_kac = sum_n W_nk W_na d_nc
 
 Next to every sum comes that sum's own first-order bound  sum_n kappa_n |term_n|  (README "Tolerances"), with the
 per-sample conditioning
@@ -129,3 +131,62 @@ def predict(us, xs, alpha0, upiv, targets, *, logD=None, g=None, counts=None) ->
         scale[i] = ((w @ ax) / den).astype(np.float64)
         kap[i] = kn[w > LD(1e-30) * w.max()].max()
     return Averages(avg, scale, kap, kn)
+
+
+class CovSums(NamedTuple):
+    """Values and bounds are long double, one leading index per target.  ``den`` and ``dabs`` are what an absolute floor
+    for products a float64 kernel flushes is built from (tests/test_mbar_kernels_gpu.py, group E)."""
+
+    Q: np.ndarray          # (n_alpha,)
+    Q_bound: np.ndarray
+    B: np.ndarray          # (n_alpha, K)
+    B_bound: np.ndarray
+    yy: np.ndarray         # (n_alpha, C)
+    yy_bound: np.ndarray
+    b: np.ndarray          # (n_alpha, C, K): the order of the kernel's output
+    b_bound: np.ndarray
+    lnw: np.ndarray        # (n_alpha,) ln sum_n v_an
+    den: np.ndarray        # (n_alpha,) sum_n v_an / max_n v_an: the denominator as the kernel holds it (>= 1)
+    dabs: np.ndarray       # (n_alpha, C) sum_n |d_nc|
+    kappa_n: np.ndarray    # (N,) float64
+    kappa: float           # the largest kappa_n
+    p_min: float
+
+
+def cov_sums(us, xs, alpha0, g, upiv, targets, means, logD) -> CovSums:
+    """What txm_mbar_cov sums.  p_kn is the softmax at ``g`` formed here; ``logD`` (N,) and ``means`` (n_alpha, C) are the
+    float64 arrays the kernel reads.  The contractions over the samples are matrix products, one target at a time."""
+    ut = pooled_ut(us, upiv)
+    t = exponents(alpha0, g, ut)
+    e = np.exp(t - t.max(axis=0))
+    p = e / e.sum(axis=0)
+    Wk = p / _ld([len(u) for u in us]).reshape(-1, 1)                   # (K, N)
+    ld = _ld(logD).reshape(-1)
+    x = np.concatenate([_ld(v).reshape(len(v), -1) for v in xs])
+    al = np.atleast_1d(np.asarray(targets, dtype=np.float64)).ravel()
+    mu = _ld(means).reshape(len(al), -1)
+    if ld.shape != ut.shape or x.shape[0] != ut.shape[0] or mu.shape[1] != x.shape[1]:
+        raise ValueError("logD and x need one row per pooled sample, means one row per target")
+    kn = kappa(alpha0, g, ut, al, ld)
+    kl = _ld(kn)
+    K, C, na = Wk.shape[0], x.shape[1], len(al)
+    Q, Qb, lnw, den = (np.empty(na, dtype=LD) for _ in range(4))
+    B, Bb = np.empty((na, K), dtype=LD), np.empty((na, K), dtype=LD)
+    yy, yyb, dabs = (np.empty((na, C), dtype=LD) for _ in range(3))
+    b, bb = np.empty((na, C, K), dtype=LD), np.empty((na, C, K), dtype=LD)
+    for i, a in enumerate(al):
+        ex = -LD(a) * ut - ld
+        mx = ex.max()
+        v = np.exp(ex - mx)
+        den[i] = v.sum()
+        lnw[i] = mx + np.log(den[i])
+        wa = v / den[i]
+        d = x - mu[i][None, :]
+        wd = wa[:, None] * d                                            # (N, C)
+        kwa = kl * wa
+        Q[i], Qb[i] = wa @ wa, kwa @ wa
+        B[i], Bb[i] = Wk @ wa, Wk @ kwa
+        yy[i], yyb[i] = (wd * wd).sum(axis=0), kl @ (wd * wd)
+        b[i], bb[i] = (Wk @ wd).T, (Wk @ (kl[:, None] * np.abs(wd))).T
+        dabs[i] = np.abs(d).sum(axis=0)
+    return CovSums(Q, Qb, B, Bb, yy, yyb, b, bb, lnw, den, dabs, kn, float(kn.max()), float(p.min()))

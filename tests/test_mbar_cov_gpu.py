@@ -7,10 +7,15 @@ txm_mbar_predict; every sum is held to |hip - ref| <= 1e-12 * sum_n |term_n| -- 
 rule of tests/test_perturb_gpu.py -- with ref the long-double sum at the same g and the same mean.  A weight's relative
 error is at most (|exponent| + c) eps with exponents of a few hundred at most here (< 1e-13), and the summation adds eps
 times (terms per lane + tree depth).  Every case prints its worst ratio |hip - ref| / sum |term| (run with -s).
-Shapes follow the kernel's paths: NA templates 1 / 2 / 4 / 8 (n_alpha 1, 2, 3, 8), the register (K <= 8) and LDS (K = 12,
-16) forms of the evaluation pass that supplies logD, one and two row tiles (K < 16, K = 16: the row of ones alone in the
-second tile), one to three column groups (C + 1 <= 16, 17 + 1, 33 + 1), a row pitch above C, states of 1 sample, of less
-than a tile and of several workgroups with a ragged last tile.
+What these cases reach of the kernel's paths: NA templates 1 / 2 / 4 / 8 (n_alpha 1, 2, 3, 8), the register (K <= 8) and
+LDS (K = 12, 16) forms of the evaluation pass that supplies logD, one row tile of states (K <= 16; at K = 16 a second tile
+holds the row of ones alone), C of 1, 3, 17 and 33 (one to three column groups, the column of ones at index 1 or 3 of its
+group), a row pitch above C, states of 1 sample, of less than a tile and of several workgroups with a ragged last tile.
+They do not reach a state row in a second row tile (K >= 17), the ones at index 15 or alone behind full tiles, two row
+tiles together with two column groups, a binding workgroup cap, or a g that is no solution; and logD and the centres come
+from two other device kernels.  All of that is group E of tests/test_mbar_kernels_gpu.py, with host-made inputs against
+oracle/mbar_oracle.py cov_sums.  The one API-level case above 16 states is
+test_api_above_sixteen_states_against_the_dense_restatement below.
 """
 
 import ctypes as ct
@@ -291,6 +296,56 @@ def test_api_against_the_dense_restatement(small):
     assert one[0].values.shape == one[1].values.shape == (1, 2)
     named = m.free_energy([1.1], alpha_name="b")
     assert named[0].dims == named[1].dims == ("b",)
+
+
+def test_api_above_sixteen_states_against_the_dense_restatement(txm):
+    """K = 17 (alpha0 1.0 ... 2.6, 9 to 13 samples per state, 187 pooled: dense_theta takes 200), C = 2: the public methods
+    with a state row in the kernel's second row tile.  The restatement's own error is about 4e-15 on this shape, so the bound is
+    its 1e-10 floor.  Nothing is asserted on the overlap eigenvalues: the smallest is about 1e-17, numerically zero."""
+    import thermoextrap_amd as xtrap
+
+    K = 17
+    a0, ns = [1.0 + 0.1 * k for k in range(K)], ([9, 10, 11, 12, 13] * 4)[:K - 2] + [11, 11]
+    assert sum(ns) == 187 and min(ns) == 9 and max(ns) == 13
+    us, xs = gauss_problem(a0, ns, C=2, seed=17)
+    m = xtrap.MBARModel([xtrap.beta.factory_extrapmodel(beta=b, data=xtrap.factory_data_values(uv=u, xv=x, order=1, central=False))
+                         for b, x, u in zip(a0, xs, us)])
+    fref = ref_solve(us, a0)
+    targets = [a0[8], 1.35, 0.9, 2.7]
+    Ws, Wt, lnw = ref_columns(us, a0, fref, targets)
+    Ns, x = np.array(ns, dtype=np.float64), np.concatenate(xs).astype(LD)
+    dense = dense_theta(Ws, Ns)
+    own = rel(gram_theta(Ws, Ns), dense)
+    tol, scale = bound(own), np.abs(dense).max()
+    th = m.free_energy_covariance()
+    print(f"\nK = 17: restatement's own {own:.2e}; Theta {rel(th, dense):.2e}")
+    assert th.shape == (K, K) and rel(th, dense) <= tol
+    f, df = m.free_energy()
+    assert df.values[0] == 0.0 and f.values[0] == 0.0
+    np.testing.assert_allclose(f.values, np.asarray(fref, dtype=np.float64), rtol=0, atol=1e-10)
+    want = np.diag(dense) + dense[0, 0] - 2.0 * dense[0]
+    assert np.all(np.abs(df.values ** 2 - want) <= tol * scale)
+    mean, err = m.predict_with_error(targets)
+    assert np.array_equal(mean.values, m.predict(targets).values) and err.values.shape == (4, 2)
+    ft, dft = m.free_energy(targets)
+    worst = 0.0
+    for t, a in enumerate(targets):
+        wa = Wt[:, t]
+        mu = target_sums(Ws, wa, x)[0]
+        assert abs(ft.values[t] + float(lnw[t])) <= 1e-10
+        W1 = np.concatenate([Ws, wa[:, None]], axis=1)
+        d1 = dense_theta(W1, np.append(Ns, 0.0))
+        o1 = rel(gram_theta(W1, np.append(Ns, 0.0)), d1)
+        v1 = d1[K, K] + d1[0, 0] - 2.0 * d1[0, K]
+        assert abs(dft.values[t] ** 2 - v1) <= bound(own, o1) * max(v1, np.abs(d1).max())
+        for c in range(2):
+            Wy = np.concatenate([Ws, (wa * (x[:, c] - mu[c]))[:, None]], axis=1)
+            dy = dense_theta(Wy, np.append(Ns, 0.0))[K, K]
+            oy = abs(gram_theta(Wy, np.append(Ns, 0.0))[K, K] - dy) / dy
+            worst = max(worst, abs(err.values[t, c] ** 2 - dy) / dy)
+            assert abs(err.values[t, c] ** 2 - dy) <= bound(own, oy) * dy, (a, c)
+    print(f"variance of the averages: worst relative difference from the dense Theta_yy {worst:.2e}")
+    assert abs(ft.values[0] - f.values[8]) <= 1e-10 and abs(dft.values[0] ** 2 - df.values[8] ** 2) <= tol * scale
 
 
 def test_asymptotic_error_matches_the_bootstrap_spread(txm):

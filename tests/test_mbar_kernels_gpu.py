@@ -1,6 +1,6 @@
 """Differential tests of the four MBAR entry points -- txm_mbar_eval, txm_mbar_predict (txm_mbar.hip), txm_mbar_boot_eval,
-txm_mbar_boot_predict (txm_mbar_boot.hip) -- against the long-double restatement oracle/mbar_oracle.py, on every path of
-their dispatch.  tests/test_mbar_gpu.py and tests/test_mbar_boot_gpu.py reach these kernels through the converged Newton
+txm_mbar_boot_predict (txm_mbar_boot.hip) -- and of the covariance pass txm_mbar_cov (txm_mbar_cov.hip, group E) against
+the long-double restatement oracle/mbar_oracle.py, on every path of their dispatch.  tests/test_mbar_gpu.py and tests/test_mbar_boot_gpu.py reach these kernels through the converged Newton
 solve only: a wrong Hessian or objective still converges, and only near-solution log-weights are ever seen.  Here g is
 NOT a solution (the thermodynamic-integration start plus N(0, 0.5) noise per state; for the bootstrap an independent
 noise row per replicate around gref, so min_k (g^r - gref)_k is non-zero and differs between rows), and S, every entry
@@ -25,6 +25,28 @@ log and the divide and for the summation (a few hundred terms per lane plus the 
 absolute floor stands for terms the device flushes to zero; it is the larger part of a bound in the poor-overlap case
 alone.  Bit-for-bit claims (``active`` subsets, ``rows``, ``logD=None``) are held with array_equal.  Every case prints
 its worst ratio |hip - ref| / bound-sum (run with -s).
+
+Group E: txm_mbar_cov.  Q_a, every B_ak, yy_ac and b_kac, with g, logD and the centres made on the host (no other device
+kernel supplies an input), at the smallest shapes where each tile-index expression of the MFMA kernel and of its final
+kernel can go wrong: state rows in row tiles 1 to 4 (K = 17 ... 64), the row of ones at index 0, 1 and 15 of its tile, the
+column of ones at index 15 of a group and alone behind full groups, RT >= 2 together with NCG >= 2, the workgroup cap
+binding (more than four grid-stride turns) and clamped to one.
+
+  Q, B, yy, b   |hip - ref| <= 1e-12 sum_n kappa_n |term_n| + floor
+  lnw_a         |hip - ref| <= 1e-12 kappa (1 + |ref|)                  (kappa: the largest kappa_n)
+
+The floor, from the kernel's own expressions.  A sample enters a matrix-pipe row as pm * va with pm = p_kn <= 1 and
+va = e^{-a ut_n - logD_n - M_a} <= 1 (M_a is the exact maximum, so sum_n va >= 1 -- ``den`` of the restatement).  Where
+the true product is below 2^-1022 -- because p_kn underflowed in the softmax, because va did, or because only their
+product does -- the device holds a subnormal or zero in its place: an absolute error of at most 2^-1022 per sample,
+times |d_nc| in b (times 1 in B).  The VALU side squares t = va d_nc: t^2 below 2^-1022 is lost in the same way (Q: d = 1).
+These errors are made BEFORE the final kernel divides by N_k sum_n va (B, b) or (sum_n va)^2 (Q, yy), so
+
+  floor(B_ak) = 2^-1022 N_total / (N_k den_a)        floor(b_kac) = 2^-1022 sum_n |d_nc| / (N_k den_a)
+  floor(Q_a) = floor(yy_ac) = 2^-1022 N_total / den_a^2
+
+(tests/test_mbar_oracle_cpu.py cov_floor).  The CPU module asserts that it is below 1e-250 of every bound in the ordinary
+cases and the larger part of some B and b bounds in the poor-overlap case.  lnw needs none: sum_n va >= 1.
 """
 
 import ctypes as ct
@@ -34,9 +56,10 @@ import pytest
 import torch
 
 from oracle import mbar_oracle as mo
-from test_mbar_oracle_cpu import (BOOT_EVAL_CASES, BOOT_NREP, BOOT_PREDICT_CASES, EVAL_CASES, EVAL_NOLOGD, PREDICT_CASES,
-                                  boot_eval_case, boot_predict_case, eval_case, poor_overlap_inputs,
-                                  poor_overlap_predict_inputs, predict_case)
+from test_mbar_oracle_cpu import (BOOT_EVAL_CASES, BOOT_NREP, BOOT_PREDICT_CASES, COV_CASES, COV_POOR, EVAL_CASES,
+                                  EVAL_NOLOGD, PREDICT_CASES, boot_eval_case, boot_predict_case, cov_floor,
+                                  cov_reference, eval_case, poor_overlap_inputs, poor_overlap_predict_inputs,
+                                  predict_case)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
@@ -404,3 +427,122 @@ def test_boot_predict_cases_cover_the_dispatch():
     assert {p["pad"] for p in plans.values()} == {1, 2, 4, 8} and {p["chunks"] for p in plans.values()} == {1, 2, 3}
     assert {(p["pad"], p["pipe"]) for p in plans.values()} >= {(1, False), (2, False), (2, True), (4, False), (4, True),
                                                                (8, False), (8, True)}
+
+
+# ---- group E: txm_mbar_cov ------------------------------------------------------------------------------------------------
+def cov_plan(K, C, na, ns, cus):
+    """txm_mbar_cov's launch: row tiles and column groups (the states plus a row of ones, the observables plus a column of
+    ones), where the ones sit as (tile, index), workgroups per (state, row tile, column group) and their cap, grid-stride
+    turns of the largest state, the target template."""
+    RT, NCG = K // 16 + 1, C // 16 + 1
+    cap = max(1, cus * 8 // (K * NCG * RT))
+    want = cdiv(max(ns), 256)
+    gx = max(1, min(want, cap))
+    return {"RT": RT, "NCG": NCG, "cap": cap, "gx": gx, "capped": want > cap, "turns": cdiv(max(ns), gx * 64),
+            "NA": 1 if na == 1 else 2 if na == 2 else 4 if na <= 4 else 8, "ones_row": (K // 16, K % 16),
+            "ones_col": (C // 16, C % 16)}
+
+
+COV_PATHS = {
+    "K16_C15_na8": {"RT": 2, "NCG": 1, "NA": 8, "ones_row": (1, 0), "ones_col": (0, 15), "capped": False},
+    "K17_C1_na1": {"RT": 2, "NCG": 1, "NA": 1, "ones_row": (1, 1), "capped": False},
+    "K31_C15_na2": {"RT": 2, "NCG": 1, "NA": 2, "ones_row": (1, 15), "ones_col": (0, 15), "capped": False},
+    "K32_C16_na3": {"RT": 3, "NCG": 2, "NA": 4, "ones_row": (2, 0), "ones_col": (1, 0), "capped": False},
+    "K33_C31_na4_pitch37": {"RT": 3, "NCG": 2, "NA": 4, "ones_row": (2, 1), "ones_col": (1, 15), "capped": False},
+    "K48_C32_na5": {"RT": 4, "NCG": 3, "NA": 8, "ones_row": (3, 0), "ones_col": (2, 0), "capped": False},
+    "K64_C17_na8_block_cap": {"RT": 5, "NCG": 2, "NA": 8, "ones_row": (4, 0), "capped": True},
+    "K64_C*_na2_cap_one": {"RT": 5, "NA": 2, "cap": 1, "gx": 1},
+    "K8_C3_na8_block_cap": {"RT": 1, "NCG": 1, "NA": 8, "capped": True},
+    COV_POOR: {"RT": 1, "NCG": 1, "NA": 4, "capped": False},
+}
+COV_BAND, COV_FILL = 4096, 0xA5
+
+
+def cov_raw(eng, case):
+    """(out (n_alpha, 1 + K + C (1 + K)), lnw) of txm_mbar_cov through the C ABI with the case's host-made g, logD and
+    centres.  out and lnw start as NaN; the workspace is txm_mbar_cov_ws_bytes long plus a band of COV_BAND bytes in the
+    same tensor, which must come back untouched."""
+    from thermoextrap_amd import _lib
+
+    L = _lib.load()
+    a0, ns, us, xs, upiv, g, targets, logD, means, pitch = case
+    K, C, na = len(ns), xs[0].shape[1], len(targets)
+    ud, xd = [dev(u) for u in us], dev_x(xs, pitch)
+    tab, keep, _, C2 = eng._mbar_table(ud, xd)
+    assert C2 == C and means.shape == (na, C) and logD.shape == (sum(ns),)
+    if pitch is not None:
+        assert all(tab[s].ldx_s == pitch for s in range(K) if ns[s] > 1)
+    a0 = np.ascontiguousarray(a0, dtype=np.float64)
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    al = np.ascontiguousarray(targets, dtype=np.float64)
+    ld, mean = dev(logD), dev(means)
+    out = torch.full((na, 1 + K + C * (1 + K)), float("nan"), dtype=torch.float64, device="cuda")
+    lnw = torch.full((na,), float("nan"), dtype=torch.float64, device="cuda")
+    nbytes = L.txm_mbar_cov_ws_bytes(K, C, na)
+    assert nbytes > 0
+    ws = torch.full((nbytes + COV_BAND,), COV_FILL, dtype=torch.uint8, device="cuda")
+    dp = ct.POINTER(ct.c_double)
+    rc = L.txm_mbar_cov(tab, K, C, float(upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp), eng._ptr(ld),
+                        al.ctypes.data_as(dp), na, eng._ptr(mean), eng._ptr(out), eng._ptr(lnw), eng._ptr(ws), nbytes,
+                        eng._stream())
+    torch.cuda.synchronize()
+    assert rc == 0, _lib.last_error()
+    del keep
+    assert bool((ws[nbytes:] == COV_FILL).all()), "txm_mbar_cov wrote past txm_mbar_cov_ws_bytes"
+    out, lnw = out.cpu().numpy(), lnw.cpu().numpy()
+    assert np.all(np.isfinite(out)) and np.all(np.isfinite(lnw))
+    return out, lnw
+
+
+def cov_worst(out, lnw, ref, ns):
+    na, K = ref.B.shape
+    C = ref.yy.shape[1]
+    rest = out[:, 1 + K:].reshape(na, C, 1 + K)
+    got = {"Q": out[:, 0], "B": out[:, 1:1 + K], "yy": rest[:, :, 0], "b": rest[:, :, 1:]}
+    floor = cov_floor(ref, ns)
+    worst = {key: float(np.max(np.abs(v.astype(LD) - getattr(ref, key)) / (getattr(ref, key + "_bound") + floor[key] / LD(TOL))))
+             for key, v in got.items()}
+    worst["lnw"] = float(np.max(np.abs(lnw.astype(LD) - ref.lnw) / (LD(ref.kappa) * (1 + np.abs(ref.lnw)))))
+    return worst
+
+
+def cov_path(name, case, cus):
+    """The launch plan of a group E case, asserted to be the path the case is named for."""
+    ns, C, na = case[1], case[3][0].shape[1], len(case[6])
+    K = len(ns)
+    plan = cov_plan(K, C, na, ns, cus)
+    for key, v in COV_PATHS[name].items():
+        assert plan[key] == v, (name, key, plan)
+    if "block_cap" in name:
+        assert plan["gx"] == plan["cap"] and plan["turns"] > 4 and max(ns) == plan["cap"] * 256 + 77
+    if "cap_one" in name:
+        assert K * plan["NCG"] * plan["RT"] > cus * 8 and plan["cap"] == 1 and plan["turns"] == cdiv(max(ns), 64) > 1
+    if name in ("K32_C16_na3", "K33_C31_na4_pitch37", "K48_C32_na5", "K64_C17_na8_block_cap", "K64_C*_na2_cap_one"):
+        assert plan["RT"] >= 2 and plan["NCG"] >= 2
+    return plan
+
+
+@pytest.mark.parametrize("name", list(COV_CASES) + [COV_POOR])
+def test_cov_against_long_double(eng, cus, name):
+    case, ref = cov_reference(name, cus)
+    cov_path(name, case, cus)
+    ns = case[1]
+    if name == COV_POOR:
+        assert ref.p_min < 1e-308 and ref.kappa > 2.0
+    else:
+        assert ref.p_min >= 1e-9 and ref.kappa <= 2.0
+    out, lnw = cov_raw(eng, case)
+    show(name, cov_worst(out, lnw, ref, ns))
+    # the structure the maths promises for any g: sum_k N_k B_ak = 1, to the sum of the B bounds
+    N = np.asarray(ns, dtype=LD)
+    assert np.all(np.abs(out[:, 1:1 + len(ns)].astype(LD) @ N - 1) <= TOL * (ref.B_bound @ N) + cov_floor(ref, ns)["B"] @ N)
+
+
+@pytest.mark.parametrize("name", ["K64_C17_na8_block_cap", "K64_C*_na2_cap_one"])
+def test_cov_capped_calls_stay_in_their_workspace_and_repeat_their_bits(eng, cus, name):
+    """Where K * cap * NCG * RT partial tiles are most: the band behind the workspace is untouched (cov_raw) and, no
+    atomics being used, two calls give equal bits."""
+    case, _ = cov_reference(name, cus)
+    cov_path(name, case, cus)
+    a, b = cov_raw(eng, case), cov_raw(eng, case)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])

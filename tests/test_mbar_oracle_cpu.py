@@ -1,5 +1,5 @@
-"""The long-double references of oracle/mbar_oracle.py pinned to mpmath at 50 digits, and the input generators of
-tests/test_mbar_kernels_gpu.py checked without a GPU.
+"""The long-double references of oracle/mbar_oracle.py (eval_sums, predict, cov_sums) pinned to mpmath at 50 digits, and
+the input generators of tests/test_mbar_kernels_gpu.py checked without a GPU.
 
 The mpmath side is scalar loops straight from the definitions (no maximum is subtracted: mpmath's exponent range has no
 end).  The agreement demanded is the one tests/test_tail_oracle_cpu.py demands of tail_oracle.py: a few long-double
@@ -12,6 +12,11 @@ can show, on the CPU, what the GPU tolerances assume: in every ordinary case no 
 is active: the floor of the bound matters in the poor-overlap case alone) and no kappa_n is above 2; and the poor-overlap
 case really has p below 1e-308, which float64 flushes.  Sizes that depend on the device (a state large enough for a grid
 cap to bind) are functions of the number of compute units; here they are taken at 256.
+
+The fifth table, COV_CASES, feeds group E of the GPU module (txm_mbar_cov).  No device kernel supplies an input there:
+logD is the long-double logD at the case's g rounded once to float64, the centres are mo.predict's at that logD.
+``cov_floor`` is the absolute floor of group E (derived in the GPU module's header); here it is shown to be negligible
+in every ordinary case and to be the larger part of a bound in the poor-overlap case.
 """
 
 import mpmath as mp
@@ -222,6 +227,73 @@ def boot_predict_case(name):
     return a0, ns, us, xs, upiv, gref, boot_g(gref, BOOT_NREP, seed=4500 + K + C), targets_for(a0, na)
 
 
+# group E (txm_mbar_cov): name -> (alpha0 step, ns(cus), C or C(cus), n_alpha, row pitch or None)
+def cov_cap(K, C, cus):
+    """txm_mbar_cov's workgroups per (state, row tile, column group): about cus * 8 in all."""
+    return max(1, cus * 8 // (K * (C // 16 + 1) * (K // 16 + 1)))
+
+
+def cov_cap_one_C(cus):
+    """The smallest C = 4 mod 16 at which 64 states (RT = 5) have K * NCG * RT > cus * 8: 100 on 256 compute units."""
+    return 16 * (cus * 8 // (64 * 5)) + 4
+
+
+def _cov64_ns(big):
+    ns = [20 + 3 * k for k in range(64)]
+    ns[0], ns[5] = 1, big
+    return ns
+
+
+COV_CASES = {
+    "K16_C15_na8": (0.02, lambda cus: _boot_ns(16, [257, 1, 63]), 15, 8, None),
+    "K17_C1_na1": (0.02, lambda cus: _lds64_ns(17), 1, 1, None),
+    "K31_C15_na2": (0.02, lambda cus: _boot_ns(31, [1, 257]), 15, 2, None),
+    "K32_C16_na3": (0.02, lambda cus: _boot_ns(32, [63, 64, 65]), 16, 3, None),
+    "K33_C31_na4_pitch37": (0.01, lambda cus: _boot_ns(33, [1, 63, 64, 65, 257]), 31, 4, 37),
+    "K48_C32_na5": (0.01, lambda cus: _boot_ns(48, [257, 1]), 32, 5, None),
+    "K64_C17_na8_block_cap": (0.01, lambda cus: _cov64_ns(cov_cap(64, 17, cus) * 256 + 77), 17, 8, None),
+    "K64_C*_na2_cap_one": (0.01, lambda cus: _cov64_ns(65), cov_cap_one_C, 2, None),
+    "K8_C3_na8_block_cap": (0.1, lambda cus: [1, 63, cov_cap(8, 3, cus) * 256 + 77, 64, 65, 255, 257, 300], 3, 8, None),
+}
+COV_POOR = "poor_overlap_K2_C3"
+COV_TINY = LD(2.0 ** -1022)
+_cov_cache = {}
+
+
+def cov_case(name, cus=CUS):
+    """(a0, ns, us, xs, upiv, g, targets, logD, means, pitch) of a group E case; logD and means are made on the host."""
+    if name == COV_POOR:
+        a0, us, xs, upiv, g, targets = poor_overlap_predict_inputs(3)
+        ns, pitch = [len(u) for u in us], None
+    else:
+        d, nsf, C, na, pitch = COV_CASES[name]
+        ns, C = nsf(cus), (C(cus) if callable(C) else C)
+        a0 = steps(len(ns), d)
+        us, xs, upiv, g = eval_inputs(a0, ns, seed=5000 + len(ns) * 8 + na, C=C)
+        targets = targets_for(a0, na)
+    logD = np.ascontiguousarray(mo.eval_sums(us, a0, g, upiv).logD, dtype=np.float64)
+    means = np.ascontiguousarray(mo.predict(us, xs, a0, upiv, targets, logD=logD).avg)
+    return a0, ns, us, xs, upiv, g, targets, logD, means, pitch
+
+
+def cov_reference(name, cus=CUS):
+    """(cov_case(name), mo.cov_sums of it), once per process: the tests that share it leave it unchanged."""
+    if (name, cus) not in _cov_cache:
+        case = cov_case(name, cus)
+        a0, ns, us, xs, upiv, g, targets, logD, means, _ = case
+        _cov_cache[name, cus] = (case, mo.cov_sums(us, xs, a0, g, upiv, targets, means, logD))
+    return _cov_cache[name, cus]
+
+
+def cov_floor(ref, ns):
+    """The absolute floor of every entry of Q, B, yy, b (long double; derivation: tests/test_mbar_kernels_gpu.py): a
+    sample's product below 2^-1022 is lost before the division by N_k sum_n v_an, resp. (sum_n v_an)^2."""
+    N, Nk = LD(sum(ns)), mo._ld(ns)
+    q = COV_TINY * N / ref.den ** 2
+    return {"Q": q, "B": COV_TINY * N / (ref.den[:, None] * Nk[None, :]), "yy": np.broadcast_to(q[:, None], ref.yy.shape),
+            "b": COV_TINY * ref.dabs[:, :, None] / (ref.den[:, None, None] * Nk[None, None, :])}
+
+
 # ---------------------------------------------------------------------------
 # the pin to mpmath
 # ---------------------------------------------------------------------------
@@ -301,6 +373,67 @@ def _pin_problem(a0, us, xs, upiv, g, counts, targets):
     return ev
 
 
+def mp_cov(us, xs, a0, g, upiv, targets, means, logD):
+    """Per target (Q, B, yy, b, lnw) and the kappa-weighted bounds of the first four, in mpmath from the definitions."""
+    K, C = len(a0), xs[0].shape[1]
+    ut = [F(float(v)) - F(upiv) for u in us for v in u]
+    x = [[F(float(v)) for v in row] for xv in xs for row in xv]
+    ld = [F(float(v)) for v in logD]
+    Nk = [F(len(u)) for u in us]
+    amax = max(abs(F(float(a))) for a in targets)
+    kap = [1 + max(max(abs(F(float(gk))) + abs(F(float(ak)) * t) for gk, ak in zip(g, a0)), amax * abs(t) + abs(l)) / 64
+           for t, l in zip(ut, ld)]
+    W = []
+    for t in ut:
+        e = [mp.exp(F(float(gk)) - F(float(ak)) * t) for gk, ak in zip(g, a0)]
+        D = mp.fsum(e)
+        W.append([v / D / n for v, n in zip(e, Nk)])
+    out = []
+    for i, a in enumerate(targets):
+        v = [mp.exp(-F(float(a)) * t - l) for t, l in zip(ut, ld)]
+        den = mp.fsum(v)
+        wa = [vn / den for vn in v]
+        d = [[xn[c] - F(float(means[i][c])) for c in range(C)] for xn in x]
+        val = {"Q": mp.fsum(w * w for w in wa), "B": [mp.fsum(Wn[k] * w for Wn, w in zip(W, wa)) for k in range(K)],
+               "yy": [mp.fsum((w * dn[c]) ** 2 for w, dn in zip(wa, d)) for c in range(C)],
+               "b": [[mp.fsum(Wn[k] * w * dn[c] for Wn, w, dn in zip(W, wa, d)) for k in range(K)] for c in range(C)],
+               "lnw": mp.log(den)}
+        bnd = {"Q": mp.fsum(kn * w * w for kn, w in zip(kap, wa)),
+               "B": [mp.fsum(kn * Wn[k] * w for kn, Wn, w in zip(kap, W, wa)) for k in range(K)],
+               "yy": [mp.fsum(kn * (w * dn[c]) ** 2 for kn, w, dn in zip(kap, wa, d)) for c in range(C)],
+               "b": [[mp.fsum(kn * Wn[k] * w * abs(dn[c]) for kn, Wn, w, dn in zip(kap, W, wa, d)) for k in range(K)]
+                     for c in range(C)]}
+        out.append((val, bnd))
+    return out, kap
+
+
+def _pin_cov(a0, us, xs, upiv, g, targets):
+    """mo.cov_sums against mp_cov at the host-made logD and centres of a group E case."""
+    logD = np.asarray(mo.eval_sums(us, a0, g, upiv).logD, dtype=np.float64)
+    means = mo.predict(us, xs, a0, upiv, targets, logD=logD).avg
+    got = mo.cov_sums(us, xs, a0, g, upiv, targets, means, logD)
+    want, kap = mp_cov(us, xs, a0, g, upiv, targets, means, logD)
+    lim, rel = F(PIN), F(1e-15)
+    def q(v):
+        return F(np.format_float_scientific(LD(v), precision=24, unique=False))
+
+    assert np.allclose(got.kappa_n, [float(v) for v in kap], rtol=1e-15, atol=0) and got.kappa == got.kappa_n.max()
+    K, C = len(a0), xs[0].shape[1]
+    for i, (val, bnd) in enumerate(want):
+        pairs = [("Q", got.Q[i], got.Q_bound[i], val["Q"], bnd["Q"])]
+        pairs += [(("B", k), got.B[i, k], got.B_bound[i, k], val["B"][k], bnd["B"][k]) for k in range(K)]
+        pairs += [(("yy", c), got.yy[i, c], got.yy_bound[i, c], val["yy"][c], bnd["yy"][c]) for c in range(C)]
+        pairs += [(("b", c, k), got.b[i, c, k], got.b_bound[i, c, k], val["b"][c][k], bnd["b"][c][k])
+                  for c in range(C) for k in range(K)]
+        for key, v, vb, w, wb in pairs:
+            assert abs(q(v) - w) <= lim * wb, (i, key)
+            assert abs(q(vb) - wb) <= rel * wb, (i, key)
+        assert abs(q(got.lnw[i]) - val["lnw"]) <= lim * F(got.kappa) * (1 + abs(val["lnw"])), (i, "lnw")
+        shift = q((-LD(targets[i]) * mo.pooled_ut(us, upiv) - mo._ld(logD)).max())      # den is sum_n v_an over its largest term
+        assert abs(q(got.den[i]) - mp.exp(val["lnw"] - shift)) <= rel * q(got.den[i]) and got.den[i] >= 1
+    return got
+
+
 def test_long_double_is_80_bit():
     assert np.finfo(LD).eps < 1.1e-19
 
@@ -330,6 +463,21 @@ def test_poor_overlap_oracle_vs_mpmath():
     xs = gauss_xs(us, 2, np.random.default_rng(5), mu=100.0)
     ev = _pin_problem(a0, us, xs, upiv, g, None, np.array([0.1, 10.0, 3.0]))
     assert ev.p_min < 1e-308
+
+
+def test_cov_oracle_vs_mpmath():
+    """An ordinary problem with state rows in a second tile of 16 (K = 17, 3 to 5 samples per state)."""
+    a0, ns = steps(17, 0.02), [3 + k % 3 for k in range(17)]
+    us, xs, upiv, g = eval_inputs(a0, ns, seed=517, C=2)
+    got = _pin_cov(a0, us, xs, upiv, g, targets_for(a0, 3))
+    assert got.p_min >= 1e-9 and got.kappa <= 2.0
+
+
+def test_cov_oracle_vs_mpmath_poor_overlap():
+    a0, us, _, upiv, g = poor_overlap_inputs(n=30)
+    xs = gauss_xs(us, 2, np.random.default_rng(6), mu=100.0)
+    got = _pin_cov(a0, us, xs, upiv, g, POOR_TARGETS)
+    assert got.p_min < 1e-308 and got.kappa > 2.0
 
 
 # ---------------------------------------------------------------------------
@@ -396,3 +544,54 @@ def test_poor_overlap_case_underflows_float64():
     ut = mo.pooled_ut(us, upiv)
     p1_in_state0 = np.exp(mo.exponents(a0, g, ut)[1, :K0] - ev.logD[:K0])
     assert float(p1_in_state0.max()) < 1e-308 and ev.kappa.max() > 2.0
+
+
+# ---- group E: txm_mbar_cov ------------------------------------------------------------------------------------------------
+def test_cov_cases_hold_the_sizes_and_shapes_they_are_named_for():
+    sizes = set()
+    for name, (d, nsf, C, na, pitch) in COV_CASES.items():
+        ns, C = nsf(CUS), (C(CUS) if callable(C) else C)
+        sizes |= set(ns)
+        K = len(ns)
+        assert name.startswith(f"K{K}_") and f"_na{na}" in name and (f"_C{C}_" in name or "_C*_" in name)
+        assert (pitch is None) == ("pitch" not in name) and (pitch is None or pitch > C)
+        if K == 64:
+            assert 6500 <= sum(ns) - max(ns) <= 7500                          # the reference stays near a second
+    assert {1, 63, 64, 65, 257} <= sizes
+    assert cov_cap_one_C(256) == 100 and 64 * 7 * 5 > 256 * 8 >= 64 * 6 * 5 and cov_cap(64, 100, 256) == 1
+    assert cov_cap(64, 17, 256) == 3 and cov_cap(8, 3, 256) == 256
+
+
+@pytest.mark.parametrize("name", list(COV_CASES))
+def test_cov_case_inputs_are_ordinary(name):
+    """What group E's tolerance assumes, from the reference alone; and that its floor is nothing here."""
+    (a0, ns, us, xs, upiv, g, targets, logD, means, _), ref = cov_reference(name)
+    assert [len(u) for u in us] == ns and means.shape == (len(targets), xs[0].shape[1]) and logD.shape == (sum(ns),)
+    off = g - ti_g(us, a0, upiv)
+    assert abs(off).max() > 0.05 and np.ptp(off) > 0.05                      # not a solution, not a constant off the start
+    assert ref.p_min >= 1e-9, ref.p_min
+    assert ref.kappa <= 2.0, ref.kappa
+    floor = cov_floor(ref, ns)
+    for key in ("Q", "B", "yy", "b"):
+        bnd = getattr(ref, key + "_bound")
+        assert np.all(bnd > 0) and np.all(floor[key] <= LD(1e-250) * 1e-12 * bnd), key
+
+
+@pytest.mark.parametrize("name", list(COV_CASES) + [COV_POOR])
+def test_cov_reference_weights_sum_to_one(name):
+    """sum_k N_k B_ak = sum_n W_na sum_k p_kn = 1 for any g: a softmax sums to one."""
+    (a0, ns, *_), ref = cov_reference(name)
+    one = ref.B @ mo._ld(ns)
+    print(f"\n{name}: sum_k N_k B_ak - 1: {float(np.abs(one - 1).max()):.1e}; p_min {ref.p_min:.1e}, kappa {ref.kappa:.3f}")
+    assert np.all(np.abs(one - 1) <= len(ns) * 64 * mo.EPS_LD)
+
+
+def test_cov_poor_overlap_case_needs_the_floor():
+    """The one case where the floor is the larger part of a bound: p_kn underflows float64, and so do products p_kn v_an."""
+    (a0, ns, us, xs, upiv, g, targets, logD, means, _), ref = cov_reference(COV_POOR)
+    assert ref.p_min < 1e-308 and ref.kappa > 2.0
+    floor = cov_floor(ref, ns)
+    assert np.any(floor["B"] > 1e-12 * ref.B_bound) and np.any(floor["b"] > 1e-12 * ref.b_bound)
+    assert np.all(floor["Q"] < 1e-200 * ref.Q_bound) and np.all(floor["yy"] < 1e-200 * ref.yy_bound)
+    big = floor["B"] <= 1e-200 * ref.B_bound                                 # and entries the floor does not touch
+    assert big.any() and np.all(ref.B[big] > 0)
