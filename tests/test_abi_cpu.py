@@ -55,6 +55,40 @@ def test_abi_version(lib):
     assert lib.txm_sampler_stream_version() == sv == _lib.SAMPLER_STREAM_VERSION == golden["stream_version"] == 3
 
 
+# the entry points whose FULL argument list INTEGRATION.md quotes, as a C declaration or as `name(arg, ...)` in the text
+# (its Python binding examples, `L.txm_...(...)`, span lines and pass expressions: they are not parsed)
+DOC_SIGNATURES = ["txm_mbar_cov_ws_bytes", "txm_mbar_cov", "txm_influence_cov_ws_bytes", "txm_influence_cov",
+                  "txm_resample_kernel", "txm_resample_operands_aligned", "txm_resample_vals_ws_bytes_opts",
+                  "txm_resample_batched_path"]
+
+
+def _quoted_arities(text, name):
+    """The argument counts of every `name(...)` in text that is not a call through the binding (`L.name(...)`)."""
+    out = []
+    for m in re.finditer(rf"(?<![\w.]){name}\(", text):
+        depth, i, commas = 1, m.end(), 0
+        while depth:
+            ch = text[i]
+            depth += (ch == "(") - (ch == ")")
+            commas += ch == "," and depth == 1
+            i += 1
+        out.append(commas + 1 if text[m.end():i - 1].strip() else 0)
+    return out
+
+
+def test_integration_doc_quotes_the_bound_arities():
+    """INTEGRATION.md is what a binder is written from: every signature it quotes in full has the number of arguments the
+    header declares and _lib.SIGNATURES binds (it once gave txm_resample_operands_aligned a sixth, `order`)."""
+    from thermoextrap_amd import _lib
+
+    text = (ROOT / "INTEGRATION.md").read_text()
+    for name in DOC_SIGNATURES:
+        got = _quoted_arities(text, name)
+        assert got, f"INTEGRATION.md no longer quotes {name}"
+        assert set(got) == {len(_lib.SIGNATURES[name][1])}, (name, got)
+    assert _quoted_arities("f(a, g(b, c), d) and L.f(x) and f()", "f") == [3, 0]
+
+
 def test_struct_layouts_match_the_header():
     """The ctypes mirrors of the header's host structs: field order, offsets and sizes (ABI 2: txm_sampler_spec.rep0,
     txm_resample_opts)."""

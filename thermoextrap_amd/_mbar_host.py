@@ -1,0 +1,255 @@
+"""The host half of MBAR: everything between two device passes that is numpy alone.
+
+The damped Newton solvers (one problem, or R bootstrap replicates at once) take their device evaluation as an argument;
+the rest is the algebra of the asymptotic covariance (Shirts & Chodera 2008, eq. 8 and appendix D): Theta =
+W^T (I_N - W N W^T)^+ W over the columns W_nk = p_kn / N_k of the sampled states and W_na of the targets needs only the
+Gram matrix G = W^T W.  Nothing here loads the library or touches a tensor; engine.py imports every name.
+"""
+
+from __future__ import annotations
+
+from typing import TYPE_CHECKING
+
+import numpy as np
+
+from . import _lib
+
+if TYPE_CHECKING:
+    from .engine import MbarSolution
+
+
+_MBAR_MAX_STEP = 50.0   # cap (in units of f) on the part of a step along directions without curvature
+
+
+def mbar_newton(evaluate, N, b, *, f0=None, tol: float = 1e-12, max_iter: int = 100):
+    """Damped Newton on the convex MBAR objective  F(f) = sum_n logD_n(f) - sum_k N_k f_k  over the K - 1 free energies
+    f_1.. (gauge f_0 = 0).  ``evaluate(g) -> (S, H, obj)`` is one pass over the pooled samples at the log-weights
+    g = b + f + c (b_k = ln N_k - alpha0_k upiv; the constant c = -max_k(b + f) keeps them near 0): S_k = sum_n p_kn,
+    H_jk = sum_n p_jn p_kn (full symmetric) and obj = sum_n logD_n + c N_tot.  The gradient is S - N and the Hessian
+    diag(S) - H.
+
+    The reduced Hessian is eigen-decomposed: directions with curvature above 1e-12 of the largest get the Newton step;
+    the rest (states without overlap) get the gradient over that floor, capped at 50 units of f, so a singular Hessian
+    still gives a finite step.  The step is halved until the objective decreases (Armijo), or -- once the change is
+    below the objective's rounding -- until the gradient does.  Converged: max_k |S_k - N_k| / N_k <= tol.
+
+    Returns (f, g, iterations, evaluations, gradient) with g the log-weights of the last evaluation (the returned f)."""
+    N = np.asarray(N, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    K = len(N)
+    Ntot = float(N.sum())
+    f = np.zeros(K) if f0 is None else np.asarray(f0, dtype=np.float64) - float(f0[0])
+    eps = np.finfo(np.float64).eps
+
+    def point(f):
+        g = b + f
+        c = -float(g.max())
+        g = g + c
+        S, H, obj = evaluate(g)
+        S, H = np.asarray(S, dtype=np.float64), np.asarray(H, dtype=np.float64)
+        F = obj - c * Ntot - float(N @ f)
+        rnd = 64 * eps * (abs(obj) + abs(c) * Ntot + float(N @ np.abs(f)) + Ntot)
+        return S, H, F, rnd, g
+
+    S, H, F, rnd, g = point(f)
+    n_eval = 1
+    for it in range(max_iter + 1):
+        grad = S - N
+        err = float(np.max(np.abs(grad) / N))
+        if not np.isfinite(err):
+            raise _lib.TxmError(f"MBAR solve: the gradient is not finite (max |S_k - N_k| / N_k = {err})")
+        if err <= tol:
+            return f, g, it, n_eval, err
+        if it == max_iter:
+            break
+        Hr = (np.diag(S) - H)[1:, 1:]
+        gr = grad[1:]
+        lam, V = np.linalg.eigh(0.5 * (Hr + Hr.T))
+        floor = 1e-12 * max(float(lam.max()), float(N.min()))
+        good = lam > floor
+        proj = V.T @ gr
+        step = -(V[:, good] @ (proj[good] / lam[good]))
+        if not good.all():
+            flat = -(V[:, ~good] @ (proj[~good] / floor))
+            big = float(np.max(np.abs(flat)))
+            if big > _MBAR_MAX_STEP:
+                flat *= _MBAR_MAX_STEP / big
+            step = step + flat
+        slope = float(gr @ step)
+        t = 1.0
+        while True:
+            fn = f.copy()
+            fn[1:] += t * step
+            Sn, Hn, Fn, rn, gn = point(fn)
+            n_eval += 1
+            errn = float(np.max(np.abs(Sn - N) / N))
+            if Fn <= F + 1e-4 * t * slope or (abs(Fn - F) <= max(rnd, rn) and errn < err):
+                break
+            t *= 0.5
+            if t < 1e-10:
+                raise _lib.TxmError(f"MBAR solve: the line search found no decrease at iteration {it}; "
+                                    f"max |S_k - N_k| / N_k = {err:.3e}")
+        f, S, H, F, rnd, g = fn, Sn, Hn, Fn, rn, gn
+    raise _lib.TxmError(f"MBAR solve did not converge in {max_iter} Newton iterations: "
+                        f"max |S_k - N_k| / N_k = {err:.3e} > tol {tol:.1e}")
+
+
+def mbar_newton_batched(evaluate, N, b, f0, *, tol: float = 1e-12, max_iter: int = 100):
+    """``mbar_newton`` for R replicates at once: the same damped Newton per replicate (eigen-floor, step halving,
+    convergence max_k |S_k - N_k| / N_k <= tol), one batched evaluation per trial point.
+
+    ``evaluate(g, active) -> (S, H, obj)``: ``g`` is the full (R, K) array of log-weights (row r = b + f_r + c_r, the
+    constant c_r = -max_k keeps them near 0), ``active`` the int array of the rows wanted; S (A, K), H (A, K, K) full
+    symmetric and obj (A,) are those rows' weighted sums (S_k = sum_n c_n p_kn, ...), in the order of ``active``.
+    A converged replicate is frozen: its f never changes again and it is absent from every later ``active``.
+    ``f0``: (R, K), one start per replicate (``np.tile(f, (R, 1))`` for a common one).
+
+    Returns (f (R, K), g (R, K) -- each row's log-weights at its f --, iterations (R,), evaluations, gradient (R,));
+    ``evaluations`` counts calls of ``evaluate``."""
+    N = np.asarray(N, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    K = len(N)
+    Ntot = float(N.sum())
+    f = np.array(f0, dtype=np.float64)
+    if f.ndim != 2 or f.shape[1] != K:
+        raise ValueError(f"f0 must be (R, {K})")
+    R = f.shape[0]
+    f -= f[:, :1]
+    eps = np.finfo(np.float64).eps
+    g = np.zeros((R, K))          # what the device is shown (trial rows included)
+    g_acc = np.zeros((R, K))      # each row's log-weights at its accepted f
+    n_eval = 0
+
+    def point(fa, rows):
+        nonlocal n_eval
+        ga = b[None, :] + fa
+        c = -ga.max(axis=1)
+        g[rows] = ga + c[:, None]
+        S, H, obj = evaluate(g, rows.copy())
+        n_eval += 1
+        S, H, obj = np.asarray(S, dtype=np.float64), np.asarray(H, dtype=np.float64), np.asarray(obj, dtype=np.float64)
+        F = obj - c * Ntot - fa @ N
+        rnd = 64 * eps * (np.abs(obj) + np.abs(c) * Ntot + np.abs(fa) @ N + Ntot)
+        return S, H, F, rnd
+
+    rows = np.arange(R)
+    S, H, F, rnd = point(f, rows)
+    g_acc[:] = g
+    err = np.max(np.abs(S - N) / N, axis=1)
+    its = np.zeros(R, dtype=np.int64)
+    done = np.zeros(R, dtype=bool)
+    for it in range(max_iter + 1):
+        if not np.all(np.isfinite(err)):
+            r = int(np.flatnonzero(~np.isfinite(err))[0])
+            raise _lib.TxmError(f"MBAR bootstrap solve: the gradient of replicate {r} is not finite")
+        done |= err <= tol
+        rows = np.flatnonzero(~done)
+        if len(rows) == 0:
+            return f, g_acc, its, n_eval, err
+        if it == max_iter:
+            break
+        steps = np.zeros((R, K - 1))
+        slopes = np.zeros(R)
+        for r in rows:
+            grad = S[r] - N
+            Hr = (np.diag(S[r]) - H[r])[1:, 1:]
+            gr = grad[1:]
+            lam, V = np.linalg.eigh(0.5 * (Hr + Hr.T))
+            floor = 1e-12 * max(float(lam.max()), float(N.min()))
+            good = lam > floor
+            proj = V.T @ gr
+            step = -(V[:, good] @ (proj[good] / lam[good]))
+            if not good.all():
+                flat = -(V[:, ~good] @ (proj[~good] / floor))
+                big = float(np.max(np.abs(flat)))
+                if big > _MBAR_MAX_STEP:
+                    flat *= _MBAR_MAX_STEP / big
+                step = step + flat
+            steps[r] = step
+            slopes[r] = float(gr @ step)
+        t = np.ones(R)
+        pending = rows
+        while len(pending):
+            fn = f[pending].copy()
+            fn[:, 1:] += t[pending, None] * steps[pending]
+            Sn, Hn, Fn, rn = point(fn, pending)
+            errn = np.max(np.abs(Sn - N) / N, axis=1)
+            ok = (Fn <= F[pending] + 1e-4 * t[pending] * slopes[pending]) | \
+                ((np.abs(Fn - F[pending]) <= np.maximum(rnd[pending], rn)) & (errn < err[pending]))
+            acc = pending[ok]
+            f[acc], S[acc], H[acc], F[acc], rnd[acc], err[acc] = fn[ok], Sn[ok], Hn[ok], Fn[ok], rn[ok], errn[ok]
+            g_acc[acc] = g[acc]
+            its[acc] += 1
+            pending = pending[~ok]
+            t[pending] *= 0.5
+            if len(pending) and t[pending].min() < 1e-10:
+                r = int(pending[np.argmin(t[pending])])
+                raise _lib.TxmError(f"MBAR bootstrap solve: the line search of replicate {r} found no decrease at "
+                                    f"iteration {it}; max |S_k - N_k| / N_k = {err[r]:.3e}")
+    worst = int(rows[np.argmax(err[rows])])
+    raise _lib.TxmError(f"MBAR bootstrap solve did not converge in {max_iter} Newton iterations: {len(rows)} of {R} "
+                        f"replicates left, the worst is replicate {worst} with max |S_k - N_k| / N_k = "
+                        f"{err[worst]:.3e} > tol {tol:.1e}")
+
+
+_MBAR_PINV_CUT = 1e-12   # eigenvalues of I - sqrt(N) G sqrt(N) below this fraction of the largest are its null space
+
+
+def mbar_solution_g(ns, alpha0, sol: MbarSolution):
+    """The shifted log-weights the solve's last evaluation ran at (``mbar_newton``'s g = b + f - max(b + f)) and the
+    shift c = -max(b + f): ``sol.logD`` is ln sum_k N_k e^{f_k - alpha0_k u_n} + c."""
+    a0 = np.asarray(alpha0, dtype=np.float64).reshape(-1)
+    g = np.log(np.asarray(ns, dtype=np.float64)) - a0 * sol.upiv + np.asarray(sol.f, dtype=np.float64)
+    c = -float(g.max())
+    return g + c, c
+
+
+def _sym_pinv(A: np.ndarray) -> np.ndarray:
+    lam, V = np.linalg.eigh(0.5 * (A + A.T))
+    keep = lam > _MBAR_PINV_CUT * max(float(np.max(np.abs(lam))), 1.0)
+    return (V[:, keep] / lam[keep]) @ V[:, keep].T
+
+
+def mbar_theta(G, N) -> np.ndarray:
+    """Theta = W^T (I - W N W^T)^+ W from the Gram matrix G = W^T W = V L V^T alone: V S (I - S V^T N V S)^+ S V^T with
+    S = L^{1/2} (negative eigenvalues of G, rounding, clipped to 0).  N: the sample count of every column, 0 for the
+    columns that were not sampled (targets)."""
+    G = np.asarray(G, dtype=np.float64)
+    N = np.asarray(N, dtype=np.float64).reshape(-1)
+    if G.shape != (len(N), len(N)):
+        raise ValueError("G must be square with one row per entry of N")
+    lam, V = np.linalg.eigh(0.5 * (G + G.T))
+    S = np.sqrt(np.clip(lam, 0.0, None))
+    VS = V * S
+    A = np.eye(len(N)) - VS.T @ (N[:, None] * VS)
+    return VS @ _sym_pinv(A) @ VS.T
+
+
+def mbar_reduced_pinv(Gs, N) -> np.ndarray:
+    """(I_K - sqrt(N) G_s sqrt(N))^+ of the sampled block: singular along sqrt(N) by construction (the rows of the
+    overlap matrix sum to 1), hence a pseudo-inverse.  Taken once per model."""
+    rn = np.sqrt(np.asarray(N, dtype=np.float64).reshape(-1))
+    Gs = np.asarray(Gs, dtype=np.float64)
+    return _sym_pinv(np.eye(len(rn)) - rn[:, None] * Gs * rn[None, :])
+
+
+def mbar_mean_variance(Gs, N, yy, b, *, pinv=None) -> np.ndarray:
+    """var of an MBAR average at a target from the K x K block alone: with y_n = W_na (x_n - <x>_a), the unsampled column
+    y has Theta_yy = yy + (sqrt(N) b)^T (I_K - sqrt(N) G_s sqrt(N))^+ (sqrt(N) b), yy = sum_n y_n^2 and
+    b_k = sum_n W_nk y_n.  ``yy`` (...,) and ``b`` (..., K) broadcast; ``pinv``: ``mbar_reduced_pinv(Gs, N)`` if the
+    caller keeps it."""
+    rn = np.sqrt(np.asarray(N, dtype=np.float64).reshape(-1))
+    P = mbar_reduced_pinv(Gs, N) if pinv is None else pinv
+    rb = np.asarray(b, dtype=np.float64) * rn
+    return np.asarray(yy, dtype=np.float64) + np.einsum("...j,jk,...k->...", rb, P, rb)
+
+
+def mbar_overlap(Gs, N):
+    """The overlap matrix O = G_s diag(N) of the sampled states (rows sum to 1), its eigenvalues in descending order --
+    those of the symmetric sqrt(N) G_s sqrt(N), which is similar to O -- and the scalar 1 - the second largest
+    (1 for a single state)."""
+    Gs = np.asarray(Gs, dtype=np.float64)
+    N = np.asarray(N, dtype=np.float64).reshape(-1)
+    rn = np.sqrt(N)
+    ev = np.linalg.eigvalsh(rn[:, None] * (0.5 * (Gs + Gs.T)) * rn[None, :])[::-1].copy()
+    return Gs * N[None, :], ev, (float(1.0 - ev[1]) if len(ev) > 1 else 1.0)

@@ -17,6 +17,9 @@ import torch
 
 from . import _lib
 from ._lib import ResampleOpts, SamplerSpec, check
+from ._mbar_host import (_MBAR_MAX_STEP, _MBAR_PINV_CUT, _sym_pinv, mbar_mean_variance, mbar_newton,  # noqa: F401
+                         mbar_newton_batched, mbar_overlap, mbar_reduced_pinv, mbar_solution_g, mbar_theta)
+from ._operands import either_layout, resample_pitch_ok, rowmajor_layout  # noqa: F401
 
 F64 = torch.float64
 _last_info: dict[tuple[int, int], torch.Tensor] = {}
@@ -81,36 +84,85 @@ def _check_f64_cuda(t, name):
         raise TypeError(f"{name} must be a float64 CUDA tensor")
 
 
-# ---------------------------------------------------------------------------
-def reduce_vals(x: torch.Tensor, u: torch.Tensor, order: int, w: torch.Tensor | None = None) -> torch.Tensor:
-    """x: (N, C) with either stride(1) == 1 or stride(0) == 1 (a transposed view
-    of a (C, N) array), or (N,).  Returns (C, 2, K) (or (2, K))."""
-    L = _L()
+# The layout rule of an entry point (_operands.py): "either" layout of reduce_vals; "rowmajor" with a pitch >= C;
+# "rowmajor_pitch", the same within TXM_RESAMPLE_PITCH_OK; "tight": always a contiguous array (the batched entry points).
+def _layout(x2, rule):
+    """(copy, ls, lc) of the (N, C) tensor x2 under ``rule``: the one place that reads a tensor's strides to decide that."""
+    N, C = x2.shape
+    s0, s1 = x2.stride()
+    if rule == "either":
+        return either_layout(N, C, s0, s1)
+    return (*rowmajor_layout(N, C, s0, s1, rule == "rowmajor_pitch"), 1)
+
+
+def _place(x2, rule):
+    """x2 (N, C) as the library takes it under ``rule``: (tensor, ls, lc) -- x2 itself, or its contiguous copy."""
+    if rule == "tight":
+        return (x2 if x2.is_contiguous() else x2.contiguous()), x2.shape[1], 1
+    copy, ls, lc = _layout(x2, rule)
+    return (x2.contiguous() if copy else x2), ls, lc
+
+
+def _sample_vector(t, name, N):
+    """u or w of N samples: checked, contiguous."""
+    _check_f64_cuda(t, name)
+    if t.shape != (N,):
+        raise ValueError(f"{name} must have shape ({N},), got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _operands(x, u, w, rule):
+    """(x2, ls, lc, u, w, N, C, squeeze) for the sample-matrix entry points: x (N, C) or (N,) placed by ``rule``, u and
+    w (N,)."""
     _check_f64_cuda(x, "x")
-    _check_f64_cuda(u, "u")
     squeeze = x.dim() == 1
     x2 = x.unsqueeze(1) if squeeze else x
     if x2.dim() != 2:
         raise ValueError("x must be (N,) or (N, C)")
     N, C = x2.shape
-    if u.shape != (N,):
-        raise ValueError(f"u must have shape ({N},), got {tuple(u.shape)}")
-    u = u.contiguous()
+    u = _sample_vector(u, "u", N)
     if w is not None:
-        _check_f64_cuda(w, "w")
-        if w.shape != (N,):
-            raise ValueError("w must have shape (N,)")
-        w = w.contiguous()
-    if C == 1:
-        x2 = x2.contiguous()
-        ls, lc = 1, 1  # a single contiguous series
-    elif x2.stride(1) == 1 and (N == 1 or x2.stride(0) >= C):
-        ls, lc = (x2.stride(0) if N > 1 else C), 1  # (rec, val) row-major, pitch ls
-    elif x2.stride(0) == 1 and (C == 1 or x2.stride(1) >= N):
-        ls, lc = 1, x2.stride(1)  # (val, rec): every column contiguous along samples
-    else:
-        x2 = x2.contiguous()
-        ls, lc = C, 1
+        w = _sample_vector(w, "w", N)
+    x2, ls, lc = _place(x2, rule)
+    return x2, ls, lc, u, w, N, C, squeeze
+
+
+def _eight_per_pass(values):
+    """(i0, chunk) over the targets, 8 per pass over the samples; every chunk a contiguous float64 array."""
+    for i0 in range(0, len(values), 8):
+        yield i0, np.ascontiguousarray(values[i0:i0 + 8])
+
+
+def _info_words(cache):
+    """The 4 int64 words a bootstrap call reports in, one buffer per (device, stream) in ``cache``."""
+    key = (torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)
+    info = cache.get(key)
+    if info is None:
+        info = cache[key] = torch.zeros(4, dtype=torch.int64, device="cuda")
+    return info
+
+
+def _most_that_fit(need, hi, budget, unit=1):
+    """The most of ``hi`` items whose ``need(n)`` bytes (growing with n) fit ``budget``: all of them when they fit or are
+    no more than one group of ``unit``, else whole groups of ``unit`` -- at least one, fitting or not."""
+    if need(hi) <= budget or hi <= unit:
+        return hi
+    lo, top = 1, (hi + unit - 1) // unit
+    while lo < top:
+        mid = (lo + top + 1) // 2
+        if need(min(mid * unit, hi)) <= budget:
+            lo = mid
+        else:
+            top = mid - 1
+    return min(lo * unit, hi)
+
+
+# ---------------------------------------------------------------------------
+def reduce_vals(x: torch.Tensor, u: torch.Tensor, order: int, w: torch.Tensor | None = None) -> torch.Tensor:
+    """x: (N, C) with either stride(1) == 1 or stride(0) == 1 (a transposed view
+    of a (C, N) array), or (N,).  Returns (C, 2, K) (or (2, K))."""
+    L = _L()
+    x2, ls, lc, u, w, N, C, squeeze = _operands(x, u, w, "either")
     out = torch.empty((C, 2, order + 1), dtype=F64, device="cuda")
     nws = L.txm_reduce_vals_ws_bytes(N, C, order)
     ws = workspace(nws)
@@ -121,41 +173,11 @@ def reduce_vals(x: torch.Tensor, u: torch.Tensor, order: int, w: torch.Tensor | 
     return out[0] if squeeze else out
 
 
-def _rowmajor_operands(x, u, w):
-    """(x2, ls, lc, u, w, N, C, squeeze) for the sample-matrix entry points: (N, C) or (N,), either layout of reduce_vals."""
-    _check_f64_cuda(x, "x")
-    _check_f64_cuda(u, "u")
-    squeeze = x.dim() == 1
-    x2 = x.unsqueeze(1) if squeeze else x
-    if x2.dim() != 2:
-        raise ValueError("x must be (N,) or (N, C)")
-    N, C = x2.shape
-    if u.shape != (N,):
-        raise ValueError(f"u must have shape ({N},), got {tuple(u.shape)}")
-    u = u.contiguous()
-    if w is not None:
-        _check_f64_cuda(w, "w")
-        if w.shape != (N,):
-            raise ValueError("w must have shape (N,)")
-        w = w.contiguous()
-    if C == 1:
-        x2 = x2.contiguous()
-        ls, lc = 1, 1
-    elif x2.stride(1) == 1 and (N == 1 or x2.stride(0) >= C):
-        ls, lc = (x2.stride(0) if N > 1 else C), 1
-    elif x2.stride(0) == 1 and (C == 1 or x2.stride(1) >= N):
-        ls, lc = 1, x2.stride(1)
-    else:
-        x2 = x2.contiguous()
-        ls, lc = C, 1
-    return x2, ls, lc, u, w, N, C, squeeze
-
-
 def reduce_pivot(x: torch.Tensor, u: torch.Tensor, w: torch.Tensor | None = None) -> torch.Tensor:
     """The library's pivot estimate {pivot_u, pivot_x[...]} for a (shard of a) sample matrix: (1 + C,) -- strided means
     (txm_reduce_vals_pivot), with ``w`` the weighted estimate reduce_vals itself uses (txm_reduce_vals_pivot_w)."""
     L = _L()
-    x2, ls, lc, u, w, N, C, _ = _rowmajor_operands(x, u, w)
+    x2, ls, lc, u, w, N, C, _ = _operands(x, u, w, "either")
     piv = torch.empty(1 + C, dtype=F64, device="cuda")
     if w is None:
         check(L.txm_reduce_vals_pivot(_ptr(x2), ls, lc, _ptr(u), N, C, _ptr(piv), _stream()), "txm_reduce_vals_pivot")
@@ -169,7 +191,7 @@ def reduce_sums(x: torch.Tensor, u: torch.Tensor, order: int, pivot: torch.Tenso
     """Weight-scaled power sums of the samples about ``pivot``: (C, 2, K) -- sums about one pivot add like the samples
     (txm_reduce_vals_sums): shards of a sample-sharded reduce, chunks of a stream."""
     L = _L()
-    x2, ls, lc, u, w, N, C, _ = _rowmajor_operands(x, u, w)
+    x2, ls, lc, u, w, N, C, _ = _operands(x, u, w, "either")
     _check_f64_cuda(pivot, "pivot")
     pivot = pivot.contiguous()
     if pivot.numel() != 1 + C:
@@ -202,7 +224,7 @@ def push_vals(state: torch.Tensor, x: torch.Tensor, u: torch.Tensor, w: torch.Te
     accumulator) and return it (txm_push_vals)."""
     L = _L()
     _check_f64_cuda(state, "state")
-    x2, ls, lc, u, w, N, C, squeeze = _rowmajor_operands(x, u, w)
+    x2, ls, lc, u, w, N, C, squeeze = _operands(x, u, w, "either")
     st = state.unsqueeze(0) if (squeeze and state.dim() == 2) else state
     if st.dim() != 3 or st.shape[0] != C or st.shape[1] != 2 or not st.is_contiguous():
         raise ValueError(f"state must be a contiguous ({C}, 2, K) tensor, got {tuple(state.shape)}")
@@ -392,17 +414,7 @@ def _slab_size(L, N, C, nrep, order, path, has_y) -> int:
     """Replicates per library call: all of them when the call's workspace fits the budget, else the largest multiple of 128
     that does (at least 128)."""
     need = lambda n: L.txm_resample_vals_ws_bytes_opts(N, C, n, order, path, int(has_y)) + (L.txm_resample_y_ws_bytes(N, C, n) if has_y else 0)  # noqa: E731
-    budget = workspace_budget()
-    if need(nrep) <= budget or nrep <= 128:
-        return nrep
-    lo, hi = 1, (nrep + 127) // 128  # groups of 128; need() grows with n
-    while lo < hi:
-        mid = (lo + hi + 1) // 2
-        if need(min(mid * 128, nrep)) <= budget:
-            lo = mid
-        else:
-            hi = mid - 1
-    return min(lo * 128, nrep)
+    return _most_that_fit(need, nrep, workspace_budget(), unit=128)
 
 
 def _call_path(path) -> int:
@@ -414,12 +426,6 @@ def _call_path(path) -> int:
     return -1
 
 
-def resample_pitch_ok(ld: int, C: int) -> bool:
-    """include/txmom.h TXM_RESAMPLE_PITCH_OK: the row pitch the bootstrap kernels' 32-bit offsets hold; anything else is copied
-    to a tight array -- which for C > 698140 is itself refused by the library."""
-    return 768 * int(ld) + int(C) <= 1 << 29
-
-
 def _table_operands_ok(x2: torch.Tensor, ls: int, C: int, y: torch.Tensor | None) -> bool:
     """txm_resample_kernel's `aligned` for the operands a call will hand the library (the library's own statement of what the
     count-table kernel's DMA needs: txm_resample_operands_aligned).  A second matrix that resample_vals will have to copy
@@ -428,10 +434,9 @@ def _table_operands_ok(x2: torch.Tensor, ls: int, C: int, y: torch.Tensor | None
     yp, ldy = None, 0
     if y is not None:
         y2 = y.unsqueeze(1) if y.dim() == 1 else y
-        if y2.dim() != 2 or y2.stride(1) != 1 or (y2.shape[0] > 1 and (y2.stride(0) < C or not resample_pitch_ok(y2.stride(0), C))):
-            yp, ldy = ct.c_void_p(256), C          # (an address with torch's allocation alignment stands in for the copy's)
-        else:
-            yp, ldy = ct.c_void_p(y2.data_ptr()), max(y2.stride(0) if y2.shape[0] > 1 else C, C)
+        copy, ldy, _ = _layout(y2, "rowmajor_pitch") if y2.dim() == 2 else (True, C, 1)
+        # (an address with torch's allocation alignment stands in for the copy's)
+        yp = ct.c_void_p(256 if copy else y2.data_ptr())
     return L.txm_resample_operands_aligned(ct.c_void_p(x2.data_ptr()), ls, C, yp, ldy) == 1
 
 
@@ -463,32 +468,11 @@ def resample_vals(
     ``y``: a second (N, C) sample matrix; returns ``(states, ymean)`` with ymean (nrep, C) = the per-replicate
     weighted mean of y on the same draw (VolumeDataCallback's <dx/dq>, reference volume.py:121-134)."""
     L = _L()
-    _check_f64_cuda(x, "x")
-    _check_f64_cuda(u, "u")
-    squeeze = x.dim() == 1
-    x2 = x.unsqueeze(1) if squeeze else x
-    if x2.dim() != 2:
-        raise ValueError("x must be (N,) or (N, C)")
-    N, C = x2.shape
     # the key of a caller-held pre-pass block describes the CALLER's tensors; the copies made below are kept with it
     src = tuple(prep_src) if prep_src is not None else (x, u, w, pivot, y)
+    # the kernels want (rec, val) row-major with a row pitch >= C that their 32-bit offsets hold (TXM_RESAMPLE_PITCH_OK)
+    x2, ls, _, u, w, N, C, squeeze = _operands(x, u, w, "rowmajor_pitch")
     src_key = tuple(_tkey(t) for t in src)
-    # the kernels want (rec, val) row-major with a row pitch >= C; anything else (transposed views,
-    # broadcast rows with stride 0, overlapping pitches) is copied
-    # (... and a row pitch beyond what the kernels' 32-bit offsets hold, which the library refuses: TXM_RESAMPLE_PITCH_OK)
-    if not (x2.stride(1) == 1 or C == 1) or (N > 1 and (x2.stride(0) < C or not resample_pitch_ok(x2.stride(0), C))):
-        x2 = x2.contiguous()
-    if C == 1 and x2.stride(1) != 1:
-        x2 = x2.contiguous()
-    ls = max(x2.stride(0) if N > 1 else C, C)
-    if u.shape != (N,):
-        raise ValueError(f"u must have shape ({N},), got {tuple(u.shape)}")
-    u = u.contiguous()
-    if w is not None:
-        _check_f64_cuda(w, "w")
-        if w.shape != (N,):
-            raise ValueError(f"w must have shape ({N},), got {tuple(w.shape)}")
-        w = w.contiguous()
     if (freq is None) == (sampler is None):
         raise ValueError("give exactly one of freq= or sampler=")
     if freq is not None:
@@ -541,10 +525,9 @@ def resample_vals(
         y2 = y.unsqueeze(1) if y.dim() == 1 else y
         if tuple(y2.shape) != (N, C):
             raise ValueError(f"y must have the shape of x, ({N}, {C}); got {tuple(y2.shape)}")
-        if y2.stride(1) != 1 or (N > 1 and (y2.stride(0) < C or not resample_pitch_ok(y2.stride(0), C))):
-            y2 = y2.contiguous()
+        y2, ldy, _ = _place(y2, "rowmajor_pitch")
         ymean = torch.empty((nrep, C), dtype=F64, device="cuda")
-        opts.y, opts.ldy_s, opts.out_y = y2.data_ptr(), max(y2.stride(0) if N > 1 else C, C), ymean.data_ptr()
+        opts.y, opts.ldy_s, opts.out_y = y2.data_ptr(), ldy, ymean.data_ptr()
     key = None
     if prep is not None and freq is None:
         if (kern & 0xFF) != _PATHS["fp64"]:
@@ -556,17 +539,15 @@ def resample_vals(
             key = (src_key, N, C, order, kern)
             kept = prep.lookup(key)
             if kept is not None:  # same caller tensors, unedited: the operands of the call that filled the block
-                x2, u, w, pivot, y2 = kept
-                ls = max(x2.stride(0) if N > 1 else C, C)
+                x2, u, w, pivot, y2 = kept   # (placed already: the rule passes them through and gives their pitch)
+                x2, ls, _ = _place(x2, "rowmajor_pitch")
                 if y2 is not None:
-                    opts.y, opts.ldy_s = y2.data_ptr(), max(y2.stride(0) if N > 1 else C, C)
+                    y2, opts.ldy_s, _ = _place(y2, "rowmajor_pitch")
+                    opts.y = y2.data_ptr()
             buf, valid = prep.bind(key, L.txm_resample_prep_bytes(N, C, nrep, order))
             opts.prep, opts.prep_bytes, opts.prep_valid = buf.data_ptr(), buf.numel(), int(valid)
-    if info is None:  # the words resample_info() reads back: one block per (device, stream)
-        ikey = (torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)
-        info = _last_info.get(ikey)
-        if info is None:
-            info = _last_info[ikey] = torch.zeros(4, dtype=torch.int64, device="cuda")
+    if info is None:  # the words resample_info() reads back
+        info = _info_words(_last_info)
     if not (info.is_cuda and info.dtype == torch.int64 and info.numel() >= 4 and info.is_contiguous()):
         raise TypeError("info must be a contiguous int64 CUDA tensor with >= 4 elements")
     opts.info = info.data_ptr()
@@ -596,24 +577,12 @@ def _state_table(xs, us, ws):
         x = x.unsqueeze(1) if x.dim() == 1 else x
         if x.dim() != 2:
             raise ValueError("every x must be (N,) or (N, C)")
-        x2.append(x if x.is_contiguous() else x.contiguous())
+        x2.append(_place(x, "tight")[0])   # (the table carries one pitch for all states: C)
     N, C = x2[0].shape
     if any(tuple(x.shape) != (N, C) for x in x2):
         raise ValueError("the batched path needs states of one shape (N, C)")
-    u2 = []
-    for u in us:
-        _check_f64_cuda(u, "u")
-        if u.shape != (N,):
-            raise ValueError(f"every u must have shape ({N},)")
-        u2.append(u.contiguous())
-    w2 = None
-    if ws is not None:
-        w2 = []
-        for w in ws:
-            _check_f64_cuda(w, "w")
-            if w.shape != (N,):
-                raise ValueError(f"every w must have shape ({N},)")
-            w2.append(w.contiguous())
+    u2 = [_sample_vector(u, "u", N) for u in us]
+    w2 = None if ws is None else [_sample_vector(w, "w", N) for w in ws]
     tab = (_lib.StatePtrs * S)()
     for s in range(S):
         tab[s].x, tab[s].u = x2[s].data_ptr(), u2[s].data_ptr()
@@ -675,11 +644,7 @@ def resample_vals_batched(xs, us, order: int, *, nrep: int, sampler: DeviceSampl
                 tab, keep = kept
             buf, valid = prep.bind(key, nb)
             opts.prep, opts.prep_bytes, opts.prep_valid = buf.data_ptr(), buf.numel(), int(valid)
-    ikey = (torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)  # the words batched_info() reads back
-    info = _last_batched_info.get(ikey)
-    if info is None:
-        info = _last_batched_info[ikey] = torch.zeros(4, dtype=torch.int64, device="cuda")
-    opts.info = info.data_ptr()
+    opts.info = _info_words(_last_batched_info).data_ptr()  # the words batched_info() reads back
     wsb = workspace(L.txm_resample_vals_batched_ws_bytes(S, N, C, nrep, order))
     check(L.txm_resample_vals_batched_opts(tab, S, C, N, C, order, nrep, _ptr(freq), spec_p, counts_p, _ptr(out), ct.byref(opts),
                                            _ptr(wsb), wsb.numel(), _stream()), "txm_resample_vals_batched_opts")
@@ -815,7 +780,7 @@ def influence_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: torch.Te
     Returns ``(cov [C, n_f, n_f], mean [C, n_f])`` on the device: ``sum w^2 psi_i psi_j / (sum w)^2`` and
     ``sum w psi_k / sum w``.  One pass over x."""
     L = _L()
-    x2, ls, lc, u, w, N, C, _ = _rowmajor_operands(x, u, w)
+    x2, ls, lc, u, w, N, C, _ = _operands(x, u, w, "either")
     for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
         _check_f64_cuda(t, name)
     if a.dim() != 3 or a.shape[0] != C or b.shape != a.shape:
@@ -854,7 +819,7 @@ def influence_cov_batched(xs, us, a: torch.Tensor, b: torch.Tensor, center_u, ce
         raise ValueError("weights for all states or for none")
     if ws is not None and ws[0] is None:
         ws = None
-    ops = [_rowmajor_operands(xs[s], us[s], None if ws is None else ws[s]) for s in range(S)]
+    ops = [_operands(xs[s], us[s], None if ws is None else ws[s], "either") for s in range(S)]
     C = ops[0][6]
     if any(o[6] != C for o in ops):
         raise ValueError("every x must have the same number of columns")
@@ -931,16 +896,7 @@ def perturb(x: torch.Tensor, u: torch.Tensor, dalphas, freq: torch.Tensor | None
     """Exponentially reweighted averages for each dalpha: (n_alpha, C), or
     (nrep, n_alpha, C) with bootstrap counts ``freq`` (nrep, N).  x: (N, C) row-major or (N,)."""
     L = _L()
-    _check_f64_cuda(x, "x")
-    _check_f64_cuda(u, "u")
-    squeeze = x.dim() == 1
-    x2 = x.unsqueeze(1) if squeeze else x
-    if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < x2.shape[1]):
-        x2 = x2.contiguous()
-    N, C = x2.shape
-    if u.shape != (N,):
-        raise ValueError(f"u must have shape ({N},), got {tuple(u.shape)}")
-    u = u.contiguous()
+    x2, ls, _, u, _, N, C, squeeze = _operands(x, u, None, "rowmajor")
     da = np.atleast_1d(np.asarray(dalphas, dtype=np.float64))
     nrep = 1
     if freq is not None:
@@ -949,13 +905,12 @@ def perturb(x: torch.Tensor, u: torch.Tensor, dalphas, freq: torch.Tensor | None
             raise ValueError(f"freq must be (nrep, {N}), got {tuple(freq.shape)}")
         nrep = freq.shape[0]
     outs = []
-    for a0 in range(0, len(da), 8):  # 8 perturbations per pass over the samples
-        chunk = np.ascontiguousarray(da[a0 : a0 + 8])
+    for _, chunk in _eight_per_pass(da):
         na = len(chunk)
         out = torch.empty((nrep, na, C), dtype=F64, device="cuda")
         ws = workspace(L.txm_perturb_ws_bytes(N, C, na, nrep))
         check(
-            L.txm_perturb(_ptr(x2), max(x2.stride(0), C) if N > 1 else C, _ptr(u), N, C,
+            L.txm_perturb(_ptr(x2), ls, _ptr(u), N, C,
                           chunk.ctypes.data_as(ct.POINTER(ct.c_double)), na, _ptr(freq), nrep, _ptr(out), _ptr(ws),
                           ws.numel(), _stream()),
             "txm_perturb",
@@ -991,7 +946,7 @@ def _mbar_table(us, xs=None):
         raise ValueError(f"MBAR needs 1 <= K <= 64 states, got {K}")
     if xs is not None and len(xs) != K:
         raise ValueError("need one x per u")
-    u2, x2, ns, C = [], [], [], 1
+    u2, x2, ldx, ns, C = [], [], [], [], 1
     for s in range(K):
         u = us[s]
         _check_f64_cuda(u, "u")
@@ -1005,20 +960,20 @@ def _mbar_table(us, xs=None):
             x = x.unsqueeze(1) if x.dim() == 1 else x
             if x.dim() != 2 or x.shape[0] != u.shape[0]:
                 raise ValueError(f"x of state {s} must be ({u.shape[0]},) or ({u.shape[0]}, C)")
-            if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
-                x = x.contiguous()
+            x, ls, _ = _place(x, "rowmajor")
             if s == 0:
                 C = x.shape[1]
             elif x.shape[1] != C:
                 raise ValueError("every state's x must have the same number of columns")
             x2.append(x)
+            ldx.append(ls)
     tab = (_lib.MbarState * K)()
     for s in range(K):
         tab[s].u = u2[s].data_ptr()
         tab[s].n = ns[s]
         if xs is not None:
             tab[s].x = x2[s].data_ptr()
-            tab[s].ldx_s = max(x2[s].stride(0), C) if ns[s] > 1 else C
+            tab[s].ldx_s = ldx[s]
     return tab, (u2, x2), np.asarray(ns, dtype=np.float64), C
 
 
@@ -1054,82 +1009,6 @@ def mbar_eval(us, alpha0, g, upiv: float, logD: torch.Tensor | None = None):
     H[np.triu_indices(K)] = v[K:K + nh]
     H = H + np.triu(H, 1).T
     return v[:K].copy(), H, float(v[K + nh])
-
-
-_MBAR_MAX_STEP = 50.0   # cap (in units of f) on the part of a step along directions without curvature
-
-
-def mbar_newton(evaluate, N, b, *, f0=None, tol: float = 1e-12, max_iter: int = 100):
-    """Damped Newton on the convex MBAR objective  F(f) = sum_n logD_n(f) - sum_k N_k f_k  over the K - 1 free energies
-    f_1.. (gauge f_0 = 0).  ``evaluate(g) -> (S, H, obj)`` is one pass over the pooled samples at the log-weights
-    g = b + f + c (b_k = ln N_k - alpha0_k upiv; the constant c = -max_k(b + f) keeps them near 0): S_k = sum_n p_kn,
-    H_jk = sum_n p_jn p_kn (full symmetric) and obj = sum_n logD_n + c N_tot.  The gradient is S - N and the Hessian
-    diag(S) - H.
-
-    The reduced Hessian is eigen-decomposed: directions with curvature above 1e-12 of the largest get the Newton step;
-    the rest (states without overlap) get the gradient over that floor, capped at 50 units of f, so a singular Hessian
-    still gives a finite step.  The step is halved until the objective decreases (Armijo), or -- once the change is
-    below the objective's rounding -- until the gradient does.  Converged: max_k |S_k - N_k| / N_k <= tol.
-
-    Returns (f, g, iterations, evaluations, gradient) with g the log-weights of the last evaluation (the returned f)."""
-    N = np.asarray(N, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64)
-    K = len(N)
-    Ntot = float(N.sum())
-    f = np.zeros(K) if f0 is None else np.asarray(f0, dtype=np.float64) - float(f0[0])
-    eps = np.finfo(np.float64).eps
-
-    def point(f):
-        g = b + f
-        c = -float(g.max())
-        g = g + c
-        S, H, obj = evaluate(g)
-        S, H = np.asarray(S, dtype=np.float64), np.asarray(H, dtype=np.float64)
-        F = obj - c * Ntot - float(N @ f)
-        rnd = 64 * eps * (abs(obj) + abs(c) * Ntot + float(N @ np.abs(f)) + Ntot)
-        return S, H, F, rnd, g
-
-    S, H, F, rnd, g = point(f)
-    n_eval = 1
-    for it in range(max_iter + 1):
-        grad = S - N
-        err = float(np.max(np.abs(grad) / N))
-        if not np.isfinite(err):
-            raise _lib.TxmError(f"MBAR solve: the gradient is not finite (max |S_k - N_k| / N_k = {err})")
-        if err <= tol:
-            return f, g, it, n_eval, err
-        if it == max_iter:
-            break
-        Hr = (np.diag(S) - H)[1:, 1:]
-        gr = grad[1:]
-        lam, V = np.linalg.eigh(0.5 * (Hr + Hr.T))
-        floor = 1e-12 * max(float(lam.max()), float(N.min()))
-        good = lam > floor
-        proj = V.T @ gr
-        step = -(V[:, good] @ (proj[good] / lam[good]))
-        if not good.all():
-            flat = -(V[:, ~good] @ (proj[~good] / floor))
-            big = float(np.max(np.abs(flat)))
-            if big > _MBAR_MAX_STEP:
-                flat *= _MBAR_MAX_STEP / big
-            step = step + flat
-        slope = float(gr @ step)
-        t = 1.0
-        while True:
-            fn = f.copy()
-            fn[1:] += t * step
-            Sn, Hn, Fn, rn, gn = point(fn)
-            n_eval += 1
-            errn = float(np.max(np.abs(Sn - N) / N))
-            if Fn <= F + 1e-4 * t * slope or (abs(Fn - F) <= max(rnd, rn) and errn < err):
-                break
-            t *= 0.5
-            if t < 1e-10:
-                raise _lib.TxmError(f"MBAR solve: the line search found no decrease at iteration {it}; "
-                                    f"max |S_k - N_k| / N_k = {err:.3e}")
-        f, S, H, F, rnd, g = fn, Sn, Hn, Fn, rn, gn
-    raise _lib.TxmError(f"MBAR solve did not converge in {max_iter} Newton iterations: "
-                        f"max |S_k - N_k| / N_k = {err:.3e} > tol {tol:.1e}")
 
 
 def mbar_initial_f(us, alpha0) -> np.ndarray:
@@ -1185,8 +1064,7 @@ def mbar_predict(xs, us, alpha0, f, logD, alphas, *, upiv: float | None = None) 
         raise ValueError("logD must hold one value per pooled sample")
     al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
     outs = []
-    for i0 in range(0, len(al), 8):
-        chunk = np.ascontiguousarray(al[i0:i0 + 8])
+    for _, chunk in _eight_per_pass(al):
         na = len(chunk)
         out = torch.empty((na, C), dtype=F64, device="cuda")
         ws = workspace(L.txm_mbar_ws_bytes(K, C, na), tag="mbar")
@@ -1204,17 +1082,6 @@ def mbar_predict(xs, us, alpha0, f, logD, alphas, *, upiv: float | None = None) 
 # only the Gram matrix G = W^T W: the sampled block is H / (N_j N_k) of one evaluation pass at the solution, the target
 # blocks are the sums of txm_mbar_cov.
 # ---------------------------------------------------------------------------
-_MBAR_PINV_CUT = 1e-12   # eigenvalues of I - sqrt(N) G sqrt(N) below this fraction of the largest are its null space
-
-
-def mbar_solution_g(ns, alpha0, sol: MbarSolution):
-    """The shifted log-weights the solve's last evaluation ran at (``mbar_newton``'s g = b + f - max(b + f)) and the
-    shift c = -max(b + f): ``sol.logD`` is ln sum_k N_k e^{f_k - alpha0_k u_n} + c."""
-    a0 = np.asarray(alpha0, dtype=np.float64).reshape(-1)
-    g = np.log(np.asarray(ns, dtype=np.float64)) - a0 * sol.upiv + np.asarray(sol.f, dtype=np.float64)
-    c = -float(g.max())
-    return g + c, c
-
 
 def mbar_gram(us, alpha0, sol: MbarSolution) -> np.ndarray:
     """G_jk = sum_n W_nj W_nk of the sampled states: one ``mbar_eval`` at the solution's g, H_jk / (N_j N_k)."""
@@ -1222,57 +1089,6 @@ def mbar_gram(us, alpha0, sol: MbarSolution) -> np.ndarray:
     g, _ = mbar_solution_g(ns, alpha0, sol)
     _, H, _ = mbar_eval(us, np.asarray(alpha0, dtype=np.float64).reshape(-1), g, sol.upiv)
     return H / np.outer(ns, ns)
-
-
-def _sym_pinv(A: np.ndarray) -> np.ndarray:
-    lam, V = np.linalg.eigh(0.5 * (A + A.T))
-    keep = lam > _MBAR_PINV_CUT * max(float(np.max(np.abs(lam))), 1.0)
-    return (V[:, keep] / lam[keep]) @ V[:, keep].T
-
-
-def mbar_theta(G, N) -> np.ndarray:
-    """Theta = W^T (I - W N W^T)^+ W from the Gram matrix G = W^T W = V L V^T alone: V S (I - S V^T N V S)^+ S V^T with
-    S = L^{1/2} (negative eigenvalues of G, rounding, clipped to 0).  N: the sample count of every column, 0 for the
-    columns that were not sampled (targets)."""
-    G = np.asarray(G, dtype=np.float64)
-    N = np.asarray(N, dtype=np.float64).reshape(-1)
-    if G.shape != (len(N), len(N)):
-        raise ValueError("G must be square with one row per entry of N")
-    lam, V = np.linalg.eigh(0.5 * (G + G.T))
-    S = np.sqrt(np.clip(lam, 0.0, None))
-    VS = V * S
-    A = np.eye(len(N)) - VS.T @ (N[:, None] * VS)
-    return VS @ _sym_pinv(A) @ VS.T
-
-
-def mbar_reduced_pinv(Gs, N) -> np.ndarray:
-    """(I_K - sqrt(N) G_s sqrt(N))^+ of the sampled block: singular along sqrt(N) by construction (the rows of the
-    overlap matrix sum to 1), hence a pseudo-inverse.  Taken once per model."""
-    rn = np.sqrt(np.asarray(N, dtype=np.float64).reshape(-1))
-    Gs = np.asarray(Gs, dtype=np.float64)
-    return _sym_pinv(np.eye(len(rn)) - rn[:, None] * Gs * rn[None, :])
-
-
-def mbar_mean_variance(Gs, N, yy, b, *, pinv=None) -> np.ndarray:
-    """var of an MBAR average at a target from the K x K block alone: with y_n = W_na (x_n - <x>_a), the unsampled column
-    y has Theta_yy = yy + (sqrt(N) b)^T (I_K - sqrt(N) G_s sqrt(N))^+ (sqrt(N) b), yy = sum_n y_n^2 and
-    b_k = sum_n W_nk y_n.  ``yy`` (...,) and ``b`` (..., K) broadcast; ``pinv``: ``mbar_reduced_pinv(Gs, N)`` if the
-    caller keeps it."""
-    rn = np.sqrt(np.asarray(N, dtype=np.float64).reshape(-1))
-    P = mbar_reduced_pinv(Gs, N) if pinv is None else pinv
-    rb = np.asarray(b, dtype=np.float64) * rn
-    return np.asarray(yy, dtype=np.float64) + np.einsum("...j,jk,...k->...", rb, P, rb)
-
-
-def mbar_overlap(Gs, N):
-    """The overlap matrix O = G_s diag(N) of the sampled states (rows sum to 1), its eigenvalues in descending order --
-    those of the symmetric sqrt(N) G_s sqrt(N), which is similar to O -- and the scalar 1 - the second largest
-    (1 for a single state)."""
-    Gs = np.asarray(Gs, dtype=np.float64)
-    N = np.asarray(N, dtype=np.float64).reshape(-1)
-    rn = np.sqrt(N)
-    ev = np.linalg.eigvalsh(rn[:, None] * (0.5 * (Gs + Gs.T)) * rn[None, :])[::-1].copy()
-    return Gs * N[None, :], ev, (float(1.0 - ev[1]) if len(ev) > 1 else 1.0)
 
 
 def mbar_cov_sums(xs, us, alpha0, sol: MbarSolution, alphas, means, *, with_lnw: bool = False):
@@ -1298,8 +1114,7 @@ def mbar_cov_sums(xs, us, alpha0, sol: MbarSolution, alphas, means, *, with_lnw:
     dp = ct.POINTER(ct.c_double)
     width = 1 + K + C * (1 + K)
     outs, lnws = [], []
-    for i0 in range(0, len(al), 8):
-        chunk = np.ascontiguousarray(al[i0:i0 + 8])
+    for i0, chunk in _eight_per_pass(al):
         na = len(chunk)
         mean = means[i0:i0 + na].contiguous()
         out = torch.empty((na, width), dtype=F64, device="cuda")
@@ -1356,17 +1171,7 @@ def _mbar_boot_slab(K: int, C: int, n_alpha: int, ntot: int, nrep: int) -> int:
     that do (at least one).  Rows of a slab equal the rows of the unslabbed call bit for bit (DeviceSampler.rows)."""
     L = _L()
     need = lambda n: L.txm_mbar_boot_ws_bytes(K, C, n_alpha, ntot, n)  # noqa: E731  (grows with n)
-    budget = workspace_budget()
-    if need(nrep) <= budget:
-        return nrep
-    lo, hi = 1, nrep
-    while lo < hi:
-        mid = (lo + hi + 1) // 2
-        if need(mid) <= budget:
-            lo = mid
-        else:
-            hi = mid - 1
-    return lo
+    return _most_that_fit(need, nrep, workspace_budget())
 
 
 def mbar_boot_eval(us, alpha0, samplers, g, upiv: float, active=None):
@@ -1397,104 +1202,6 @@ def mbar_boot_eval(us, alpha0, samplers, g, upiv: float, active=None):
     H[:, iu[0], iu[1]] = v[:, K:K + nh]
     H[:, iu[1], iu[0]] = v[:, K:K + nh]
     return v[:, :K].copy(), H, v[:, K + nh].copy()
-
-
-def mbar_newton_batched(evaluate, N, b, f0, *, tol: float = 1e-12, max_iter: int = 100):
-    """``mbar_newton`` for R replicates at once: the same damped Newton per replicate (eigen-floor, step halving,
-    convergence max_k |S_k - N_k| / N_k <= tol), one batched evaluation per trial point.
-
-    ``evaluate(g, active) -> (S, H, obj)``: ``g`` is the full (R, K) array of log-weights (row r = b + f_r + c_r, the
-    constant c_r = -max_k keeps them near 0), ``active`` the int array of the rows wanted; S (A, K), H (A, K, K) full
-    symmetric and obj (A,) are those rows' weighted sums (S_k = sum_n c_n p_kn, ...), in the order of ``active``.
-    A converged replicate is frozen: its f never changes again and it is absent from every later ``active``.
-    ``f0``: (R, K), one start per replicate (``np.tile(f, (R, 1))`` for a common one).
-
-    Returns (f (R, K), g (R, K) -- each row's log-weights at its f --, iterations (R,), evaluations, gradient (R,));
-    ``evaluations`` counts calls of ``evaluate``."""
-    N = np.asarray(N, dtype=np.float64)
-    b = np.asarray(b, dtype=np.float64)
-    K = len(N)
-    Ntot = float(N.sum())
-    f = np.array(f0, dtype=np.float64)
-    if f.ndim != 2 or f.shape[1] != K:
-        raise ValueError(f"f0 must be (R, {K})")
-    R = f.shape[0]
-    f -= f[:, :1]
-    eps = np.finfo(np.float64).eps
-    g = np.zeros((R, K))          # what the device is shown (trial rows included)
-    g_acc = np.zeros((R, K))      # each row's log-weights at its accepted f
-    n_eval = 0
-
-    def point(fa, rows):
-        nonlocal n_eval
-        ga = b[None, :] + fa
-        c = -ga.max(axis=1)
-        g[rows] = ga + c[:, None]
-        S, H, obj = evaluate(g, rows.copy())
-        n_eval += 1
-        S, H, obj = np.asarray(S, dtype=np.float64), np.asarray(H, dtype=np.float64), np.asarray(obj, dtype=np.float64)
-        F = obj - c * Ntot - fa @ N
-        rnd = 64 * eps * (np.abs(obj) + np.abs(c) * Ntot + np.abs(fa) @ N + Ntot)
-        return S, H, F, rnd
-
-    rows = np.arange(R)
-    S, H, F, rnd = point(f, rows)
-    g_acc[:] = g
-    err = np.max(np.abs(S - N) / N, axis=1)
-    its = np.zeros(R, dtype=np.int64)
-    done = np.zeros(R, dtype=bool)
-    for it in range(max_iter + 1):
-        if not np.all(np.isfinite(err)):
-            r = int(np.flatnonzero(~np.isfinite(err))[0])
-            raise _lib.TxmError(f"MBAR bootstrap solve: the gradient of replicate {r} is not finite")
-        done |= err <= tol
-        rows = np.flatnonzero(~done)
-        if len(rows) == 0:
-            return f, g_acc, its, n_eval, err
-        if it == max_iter:
-            break
-        steps = np.zeros((R, K - 1))
-        slopes = np.zeros(R)
-        for r in rows:
-            grad = S[r] - N
-            Hr = (np.diag(S[r]) - H[r])[1:, 1:]
-            gr = grad[1:]
-            lam, V = np.linalg.eigh(0.5 * (Hr + Hr.T))
-            floor = 1e-12 * max(float(lam.max()), float(N.min()))
-            good = lam > floor
-            proj = V.T @ gr
-            step = -(V[:, good] @ (proj[good] / lam[good]))
-            if not good.all():
-                flat = -(V[:, ~good] @ (proj[~good] / floor))
-                big = float(np.max(np.abs(flat)))
-                if big > _MBAR_MAX_STEP:
-                    flat *= _MBAR_MAX_STEP / big
-                step = step + flat
-            steps[r] = step
-            slopes[r] = float(gr @ step)
-        t = np.ones(R)
-        pending = rows
-        while len(pending):
-            fn = f[pending].copy()
-            fn[:, 1:] += t[pending, None] * steps[pending]
-            Sn, Hn, Fn, rn = point(fn, pending)
-            errn = np.max(np.abs(Sn - N) / N, axis=1)
-            ok = (Fn <= F[pending] + 1e-4 * t[pending] * slopes[pending]) | \
-                ((np.abs(Fn - F[pending]) <= np.maximum(rnd[pending], rn)) & (errn < err[pending]))
-            acc = pending[ok]
-            f[acc], S[acc], H[acc], F[acc], rnd[acc], err[acc] = fn[ok], Sn[ok], Hn[ok], Fn[ok], rn[ok], errn[ok]
-            g_acc[acc] = g[acc]
-            its[acc] += 1
-            pending = pending[~ok]
-            t[pending] *= 0.5
-            if len(pending) and t[pending].min() < 1e-10:
-                r = int(pending[np.argmin(t[pending])])
-                raise _lib.TxmError(f"MBAR bootstrap solve: the line search of replicate {r} found no decrease at "
-                                    f"iteration {it}; max |S_k - N_k| / N_k = {err[r]:.3e}")
-    worst = int(rows[np.argmax(err[rows])])
-    raise _lib.TxmError(f"MBAR bootstrap solve did not converge in {max_iter} Newton iterations: {len(rows)} of {R} "
-                        f"replicates left, the worst is replicate {worst} with max |S_k - N_k| / N_k = "
-                        f"{err[worst]:.3e} > tol {tol:.1e}")
 
 
 def mbar_bootstrap_solve(us, alpha0, samplers, sol0: MbarSolution, *, tol: float = 1e-12, max_iter: int = 100) -> np.ndarray:
@@ -1554,8 +1261,7 @@ def mbar_bootstrap_predict(xs, us, alpha0, samplers, f, sol0: MbarSolution, alph
         sub = list(samplers) if (r0, r1) == (0, nrep) else [sm.rows(r0, r1) for sm in samplers]
         _, stab, keep2, _, _, _ = _mbar_boot_tables(us, sub)
         gd = torch.as_tensor(g[r0:r1]).to("cuda")
-        for i0 in range(0, len(al), 8):
-            chunk = np.ascontiguousarray(al[i0:i0 + 8])
+        for i0, chunk in _eight_per_pass(al):
             na = len(chunk)
             out = torch.empty((r1 - r0, na, C), dtype=F64, device="cuda")
             ws = workspace(L.txm_mbar_boot_ws_bytes(K, C, na, ntot, r1 - r0), tag="mbar_boot")
@@ -1601,9 +1307,7 @@ def _lag_series_args(x, u):
         if C == 0:
             x2 = None
         else:
-            if x2.stride(1) != 1 or (N > 1 and x2.stride(0) < C):
-                x2 = x2.contiguous()
-            ls = max(x2.stride(0), C) if N > 1 else C
+            x2, ls, _ = _place(x2, "rowmajor")
     return x2, u, N, C, ls
 
 
