@@ -667,6 +667,34 @@ int txm_influence_cov_batched(const txm_inf_state *states_host, int64_t S, int64
                               const double *center_u, const double *center_x, const double *a, const double *b,
                               double *cov, double *mean, void *ws, size_t ws_bytes, txm_stream stream);
 
+/* ---- (f-11) blocked (batch-means) delta-method covariance for correlated samples, with the blocking curve ------ */
+/* The operands of (f-9) for x row-major with pitch ldx_s >= C (w may be NULL), a block length `block` = B >= 1 and
+ * n_levels in [1, 32].  With p_n = w_n / sum w and psi_k(n, c) as in (f-9), level-l block j covers the rows
+ * [j B 2^l, min(N, (j + 1) B 2^l)) -- the last block may be short and is kept -- and
+ *     z_j[c][k]          = sum_{n in block j} p_n psi_k(n, c)
+ *     cov[l][c][i][j']   = sum_j z_j[c][i] z_j[c][j']      (l < n_levels; full symmetric n_f x n_f, [i][j'] and [j'][i] same bits)
+ *     mean[c][k]         = sum_n p_n psi_k(n, c)           (diagnostic: ~ 0)
+ * -- batch means / the cluster-robust sandwich estimator with time blocks as clusters: the covariance of the estimates
+ * when the samples are a correlated series and B exceeds its correlation time.  There is NO nb / (nb - 1) factor, so
+ * block = 1, level 0 is the cov of (f-9); the relative bias is -1 / nb with nb = ceil(N / (B 2^l)) blocks at level l.
+ * Levels with a single block are allowed and computed (block > N too: one block).  cov [n_levels][C][n_f][n_f] and
+ * mean [C][n_f] are device arrays, the rest as in (f-9).
+ * Pass 1 reads the samples once: per level-0 block and column the 2 n_q sums  sum w du^q,  sum w dx du^q  are contracted
+ * with a, b once per block into the workspace; every block is summed by one workgroup in a fixed order, so its bits do
+ * not depend on the launch width.  Pass 2 (a workgroup per column) adds the total weight in a fixed order and merges the
+ * pairs of the level below in place, level by level.  No floating-point atomics; two calls give the same bits.
+ * A row of weight zero is selected out and may hold anything; a block of total weight zero contributes zero; total
+ * weight zero gives zeros.  First-order rounding bound per level: eps * sum_b beta_bi beta_bj',
+ * beta_bk = sum_{n in b} p_n B_k(n), B_k as in (f-9).
+ * Workspace: 8 ceil(N / block) (C n_f + 1) + 256 bytes -- txm_influence_block_cov_ws_bytes, host logic, 0 for bad
+ * arguments.  Null pointers, N < 1, C outside [1, 65535], n_f or n_q outside [1, 9], ldx_s < C, a NaN center_u,
+ * block < 1, n_levels outside [1, 32] and a short workspace are refused before anything is enqueued. */
+size_t txm_influence_block_cov_ws_bytes(int64_t N, int64_t C, int n_f, int n_q, int64_t block);
+int txm_influence_block_cov(const double *x, int64_t ldx_s, const double *u, const double *w, int64_t N, int64_t C,
+                            int n_f, int n_q, double center_u, const double *center_x, const double *a, const double *b,
+                            int64_t block, int n_levels, double *cov, double *mean, void *ws, size_t ws_bytes,
+                            txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

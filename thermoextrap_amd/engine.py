@@ -862,6 +862,55 @@ def influence_cov_batched(xs, us, a: torch.Tensor, b: torch.Tensor, center_u, ce
     return cov, mean
 
 
+def block_levels(n: int, block: int) -> tuple[np.ndarray, np.ndarray]:
+    """The levels of a blocking curve over ``n`` records from block length ``block``: ``(block_lengths, n_blocks)``
+    with ``block_lengths[l] = block * 2**l`` and ``n_blocks[l] = ceil(n / block_lengths[l])`` -- a last short block is
+    kept -- for every level that still has at least two blocks (at most 32).  Host logic."""
+    n, block = int(n), int(block)
+    if block < 1 or 2 * block > n:
+        raise ValueError(f"block must satisfy 1 <= block and 2 * block <= N = {n} (at least two blocks), got {block}")
+    lengths, counts = [], []
+    b = block
+    while -(-n // b) >= 2 and len(lengths) < 32:
+        lengths.append(b)
+        counts.append(-(-n // b))
+        b *= 2
+    return np.asarray(lengths, dtype=np.int64), np.asarray(counts, dtype=np.int64)
+
+
+def influence_block_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: torch.Tensor, center_u: float,
+                        center_x: torch.Tensor, block: int, n_levels: int = 1,
+                        w: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Blocked (batch-means) delta-method covariance for a correlated series (txm_influence_block_cov): with psi_k as in
+    ``influence_cov`` and p = w / sum w, ``cov[l, c] = sum_j z_j z_j'`` over the sums ``z_j = sum_{n in block j} p_n psi(n)``
+    of the contiguous blocks of ``block * 2**l`` rows (a last short block is kept; no nb / (nb - 1) factor, so
+    ``block=1`` is ``influence_cov``'s result).  x: (N, C) or (N,), copied to row-major if it is not; a, b:
+    (C, n_f, n_q); center_x: (C,).  Returns ``(cov [n_levels, C, n_f, n_f], mean [C, n_f])`` on the device from one
+    pass over x."""
+    L = _L()
+    x2, ls, _, u, w, N, C, _ = _operands(x, u, w, "rowmajor")
+    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
+        _check_f64_cuda(t, name)
+    if a.dim() != 3 or a.shape[0] != C or b.shape != a.shape:
+        raise ValueError(f"a and b must both have shape ({C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
+    if center_x.shape != (C,):
+        raise ValueError(f"center_x must have shape ({C},), got {tuple(center_x.shape)}")
+    block, n_levels = int(block), int(n_levels)
+    if block < 1 or not 1 <= n_levels <= 32:
+        raise ValueError(f"need block >= 1 and 1 <= n_levels <= 32, got block={block}, n_levels={n_levels}")
+    _, n_f, n_q = a.shape
+    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
+    cov = torch.empty((n_levels, C, n_f, n_f), dtype=F64, device="cuda")
+    mean = torch.empty((C, n_f), dtype=F64, device="cuda")
+    ws = workspace(L.txm_influence_block_cov_ws_bytes(N, C, n_f, n_q, block))
+    check(
+        L.txm_influence_block_cov(_ptr(x2), ls, _ptr(u), _ptr(w), N, C, n_f, n_q, float(center_u), _ptr(center_x), _ptr(a),
+                                  _ptr(b), block, n_levels, _ptr(cov), _ptr(mean), _ptr(ws), ws.numel(), _stream()),
+        "txm_influence_block_cov",
+    )
+    return cov, mean
+
+
 TAYLOR_MODES ={"sum": 0, "cumsum": 1, "terms": 2}
 
 

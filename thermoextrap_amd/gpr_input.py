@@ -48,7 +48,7 @@ def _check_method(method):
         raise ValueError(f'method must be "bootstrap" or "delta", got {method!r}')
 
 
-def input_GP_from_state(state, n_rep=100, log_scale=False, sampler=None, method="bootstrap"):  # noqa: N802
+def input_GP_from_state(state, n_rep=100, log_scale=False, sampler=None, method="bootstrap", block=None):  # noqa: N802
     """(x_data, y_data, cov_data) for one ExtrapModel state.
 
     ``sampler`` overrides the default ``{"nrep": n_rep}`` (e.g. to fix a seed or
@@ -56,8 +56,12 @@ def input_GP_from_state(state, n_rep=100, log_scale=False, sampler=None, method=
 
     ``method="delta"`` (extension): ``cov_data`` is the delta-method covariance ``state.derivs_cov()`` -- one pass over
     the samples, no sampler drawn, ``n_rep`` and ``sampler`` unused -- instead of the covariance over bootstrap
-    replicates, of which it is the first-order term.  Both assume independent samples."""
+    replicates, of which it is the first-order term.  Both assume independent samples -- unless ``block`` (an int,
+    ``method="delta"`` only) is given: then ``cov_data`` is the blocked ``state.derivs_cov(block=block)`` of a correlated
+    series kept whole."""
     _check_method(method)
+    if block is not None and method != "delta":
+        raise ValueError('block applies to method="delta" only')
     order = state.order
     alphas = state.alpha0 * np.ones((order + 1, 1))
     if log_scale:
@@ -66,7 +70,7 @@ def input_GP_from_state(state, n_rep=100, log_scale=False, sampler=None, method=
 
     if method == "delta":
         derivs = state.derivs(norm=False).values
-        cov = state._derivs_cov_device(order, state.minus_log)[0].cpu().numpy()   # (n_out, order+1, order+1)
+        cov = state._derivs_cov_device(order, state.minus_log, block)[0].cpu().numpy()   # (n_out, order+1, order+1)
     elif isinstance(state.data, DataCentralMomentsVals):
         derivs = state.derivs(norm=False).values
         boot = state.resample(sampler=sampler if sampler is not None else {"nrep": n_rep})
@@ -186,7 +190,8 @@ def _input_gp_sharded(coll, n_rep, log_scale, spec, local):
     return _assemble(full[:, 0].copy(), y_s, cov, log_scale, order)
 
 
-def input_GP_from_states(states, n_rep=100, log_scale=False, sampler=None, sharded=False, method="bootstrap"):  # noqa: N802
+def input_GP_from_states(states, n_rep=100, log_scale=False, sampler=None, sharded=False, method="bootstrap",  # noqa: N802
+                         block=None):
     """`input_GP_from_state` for a whole StateCollection (BASELINE config 5: 64 state points) with the
     bootstrap, the derivative evaluation and the covariance over replicates each done in ONE launch for all
     states.  The reference loops over the states calling input_GP_from_state and stacks the pieces
@@ -202,17 +207,22 @@ def input_GP_from_states(states, n_rep=100, log_scale=False, sampler=None, shard
     ``method="delta"`` (extension): the per-state delta-method covariances (``input_GP_from_state(method="delta")``, one
     pass over each state's samples) in the same block-diagonal layout; no sampler is drawn.  States of one column shape
     and order -- of ANY length each -- take one launch per kernel for the whole collection
-    (``StateCollection.derivs_cov``, txm_influence_cov_batched); other collections loop over the states."""
+    (``StateCollection.derivs_cov``, txm_influence_cov_batched); other collections loop over the states.  ``block`` (an
+    int for all states, or one entry per state; ``method="delta"`` only): the blocked covariances of correlated series
+    kept whole (``ExtrapModel.derivs_cov(block=...)``), state by state."""
     from .models import StateCollection
 
     _check_method(method)
+    if block is not None and method != "delta":
+        raise ValueError('block applies to method="delta" only')
     coll = states if isinstance(states, StateCollection) else StateCollection(list(states))
     spec = sampler if sampler is not None else {"nrep": n_rep}
     if method == "delta":
         if sharded:
             raise NotImplementedError('method="delta" with sharded=...')
         order = coll.order
-        if coll._delta_batch_eligible() is not None:
+        blocks = coll._blocks_per_state(block)
+        if blocks is None and coll._delta_batch_eligible() is not None:
             # every state's covariance from one launch per kernel whatever the states' lengths, the states' own
             # derivatives from one evaluation over the stacked states (as _batched_blocks does): two copies back
             import torch
@@ -227,7 +237,7 @@ def input_GP_from_states(states, n_rep=100, log_scale=False, sampler=None, shard
             dv_d, _ = st0.derivatives.derivs(data=one, order=order, norm=False, minus_log=st0.minus_log, _device=True)
             return _assemble(np.array([float(st.alpha0) for st in coll]), dv_d.permute(1, 0, 2).contiguous().cpu().numpy(),
                              cov_d.cpu().numpy(), log_scale, order)
-        parts = [input_GP_from_state(st, method="delta") for st in coll]
+        parts = [input_GP_from_state(st, method="delta", block=None if blocks is None else blocks[s]) for s, st in enumerate(coll)]
         return _assemble(np.array([float(st.alpha0) for st in coll]), np.stack([p_[1] for p_ in parts]),
                          np.stack([p_[2] for p_ in parts]), log_scale, order)
     if sharded:

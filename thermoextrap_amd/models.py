@@ -408,6 +408,14 @@ def taylor_series_norm(order, order_dim="order"):
     return out
 
 
+def _check_block_type(block) -> int:
+    """A block length of the blocked error bars as a Python int; TypeError for anything that is not an integer (its
+    range depends on the number of records: ``engine.block_levels`` raises the ValueError)."""
+    if isinstance(block, bool) or not isinstance(block, (int, np.integer)):
+        raise TypeError(f"block must be an integer number of records, got {type(block).__name__}")
+    return int(block)
+
+
 class ExtrapModel(_Params):
     """Taylor-series extrapolation about ``alpha0`` (reference models.py:433-576)."""
 
@@ -567,13 +575,31 @@ class ExtrapModel(_Params):
         a, b = S.influence_coefs(self.derivatives.series, order, mom, minus_log=minus_log)
         return np.ascontiguousarray(a), np.ascontiguousarray(b), um, xm
 
-    def _derivs_cov_device(self, order, minus_log):
+    def _derivs_cov_device(self, order, minus_log, block=None):
+        if block is not None:
+            return self._blocked_cov_device(order, minus_log, block, curve=False)[:2]
         key = ("dcov", order, minus_log)
         if key not in self._cache:
             x2, ut, wt, st, src = self._delta_operands()
             a, b, um, xm = self._delta_coefs(st, order, minus_log)
             cov, _ = engine.influence_cov(x2, ut, engine.to_device(a), engine.to_device(b), um, engine.to_device(xm), w=wt)
             self._cache[key] = (cov, src)
+        return self._cache[key]
+
+    def _blocked_cov_device(self, order, minus_log, block, curve):
+        """``(cov, source, block_lengths, n_blocks)`` of the blocked estimator from ONE
+        ``engine.influence_block_cov``: cov [n_out, order + 1, order + 1] at ``block`` alone, or with ``curve``
+        [level, n_out, order + 1, order + 1] for every level of ``engine.block_levels``.  Cached under keys of their own
+        (the block is part of them): the iid entry ``("dcov", ...)`` is neither read nor written."""
+        block = _check_block_type(block)
+        key = ("dcov_block", order, minus_log, block, bool(curve))
+        if key not in self._cache:
+            x2, ut, wt, st, src = self._delta_operands()         # (first: an unsupported model says so, whatever the block)
+            lengths, counts = engine.block_levels(x2.shape[0], block)
+            a, b, um, xm = self._delta_coefs(st, order, minus_log)
+            cov, _ = engine.influence_block_cov(x2, ut, engine.to_device(a), engine.to_device(b), um, engine.to_device(xm),
+                                                block, n_levels=len(lengths) if curve else 1, w=wt)
+            self._cache[key] = (cov if curve else cov[0], src, lengths, counts)
         return self._cache[key]
 
     @staticmethod
@@ -587,7 +613,7 @@ class ExtrapModel(_Params):
         out._inherit(src.coords)
         return out
 
-    def derivs_cov(self, order=None, norm=False, minus_log=None):
+    def derivs_cov(self, order=None, norm=False, minus_log=None, block=None):
         """Delta-method (infinitesimal-jackknife) covariance of ``derivs(order)``: dims ``(order, order_2, *val_dims)``.
 
         ``V_ij = sum_n p_n^2 psi_i(n) psi_j(n)`` with ``p_n`` the normalised sample weights and ``psi_k(n)`` the empirical
@@ -598,23 +624,51 @@ class ExtrapModel(_Params):
         ``norm=True`` carries the ``1 / (i! j!)`` factors of ``derivs(norm=True)``.
 
         Supported: beta-extrapolation models of ``x_ave`` (central or raw, ``minus_log`` on or off, weights) over
-        ``DataCentralMomentsVals``; anything else raises NotImplementedError."""
+        ``DataCentralMomentsVals``; anything else raises NotImplementedError.
+
+        ``block=B`` (an int, ``1 <= B`` and ``2 B <= N``) is for a CORRELATED series kept whole: the records are cut
+        into contiguous blocks of B (a last short one is kept) and ``V_ij = sum_b z_bi z_bj`` with
+        ``z_bk = sum_{n in b} p_n psi_k(n)`` -- batch means over the derivative's own influence series, one pass
+        (txm_influence_block_cov), every record used.  B must exceed the correlation time: for an AR(1)-like series of
+        statistical inefficiency g the relative bias is about ``-g / (2 B)`` (``timeseries.block_length``), and
+        ``blocking_curve`` shows whether V has levelled off.  No ``nb / (nb - 1)`` factor is applied (``block=1`` is the
+        iid result; the relative bias ``-1 / nb`` can be corrected with ``blocking_curve``'s block counts).  A non-integer
+        block raises TypeError, one outside the range ValueError; ``block=None`` is the iid path, untouched."""
         if minus_log is None:
             minus_log = self.minus_log
         if order is None:
             order = self.order
-        cov, src = self._derivs_cov_device(order, bool(minus_log))
+        cov, src = self._derivs_cov_device(order, bool(minus_log), block)
         return self._ds(self._derivs_cov_labelled(cov.cpu().numpy(), src, order, norm))     # (n_out, order + 1, order + 1)
 
-    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None):
+    def blocking_curve(self, block, order=None, norm=False, minus_log=None):
+        """The blocking curve of Flyvbjerg & Petersen (1989) for ``derivs_cov``: ``(V, block_lengths, n_blocks)`` with
+        ``V[l] = derivs_cov(block=block * 2**l)`` (dims ``(level, order, order_2, *val_dims)``), ``block_lengths[l] =
+        block * 2**l`` and ``n_blocks[l] = ceil(N / block_lengths[l])``, for every level that still has at least two
+        blocks.  ONE kernel call: block sums are additive, so each level merges the pairs of the level below.  Where
+        the diagonal of V stops growing with the block length the blocks are longer than the correlation time; the
+        last levels are noisy (relative standard deviation about ``sqrt(2 / (n_blocks - 1))``) and biased by
+        ``-1 / n_blocks``."""
+        if minus_log is None:
+            minus_log = self.minus_log
+        if order is None:
+            order = self.order
+        cov, src, lengths, counts = self._blocked_cov_device(order, bool(minus_log), block, curve=True)
+        host = cov.cpu().numpy()
+        levels = [self._derivs_cov_labelled(host[l], src, order, norm) for l in range(host.shape[0])]
+        out = concat(levels, dim=DataArray(lengths.copy(), "level"))
+        return self._ds(out), lengths.copy(), counts.copy()
+
+    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None, block=None):
         """``(prediction, std)``: ``predict(alpha)`` and its delta-method standard deviation ``sqrt(t' V t)``,
-        ``t_k = (alpha - alpha0)^k / k!``, ``V = derivs_cov(order)`` (named after ``MBARModel.predict_with_error``; the
-        assumptions of ``derivs_cov`` apply: independent samples, first order)."""
+        ``t_k = (alpha - alpha0)^k / k!``, ``V = derivs_cov(order, block=block)`` (named after
+        ``MBARModel.predict_with_error``; the assumptions of ``derivs_cov`` apply: first order, and independent samples
+        unless a ``block`` longer than the correlation time is given)."""
         if order is None:
             order = self.order
         if minus_log is None:
             minus_log = self.minus_log
-        cov, src = self._derivs_cov_device(order, bool(minus_log))
+        cov, src = self._derivs_cov_device(order, bool(minus_log), block)
         pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name)
         dalpha = xrwrap_alpha(alpha, name=alpha_name or self.alpha_name) - self.alpha0
         d = np.asarray(dalpha.values, dtype=np.float64).reshape(-1)
@@ -710,7 +764,18 @@ class StateCollection(_Params):
                 return None
         return key
 
-    def _derivs_cov_fill(self, order=None, minus_log=None):
+    def _blocks_per_state(self, block):
+        """``block`` of the blocked error bars as one entry per state (None: the iid path): an int serves every state, a
+        sequence gives each state its own -- states have different correlation times."""
+        if block is None:
+            return None
+        if isinstance(block, (str, bytes)) or not hasattr(block, "__len__"):
+            return [_check_block_type(block)] * len(self)
+        if len(block) != len(self):
+            raise ValueError(f"block must be an int or hold one entry per state: len(block)={len(block)}, {len(self)} states")
+        return [_check_block_type(b) for b in block]
+
+    def _derivs_cov_fill(self, order=None, minus_log=None, block=None):
         """Fill every state's ``("dcov", order, minus_log)`` cache -- what ``ExtrapModel._derivs_cov_device`` computes,
         bit for bit -- and return ``(cov [S, n_out, order + 1, order + 1] on the device, sources, order)``.
         Eligible states (``_delta_batch_eligible``): ONE copy of the stacked central states to the host, the
@@ -718,9 +783,13 @@ class StateCollection(_Params):
 
         The host algebra runs state by state although symbolic.influence_coefs broadcasts: the single path hands it
         ``<u>`` as a Python float, and ``float ** int`` need not round like ``ndarray ** int`` (it matters in the raw
-        form, which expands about zero), so only the per-state call is certain to give the single call's coefficients."""
+        form, which expands about zero), so only the per-state call is certain to give the single call's coefficients.
+
+        With ``block`` (``_blocks_per_state``) the states are looped on the single blocked entry point, each with its own
+        block length; the iid caches are neither read nor written."""
         sts = self.states
-        if self._delta_batch_eligible() is not None:
+        blocks = self._blocks_per_state(block)
+        if blocks is None and self._delta_batch_eligible() is not None:
             o = sts[0].order if order is None else order
             ml = bool(sts[0].minus_log if minus_log is None else minus_log)
             key = ("dcov", o, ml)
@@ -741,17 +810,18 @@ class StateCollection(_Params):
             parts = [st._derivs_cov_device(o, ml) for st in sts]
             return torch.stack([p_[0] for p_ in parts]), [p_[1] for p_ in parts], o
         parts, orders = [], []
-        for st in sts:
+        for s, st in enumerate(sts):
             if not hasattr(st, "_derivs_cov_device"):
                 raise NotImplementedError(f"derivs_cov / predict_with_error (delta-method error bars): unsupported state "
                                           f"{type(st).__name__}")
             o = st.order if order is None else order
-            parts.append(st._derivs_cov_device(o, bool(st.minus_log if minus_log is None else minus_log)))
+            ml = bool(st.minus_log if minus_log is None else minus_log)
+            parts.append(st._derivs_cov_device(o, ml) if blocks is None else st._derivs_cov_device(o, ml, blocks[s]))
             orders.append(o)
         same = len(set(orders)) == 1 and len({tuple(p_[0].shape) for p_ in parts}) == 1
         return (torch.stack([p_[0] for p_ in parts]) if same else None), [p_[1] for p_ in parts], orders[0]
 
-    def derivs_cov(self, order=None, norm=False, minus_log=None):
+    def derivs_cov(self, order=None, norm=False, minus_log=None, block=None):
         """Every state's ``derivs_cov`` joined along the states: bit for bit
         ``map_concat(lambda m: m.derivs_cov(order, norm, minus_log))``.  The states are independent simulations, so the
         covariance of anything linear in their derivatives is block diagonal in these per-state blocks.
@@ -759,22 +829,31 @@ class StateCollection(_Params):
         States that share a column shape, order and derivatives object -- with ANY number of samples each, as
         ``timeseries.decorrelate`` leaves them -- are served by one launch per kernel (txm_influence_cov_batched) after one
         copy of their moments to the host; other collections loop.  Either way every state's own ``derivs_cov()`` is
-        answered from its cache afterwards.  Assumptions: those of ``ExtrapModel.derivs_cov``."""
-        cov, srcs, o = self._derivs_cov_fill(order, minus_log)
+        answered from its cache afterwards.  Assumptions: those of ``ExtrapModel.derivs_cov``.
+
+        ``block`` (an int for all states, or one entry per state) gives the blocked error bars of correlated series
+        (``ExtrapModel.derivs_cov(block=...)``): the states are looped on the single blocked entry point; ``block=None``
+        leaves the path above untouched."""
+        cov, srcs, o = self._derivs_cov_fill(order, minus_log, block)
         if cov is None:
-            return self.map_concat(lambda m: m.derivs_cov(order=order, norm=norm, minus_log=minus_log))
-        host = cov.cpu().numpy()
-        out = [st._ds(ExtrapModel._derivs_cov_labelled(host[s], srcs[s], o, norm)) for s, st in enumerate(self.states)]
+            if block is None:
+                return self.map_concat(lambda m: m.derivs_cov(order=order, norm=norm, minus_log=minus_log))
+            blocks = self._blocks_per_state(block)
+            out = [m.derivs_cov(order=order, norm=norm, minus_log=minus_log, block=blocks[s]) for s, m in enumerate(self.states)]
+        else:
+            host = cov.cpu().numpy()
+            out = [st._ds(ExtrapModel._derivs_cov_labelled(host[s], srcs[s], o, norm)) for s, st in enumerate(self.states)]
         if is_labelled(out[0]):
             out = concat(out, dim=DataArray(np.asarray(self.alpha0), self.alpha_name))
         return out
 
-    def _state_covs(self, order, minus_log):
+    def _state_covs(self, order, minus_log, block=None):
         """Host copies of the states' delta-method covariances, [S][n_out, order + 1, order + 1], and their sources."""
-        cov, srcs, _ = self._derivs_cov_fill(order, minus_log)
+        cov, srcs, _ = self._derivs_cov_fill(order, minus_log, block)
         if cov is None:
-            return [st._derivs_cov_device(order, bool(st.minus_log if minus_log is None else minus_log))[0].cpu().numpy()
-                    for st in self.states], srcs
+            blocks = self._blocks_per_state(block) or [None] * len(self)
+            return [st._derivs_cov_device(order, bool(st.minus_log if minus_log is None else minus_log), blocks[s])[0].cpu().numpy()
+                    for s, st in enumerate(self.states)], srcs
         return list(cov.cpu().numpy()), srcs
 
     # states per launch of the batched path: the sampler table is [S * nrep][ntiles] and the grid carries the state on z
@@ -1172,7 +1251,7 @@ class ExtrapWeightedModel(StateCollection, PiecewiseMixin):
         num = sum(p * w.isel(state=i) for i, p in enumerate(preds))
         return num / w.sum("state")
 
-    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None, method=None, bounded=False):
+    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None, method=None, bounded=False, block=None):
         """``(predict(alpha, ...), std)``: the blended prediction, bit for bit ``predict``'s, and its delta-method
         standard deviation.  The blend is ``sum_i w_i T_i(alpha) / sum_i w_i`` over the two states ``predict`` picks
         (``method``, ``bounded`` as there), with the Minkowski weights ``w_i`` a function of alpha alone, so
@@ -1181,13 +1260,14 @@ class ExtrapWeightedModel(StateCollection, PiecewiseMixin):
 
         Assumptions: independent samples within a state (``ExtrapModel.derivs_cov``), independent states (no cross
         terms), first order.  All states' ``V_i`` come from one launch per kernel (``StateCollection.derivs_cov``); a state
-        that ``derivs_cov`` refuses raises its NotImplementedError."""
+        that ``derivs_cov`` refuses raises its NotImplementedError.  ``block`` (an int, or one entry per state): the
+        blocked ``V_i`` of correlated series (``StateCollection.derivs_cov``)."""
         self._check_alpha(alpha, bounded)
         if order is None:
             order = self.order
         if alpha_name is None:
             alpha_name = self.alpha_name
-        covs, srcs = self._state_covs(order, minus_log)                # (first: an unsupported state says so)
+        covs, srcs = self._state_covs(order, minus_log, block)         # (first: an unsupported state says so)
         pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name, method=method, bounded=bounded)
         al = xrwrap_alpha(alpha, name=alpha_name)
         a0 = np.asarray(self.alpha0, dtype=np.float64)
@@ -1252,9 +1332,9 @@ class InterpModel(StateCollection):
         p = DataArray(np.arange(coefs.sizes[order_dim]), order_dim)
         return ((alpha**p) * coefs).sum(order_dim)
 
-    def _predict_std(self, alpha, order, minus_log, alpha_name):
+    def _predict_std(self, alpha, order, minus_log, alpha_name, block=None):
         """Delta-method standard deviation of ``predict(alpha)`` (see ``predict_with_error``)."""
-        covs, srcs = self._state_covs(order, minus_log)                # [S][n_out, order + 1, order + 1]
+        covs, srcs = self._state_covs(order, minus_log, block)              # [S][n_out, order + 1, order + 1]
         inv = self._hermite_inverse(order)                              # [porder, state * (order + 1)]
         al = xrwrap_alpha(alpha, name=alpha_name)
         av = np.asarray(al.values, dtype=np.float64).reshape(-1)
@@ -1267,7 +1347,7 @@ class InterpModel(StateCollection):
         std._inherit(src.coords)
         return self[0]._ds(std)
 
-    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None):
+    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None, block=None):
         """``(predict(alpha), std)``: the interpolation, bit for bit ``predict``'s, and its delta-method standard
         deviation.  ``predict`` is linear in the states' un-normalised derivatives D (stacked state by state):
         ``g(alpha)' D`` with ``g = (alpha^p) . hermite_inverse``, so
@@ -1276,12 +1356,13 @@ class InterpModel(StateCollection):
 
         Assumptions: independent samples within a state (``ExtrapModel.derivs_cov``: decorrelate time series first),
         independent states (the covariance of D is block diagonal), first order.  All ``V_s`` come from one launch per
-        kernel (``StateCollection.derivs_cov``); a state that ``derivs_cov`` refuses raises its NotImplementedError."""
+        kernel (``StateCollection.derivs_cov``); a state that ``derivs_cov`` refuses raises its NotImplementedError.
+        ``block`` (an int, or one entry per state): the blocked ``V_s`` of correlated series kept whole."""
         if order is None:
             order = self.order
         if alpha_name is None:
             alpha_name = self.alpha_name
-        std = self._predict_std(alpha, order, minus_log, alpha_name)    # (first: an unsupported state says so)
+        std = self._predict_std(alpha, order, minus_log, alpha_name, block)    # (first: an unsupported state says so)
         return self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name), std
 
 
@@ -1309,24 +1390,28 @@ class InterpModelPiecewise(StateCollection, PiecewiseMixin):
             return outs[0]
         return concat(outs, dim=DataArray(np.asarray(seq), alpha_name))
 
-    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None, method=None, bounded=False):
+    def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None, method=None, bounded=False, block=None):
         """``(predict(alpha, ...), std)``: for every alpha the two-state ``InterpModel`` that ``predict`` chooses
         (``method``, ``bounded`` as there) and that model's ``predict_with_error`` -- its assumptions apply: independent
         samples within a state, independent states, first order.  The covariances of ALL states are taken first, in one
-        launch per kernel, so the pairs find them in their states' caches."""
+        launch per kernel, so the pairs find them in their states' caches.  ``block`` (an int, or one entry per state):
+        the blocked covariances of correlated series; a pair takes its two states' entries."""
         self._check_alpha(alpha, bounded)
-        self._derivs_cov_fill(order, minus_log)                         # (first: an unsupported state says so)
+        blocks = self._blocks_per_state(block)
+        self._derivs_cov_fill(order, minus_log, block)                  # (first: an unsupported state says so)
         pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name, method=method, bounded=bounded)
         if alpha_name is None:
             alpha_name = self.alpha_name
 
-        def std_of(pair, a):
-            return pair._predict_std(a, pair.order if order is None else order, minus_log, alpha_name)
+        def std_of(idx, a):
+            pair = self.single_interpmodel(*idx)
+            return pair._predict_std(a, pair.order if order is None else order, minus_log, alpha_name,
+                                     None if blocks is None else [blocks[int(i)] for i in idx])
 
         if len(self) == 2:
-            return pred, std_of(self.single_interpmodel(0, 1), alpha)
+            return pred, std_of((0, 1), alpha)
         seq = [float(a) for a in _alpha_seq(alpha)]
-        outs = [std_of(self.single_interpmodel(*self._indices_alpha(a, method)), a) for a in seq]
+        outs = [std_of(self._indices_alpha(a, method), a) for a in seq]
         if len(outs) == 1:
             return pred, outs[0]
         return pred, concat(outs, dim=DataArray(np.asarray(seq), alpha_name))
@@ -1449,7 +1534,7 @@ class MBARModel(StateCollection):
             raise ValueError("alpha must be a scalar or 1-D")
         return avals, alpha_name
 
-    def derivs_cov(self, order=None, norm=False, minus_log=None):
+    def derivs_cov(self, order=None, norm=False, minus_log=None, block=None):
         raise NotImplementedError("derivs_cov (delta-method error bars of the states' derivatives): MBARModel predicts "
                                   "from the pooled samples, not from derivatives; its error bars are predict_with_error")
 
