@@ -695,6 +695,32 @@ int txm_influence_block_cov(const double *x, int64_t ldx_s, const double *u, con
                             int64_t block, int n_levels, double *cov, double *mean, void *ws, size_t ws_bytes,
                             txm_stream stream);
 
+/* ---- (f-12) delta-method covariance ACROSS the observable columns: every block Cov(estimate i of c, estimate j of c') -- */
+/* The operands of (f-9) for x row-major with pitch ldx_s >= C (w may be NULL) and C <= 255.  With p_n = w_n / sum w and
+ * psi_k(n, c) as in (f-9),
+ *     cov[c][i][c'][j] = sum_n p_n^2 psi_i(n, c) psi_j(n, c')                      c, c' < C;  i, j < n_f <= 9;  n_q <= 9
+ * -- the (C n_f) x (C n_f) infinitesimal-jackknife covariance of ALL estimates of ALL columns, which share one u and one
+ * set of samples: what a sum over bins, a ratio of two observables or a multi-output model needs.  The device array cov
+ * [C][n_f][C][n_f] is symmetric as a (C n_f)^2 matrix, [c][i][c'][j] and [c'][j][c][i] holding the same bits; its blocks
+ * c == c' are the cov of (f-9) within the two calls' rounding bounds (another summation order, not the same bits).  There
+ * is no `mean` output.  Independent samples are assumed, as in (f-9); there is no blocked form yet.
+ * psi psi' depends on (q, q') only through r = q + q', so the sample pass needs no coefficients: it accumulates the
+ * 2 n_q - 1 Gram matrices  G_r = sum_n w_n^2 du^r z_n z_n^T,  z_n = (dx_n0 .. dx_n,C-1, 1),  on the FP64 matrix pipe
+ * (v_mfma_f64_16x16x4_f64) in tiles of 16 x 16 over the C + 1 logical columns, upper-triangle tile pairs only, one record
+ * per (workgroup, tile pair) in the workspace.  A second kernel adds the workgroups in index order and a third contracts
+ * with a, b in one fixed order, reading G at (row <= column) only and storing every entry with its mirror.  No
+ * floating-point atomics: two calls give the same bits.  The bits depend on N (the samples' assignment to waves does).
+ * A row of weight zero is selected out and may hold anything; total weight zero gives zeros.
+ * First-order rounding bound: eps * sum_n p_n^2 B_i(n, c) B_j(n, c'), B_k as in (f-9).
+ * Workspace: txm_influence_cross_cov_ws_bytes(N, C, n_f, n_q), host logic, nondecreasing in C, 0 for bad arguments (at
+ * most 8 (256 (2 n_q - 1) + 8) (8 workgroups per CU + 2 * tile pairs) + 256 bytes: 76 MB at C = 255, order 8).
+ * Null pointers, N < 1, C outside [1, 255], n_f or n_q outside [1, 9], ldx_s < C and a NaN center_u return
+ * TXM_ERR_INVALID, a short workspace TXM_ERR_WORKSPACE, all before anything is enqueued. */
+size_t txm_influence_cross_cov_ws_bytes(int64_t N, int64_t C, int n_f, int n_q);
+int txm_influence_cross_cov(const double *x, int64_t ldx_s, const double *u, const double *w, int64_t N, int64_t C,
+                            int n_f, int n_q, double center_u, const double *center_x, const double *a, const double *b,
+                            double *cov, void *ws, size_t ws_bytes, txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,274 @@
+// txm_influence_cross.hip -- the delta-method covariance of txm_influence.hip ACROSS observable columns
+// (ExtrapModel.derivs_cross_cov / predict_cov).
+//
+// With the influence polynomials of txm_influence.hip,
+//      psi_k(n, c) = sum_q (a[c][k][q] + b[c][k][q] dx_nc) du_n^q,   dx_nc = x[n][c] - center_x[c],  du_n = u[n] - center_u,
+// the caller wants every block of
+//      cov[c][i][c'][j] = sum_n w_n^2 psi_i(n, c) psi_j(n, c') / (sum_n w_n)^2           ((C n_f)^2, symmetric).
+//
+// psi psi' depends on (q, q') through r = q + q' alone (a Hankel structure), so the sample pass needs no coefficient:
+// it accumulates the R = 2 n_q - 1 weighted Gram matrices
+//      G_r = sum_n w_n^2 du_n^r z_n z_n^T,     z_n = (dx_n0, ..., dx_n,C-1, 1)           (C + 1 logical columns)
+// and a finalize contracts them:  sum_{q,q'} a a' G_r[1][1] + a b' G_r[1][c'] + b a' G_r[c][1] + b b' G_r[c][c'],  where
+// index 1 stands for the column of ones -- logical column C, BEHIND the observables, so that every entry the finalize
+// needs lies at (row <= column).  G_r[1][1] is txm_influence_cov's T_0, the border G_r[c][1] its T_1, the diagonal of the
+// C x C block its T_2; the off-diagonal of that block is what is new.
+//
+// The Grams are FP64 matrix-pipe work (v_mfma_f64_16x16x4_f64; operand layout as txm_mbar_cov.hip phase 2).  The
+// C + 1 logical columns are cut into T = ceil((C + 1) / 16) tiles of 16; only tile pairs (ti <= tj) are computed.
+//   influence_cross_kernel   grid (tile pairs, sample workgroups) -- the pair is the fast index, so the workgroups that
+//                            read the same rows are dispatched together.  A wave owns samples 4 at a time: lane
+//                            (m = lane & 15, k = lane >> 4) holds A[m][k] = w^2 du^r z_{16 ti + m} and
+//                            B[k][m] = z_{16 tj + m} of sample k of the step.  One MFMA per r into the accumulator tile
+//                            of G_r; from r to r + 1 the A operand is multiplied by du once.  R accumulator tiles of
+//                            8 VGPRs live in the wave (R = 7 at order 3 ... 17 at order 8).  At the end the four waves'
+//                            tiles are added in wave order through LDS: one record per (workgroup, tile pair).
+//                            The total weight sum_n w_n rides on the VALU (lanes m == 0) behind the tiles of the record.
+//   influence_cross_sum_kernel     adds the workgroups' records in index order into one record per tile pair.
+//   influence_cross_final_kernel   a thread per pair of outputs {(c,i), (c',j)} with (c,i) <= (c',j): reads G at
+//                            (row <= column) only -- inside a diagonal tile the MFMA rounds (m,n) and (n,m) differently
+//                            -- contracts in one fixed order, divides by (sum w)^2 and stores the entry and its mirror.
+// No floating-point atomics: two calls give the same bits.  A row of weight zero is selected out (its operands are set
+// to zero, not multiplied by zero) and may hold anything; total weight zero gives zeros.
+// Rounding: every product of the expansion is bounded by the matching product of B_k(n, c) = sum_q (|a| + |b| |dx|) |du|^q,
+// so the first-order bound is eps * sum_n p_n^2 B_i(n, c) B_j(n, c'),  p_n = w_n / sum w.
+#include "txm_common.h"
+
+namespace txm {
+
+typedef double cx_v4d __attribute__((ext_vector_type(4)));
+
+constexpr int CX_BLOCK = 256;  // four waves
+constexpr int CX_SHARE = 256;  // samples a workgroup takes before the grid grows by one workgroup
+constexpr int CX_MAXC = 255;   // C + 1 logical columns <= 256: at most 16 tiles a side
+constexpr int CX_UNR = 4;      // 4-sample steps a wave has in flight
+
+// doubles of one (workgroup, tile pair) record: R tiles of 16 x 16, then the total weight (padded to 8)
+__host__ __device__ constexpr int cx_rec(int n_q) { return (2 * n_q - 1) * 256 + 8; }
+
+// tile pair p of the upper triangle in row order: (0,0) (0,1) ... (0,T-1) (1,1) ...
+__device__ __forceinline__ void cx_pair(int p, int T, int &ti, int &tj) {
+  ti = 0;
+  while (p >= T - ti) {
+    p -= T - ti;
+    ++ti;
+  }
+  tj = ti + p;
+}
+
+__host__ __device__ __forceinline__ int cx_pair_index(int ti, int tj, int T) { return ti * T - ti * (ti - 1) / 2 + (tj - ti); }
+
+// partial [gridDim.y sample workgroups][gridDim.x tile pairs][cx_rec]
+template <int NQ, bool WEIGHTED>
+__global__ __launch_bounds__(CX_BLOCK) void influence_cross_kernel(const double *__restrict__ x, int64_t ldx_s,
+                                                                   const double *__restrict__ u,
+                                                                   const double *__restrict__ w, int64_t N, int C, int T,
+                                                                   double cu, const double *__restrict__ cx,
+                                                                   double *__restrict__ partial) {
+  constexpr int R = 2 * NQ - 1, REC = cx_rec(NQ);
+  __shared__ double red[4 * 256];
+  __shared__ double sws[16];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, k4 = lane >> 4;
+  int ti, tj;
+  cx_pair((int)blockIdx.x, T, ti, tj);
+  const bool diag = ti == tj;
+  // logical columns of this lane's A row and B column: < C an observable, C the ones, above it nothing
+  const int ca = 16 * ti + m, cb = 16 * tj + m;
+  const bool a_x = ca < C, b_x = cb < C;
+  const double a_one = ca == C ? 1.0 : 0.0, b_one = cb == C ? 1.0 : 0.0;
+  const double pa = a_x ? cx[ca] : 0.0, pb = b_x ? cx[cb] : 0.0;
+
+  cx_v4d acc[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = cx_v4d{0.0, 0.0, 0.0, 0.0};
+  double sw = 0.0;
+
+  // wave wg of NW takes the 4-sample steps wg, wg + NW, ...; the loop bounds are wave-uniform
+  const int64_t NW = (int64_t)gridDim.y * 4, stride = NW * 4;
+  for (int64_t ib = ((int64_t)blockIdx.y * 4 + wave) * 4; ib < N; ib += CX_UNR * stride) {
+    double ui[CX_UNR], wi[CX_UNR], xa[CX_UNR], xb[CX_UNR];
+    bool ok[CX_UNR];
+#pragma unroll
+    for (int s = 0; s < CX_UNR; ++s) {
+      const int64_t i = ib + s * stride + k4;
+      ok[s] = i < N;
+      const int64_t ic = ok[s] ? i : 0;  // (a row that exists: the value is selected out below)
+      ui[s] = u[ic];
+      wi[s] = WEIGHTED ? w[ic] : 1.0;
+      xa[s] = a_x ? x[ic * ldx_s + ca] : 0.0;
+      xb[s] = diag ? xa[s] : (b_x ? x[ic * ldx_s + cb] : 0.0);
+    }
+#pragma unroll
+    for (int s = 0; s < CX_UNR; ++s) {
+      const bool live = ok[s] && (!WEIGHTED || wi[s] != 0.0);
+      const double du = live ? ui[s] - cu : 0.0;
+      const double za = live ? (a_x ? xa[s] - pa : a_one) : 0.0;
+      const double zb = live ? (b_x ? xb[s] - pb : b_one) : 0.0;
+      const double wl = live ? wi[s] : 0.0;
+      sw += wl;
+      double av = wl * wl * za;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, zb, acc[r], 0, 0, 0);
+        av *= du;
+      }
+    }
+  }
+
+  // the four waves' tiles in wave order.  D layout: column = lane & 15, row = (lane >> 4) + 4 * reg
+  double *dst = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * REC;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) red[wave * 256 + (k4 + 4 * g) * 16 + m] = acc[r][g];
+    __syncthreads();
+    dst[r * 256 + tid] = ((red[tid] + red[256 + tid]) + red[512 + tid]) + red[768 + tid];
+    __syncthreads();
+  }
+  // total weight: the lanes m == 0 of a wave hold its four sample slots
+  if (m == 0) sws[wave * 4 + k4] = sw;
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += sws[q];
+    dst[R * 256] = s;
+  }
+}
+
+// G[e] = sum over the nblk workgroups, in index order, of partial[blk][e]      (e < per_blk = pairs * REC)
+__global__ __launch_bounds__(CX_BLOCK) void influence_cross_sum_kernel(const double *__restrict__ partial, int nblk,
+                                                                       size_t per_blk, double *__restrict__ G) {
+  const size_t e = (size_t)blockIdx.x * CX_BLOCK + threadIdx.x;
+  if (e >= per_blk) return;
+  double acc = 0.0;
+  for (int b = 0; b < nblk; ++b) acc += partial[(size_t)b * per_blk + e];
+  G[e] = acc;
+}
+
+// cov [C n_f][C n_f]; a thread per (P, Q) = ((c, i), (c', j)), the threads with P <= Q compute and store both
+template <int NQ>
+__global__ __launch_bounds__(CX_BLOCK) void influence_cross_final_kernel(const double *__restrict__ G, int C, int T,
+                                                                         int n_f, const double *__restrict__ a,
+                                                                         const double *__restrict__ b,
+                                                                         double *__restrict__ cov) {
+  constexpr int R = 2 * NQ - 1, REC = cx_rec(NQ);
+  const size_t M = (size_t)C * n_f;
+  const size_t e = (size_t)blockIdx.x * CX_BLOCK + threadIdx.x;
+  if (e >= M * M) return;
+  const size_t P = e / M, Q = e % M;
+  if (P > Q) return;
+  const int c = (int)(P / n_f), i = (int)(P % n_f), d = (int)(Q / n_f), j = (int)(Q % n_f);  // c <= d
+  // G_r at (row, col), row <= col, as logical columns: the ones are column C
+  auto at = [&](int row, int col) {
+    return G + (size_t)cx_pair_index(row >> 4, col >> 4, T) * REC + (row & 15) * 16 + (col & 15);
+  };
+  const double *g11 = at(C, C), *g1d = at(d, C), *gc1 = at(c, C), *gcd = at(c, d);
+  double t11[R], t1d[R], tc1[R], tcd[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    t11[r] = g11[r * 256];
+    t1d[r] = g1d[r * 256];
+    tc1[r] = gc1[r * 256];
+    tcd[r] = gcd[r * 256];
+  }
+  const double *ai = a + (P * NQ), *bi = b + (P * NQ), *aj = a + (Q * NQ), *bj = b + (Q * NQ);
+  double s = 0.0;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const double aiq = ai[q], biq = bi[q];
+#pragma unroll
+    for (int p = 0; p < NQ; ++p) {
+      const double ajp = aj[p], bjp = bj[p];
+      s += ((aiq * ajp * t11[q + p] + aiq * bjp * t1d[q + p]) + biq * ajp * tc1[q + p]) + biq * bjp * tcd[q + p];
+    }
+  }
+  const double W = G[R * 256];  // the record of tile pair 0
+  const double v = W == 0.0 ? 0.0 : s / (W * W);
+  cov[P * M + Q] = v;
+  cov[Q * M + P] = v;
+}
+
+struct CxPlan {
+  int T, pairs, grid_x;
+};
+
+// One workgroup per CX_SHARE samples and tile pair, up to about eight workgroups per CU in all; the rest is strided.
+static CxPlan cx_plan(int64_t N, int64_t C) {
+  CxPlan p{};
+  p.T = (int)((C + 1 + 15) / 16);
+  p.pairs = p.T * (p.T + 1) / 2;
+  int64_t cap = (int64_t)num_cus() * 8 / p.pairs;
+  if (cap < 1) cap = 1;
+  const int64_t gx = cdiv(N, CX_SHARE);
+  p.grid_x = (int)(gx > cap ? cap : gx);
+  return p;
+}
+
+// records of partials the plan can ask for, nondecreasing in C: grid_x * pairs <= min(shares * pairs, max(cap, pairs))
+static size_t cx_ws_records(int64_t N, int64_t C) {
+  const CxPlan p = cx_plan(N, C);
+  const int64_t cap = (int64_t)num_cus() * 8, shares = cdiv(N, CX_SHARE);
+  const int64_t hi = cap > p.pairs ? cap : p.pairs;
+  const int64_t part = shares <= hi / p.pairs ? shares * p.pairs : hi;  // (no overflow for N near 2^63)
+  return (size_t)part + (size_t)p.pairs;                                 // the partials, then the summed records
+}
+
+template <int NQ>
+static int cx_launch(const CxPlan &p, const double *x, int64_t ldx_s, const double *u, const double *w, int64_t N, int C,
+                     int n_f, double cu, const double *cx, const double *a, const double *b, double *cov, double *ws,
+                     hipStream_t st) {
+  const size_t per_blk = (size_t)p.pairs * cx_rec(NQ);
+  double *partial = ws, *G = ws + (size_t)p.grid_x * per_blk;
+  const dim3 grid(p.pairs, p.grid_x), block(CX_BLOCK);
+  if (w)
+    hipLaunchKernelGGL((influence_cross_kernel<NQ, true>), grid, block, 0, st, x, ldx_s, u, w, N, C, p.T, cu, cx, partial);
+  else
+    hipLaunchKernelGGL((influence_cross_kernel<NQ, false>), grid, block, 0, st, x, ldx_s, u, w, N, C, p.T, cu, cx, partial);
+  TXM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(influence_cross_sum_kernel, dim3((unsigned)cdiv((int64_t)per_blk, CX_BLOCK)), block, 0, st, partial,
+                     p.grid_x, per_blk, G);
+  TXM_LAUNCH_CHECK();
+  const int64_t M = (int64_t)C * n_f;
+  hipLaunchKernelGGL((influence_cross_final_kernel<NQ>), dim3((unsigned)cdiv(M * M, CX_BLOCK)), block, 0, st, G, C, p.T, n_f,
+                     a, b, cov);
+  TXM_LAUNCH_CHECK();
+  return TXM_OK;
+}
+
+}  // namespace txm
+
+using namespace txm;
+
+extern "C" size_t txm_influence_cross_cov_ws_bytes(int64_t N, int64_t C, int n_f, int n_q) {
+  if (N < 1 || C < 1 || C > CX_MAXC || n_f < 1 || n_f > TXM_MAXK || n_q < 1 || n_q > TXM_MAXK) return 0;
+  return cx_ws_records(N, C) * (size_t)cx_rec(n_q) * sizeof(double) + 256;
+}
+
+extern "C" int txm_influence_cross_cov(const double *x, int64_t ldx_s, const double *u, const double *w, int64_t N,
+                                       int64_t C, int n_f, int n_q, double center_u, const double *center_x,
+                                       const double *a, const double *b, double *cov, void *ws, size_t ws_bytes,
+                                       txm_stream stream) {
+  TXM_REQUIRE(x && u && center_x && a && b && cov && ws, "influence_cross_cov: null pointer");
+  TXM_REQUIRE(N >= 1 && C >= 1, "influence_cross_cov: need N >= 1 and C >= 1 (N=%lld C=%lld)", (long long)N, (long long)C);
+  TXM_REQUIRE(C <= CX_MAXC, "influence_cross_cov: C > %d unsupported (the result has (C n_f)^2 entries)", CX_MAXC);
+  TXM_REQUIRE(n_f >= 1 && n_f <= TXM_MAXK, "influence_cross_cov: n_f=%d outside [1, %d]", n_f, TXM_MAXK);
+  TXM_REQUIRE(n_q >= 1 && n_q <= TXM_MAXK, "influence_cross_cov: n_q=%d outside [1, %d]", n_q, TXM_MAXK);
+  TXM_REQUIRE(ldx_s >= C, "influence_cross_cov: row pitch ldx_s < C");
+  TXM_REQUIRE(center_u == center_u, "influence_cross_cov: center_u is NaN");
+  if (ws_bytes < txm_influence_cross_cov_ws_bytes(N, C, n_f, n_q)) {
+    set_error("influence_cross_cov: workspace too small");
+    return TXM_ERR_WORKSPACE;
+  }
+  const CxPlan p = cx_plan(N, C);
+  hipStream_t st = (hipStream_t)stream;
+  switch (n_q) {
+#define TXM_CX_CASE(Q) \
+  case Q: return cx_launch<Q>(p, x, ldx_s, u, w, N, (int)C, n_f, center_u, center_x, a, b, cov, (double *)ws, st);
+    TXM_CX_CASE(1) TXM_CX_CASE(2) TXM_CX_CASE(3) TXM_CX_CASE(4) TXM_CX_CASE(5)
+    TXM_CX_CASE(6) TXM_CX_CASE(7) TXM_CX_CASE(8) TXM_CX_CASE(9)
+#undef TXM_CX_CASE
+  }
+  set_error("influence_cross_cov: n_q out of range");
+  return TXM_ERR_INVALID;
+}

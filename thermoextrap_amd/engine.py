@@ -911,6 +911,39 @@ def influence_block_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: to
     return cov, mean
 
 
+CROSS_COV_MAX_COLUMNS = 255  # include/txmom.h (f-12): C + 1 logical columns in at most 16 tiles a side
+
+
+def influence_cross_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: torch.Tensor, center_u: float,
+                        center_x: torch.Tensor, w: torch.Tensor | None = None) -> torch.Tensor:
+    """Delta-method covariance ACROSS the columns (txm_influence_cross_cov): with psi_k(n, c) as in ``influence_cov`` and
+    p = w / sum w, ``cov[c, i, c', j] = sum_n p_n^2 psi_i(n, c) psi_j(n, c')`` -- every block of the (C n_f)^2 matrix,
+    bitwise symmetric, from one pass over x on the FP64 matrix pipe.  x: (N, C) or (N,), copied to row-major if it is
+    not; a, b: (C, n_f, n_q); center_x: (C,); C <= 255.  Returns ``cov [C, n_f, C, n_f]`` on the device.  Independent
+    samples are assumed (there is no blocked form)."""
+    L = _L()
+    x2, ls, _, u, w, N, C, _ = _operands(x, u, w, "rowmajor")
+    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
+        _check_f64_cuda(t, name)
+    if a.dim() != 3 or a.shape[0] != C or b.shape != a.shape:
+        raise ValueError(f"a and b must both have shape ({C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
+    if center_x.shape != (C,):
+        raise ValueError(f"center_x must have shape ({C},), got {tuple(center_x.shape)}")
+    if C > CROSS_COV_MAX_COLUMNS:
+        raise ValueError(f"influence_cross_cov: C = {C} columns, the limit is {CROSS_COV_MAX_COLUMNS} (the result has "
+                         "(C n_f)^2 entries)")
+    _, n_f, n_q = a.shape
+    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
+    cov = torch.empty((C, n_f, C, n_f), dtype=F64, device="cuda")
+    ws = workspace(L.txm_influence_cross_cov_ws_bytes(N, C, n_f, n_q))
+    check(
+        L.txm_influence_cross_cov(_ptr(x2), ls, _ptr(u), _ptr(w), N, C, n_f, n_q, float(center_u), _ptr(center_x), _ptr(a),
+                                  _ptr(b), _ptr(cov), _ptr(ws), ws.numel(), _stream()),
+        "txm_influence_cross_cov",
+    )
+    return cov
+
+
 TAYLOR_MODES ={"sum": 0, "cumsum": 1, "terms": 2}
 
 

@@ -679,6 +679,81 @@ class ExtrapModel(_Params):
         std._inherit(src.coords)
         return pred, self._ds(std)
 
+    # ---- the same across the observable columns ---------------------------------------------------------
+    def _derivs_cross_cov_device(self, order, minus_log):
+        """``(cov [n_out, order + 1, n_out, order + 1] on the device, source)`` from ONE ``engine.influence_cross_cov``,
+        cached under a key of its own: the per-column entry ``("dcov", ...)`` is neither read nor written."""
+        key = ("dxcov", order, minus_log)
+        if key not in self._cache:
+            x2, ut, wt, st, src = self._delta_operands()         # (first: an unsupported model says so, whatever its width)
+            if x2.shape[1] > engine.CROSS_COV_MAX_COLUMNS:
+                raise ValueError(f"derivs_cross_cov / predict_cov: {x2.shape[1]} observable columns, the limit is "
+                                 f"{engine.CROSS_COV_MAX_COLUMNS} (the result has (columns * (order + 1))^2 entries)")
+            a, b, um, xm = self._delta_coefs(st, order, minus_log)
+            cov = engine.influence_cross_cov(x2, ut, engine.to_device(a), engine.to_device(b), um, engine.to_device(xm), w=wt)
+            self._cache[key] = (cov, src)
+        return self._cache[key]
+
+    @staticmethod
+    def _cross_labels(out, src):
+        """The coordinates of the value dims on ``out``, and their copies under the ``_2`` names."""
+        out._inherit(src.coords)
+        out._inherit({k + "_2": (tuple(d + "_2" for d in cd), cv) for k, (cd, cv) in src.coords.items()})
+        return out
+
+    def derivs_cross_cov(self, order=None, norm=False, minus_log=None):
+        """Delta-method covariance of ``derivs(order)`` ACROSS the observable columns: dims
+        ``(order, order_2, *val_dims, *[d + "_2" for d in val_dims])`` with
+
+            ``V[i, j, c, c'] = sum_n p_n^2 psi_i(n, c) psi_j(n, c')``
+
+        -- the off-diagonal blocks ``Cov(d_i of column c, d_j of column c')`` that ``derivs_cov`` does not hold and that
+        any quantity combining columns needs: an integral over the bins of a profile, a sum of tensor components, a
+        ratio of two observables.  The columns share one energy series and one set of samples, so these blocks are
+        large.  ONE pass over the samples (txm_influence_cross_cov, Gram matrices on the FP64 matrix pipe) -- no
+        replicates, no sampling noise.  The blocks ``c == c'`` are ``derivs_cov(order)`` up to rounding (another order of
+        summation), and the result is exactly symmetric under ``(i, c) <-> (j, c')``.  ``norm=True`` carries the
+        ``1 / (i! j!)`` factors of ``derivs(norm=True)``; ``minus_log`` acts per column as in ``derivs_cov``.
+
+        The assumptions and the supported models are those of ``derivs_cov`` (first order, INDEPENDENT samples; anything
+        else raises the same NotImplementedError), with at most 255 observable columns (ValueError beyond).  Out of
+        scope here: ``block=`` for correlated series, state collections and multi-state models, ``gpr_input``.  A
+        Dataset-valued observable comes back as ONE array over its stacked variable dimension -- the blocks between two
+        variables have no place in a Dataset."""
+        if minus_log is None:
+            minus_log = self.minus_log
+        if order is None:
+            order = self.order
+        cov, src = self._derivs_cross_cov_device(order, bool(minus_log))
+        host = cov.cpu().numpy().transpose(1, 3, 0, 2)                                       # (order, order_2, c, c')
+        if norm:
+            f = np.array([1.0 / math.factorial(i) for i in range(order + 1)])
+            host = host * f[:, None, None, None] * f[None, :, None, None]
+        out = DataArray(np.ascontiguousarray(host).reshape(order + 1, order + 1, *src.out_shape, *src.out_shape),
+                        ("order", "order_2", *src.out_dims, *[d + "_2" for d in src.out_dims]))
+        return self._cross_labels(out, src)
+
+    def predict_cov(self, alpha, order=None, minus_log=None, alpha_name=None):
+        """``(prediction, cov)``: ``predict(alpha)`` and the delta-method covariance of the predicted columns,
+        ``cov[alpha, c, c'] = sum_ij t_i t_j V[i, j, c, c']`` with ``t_k = (alpha - alpha0)^k / k!`` and
+        ``V = derivs_cross_cov(order)``; cov has dims ``(*alpha dims, *val_dims, *[d + "_2" for d in val_dims])``.  Its
+        diagonal ``c == c'`` is the square of ``predict_with_error``'s std; the rest is what the error bar of a sum, an
+        integral or a ratio of predicted columns needs.  Assumptions, supported models and limits: ``derivs_cross_cov``."""
+        if order is None:
+            order = self.order
+        if minus_log is None:
+            minus_log = self.minus_log
+        cov, src = self._derivs_cross_cov_device(order, bool(minus_log))
+        pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name)
+        dalpha = xrwrap_alpha(alpha, name=alpha_name or self.alpha_name) - self.alpha0
+        d = np.asarray(dalpha.values, dtype=np.float64).reshape(-1)
+        t = np.stack([d**k / math.factorial(k) for k in range(order + 1)], axis=1)            # (n_alpha, order + 1)
+        pc = np.einsum("ai,cidj,aj->acd", t, cov.cpu().numpy(), t)
+        out = DataArray(pc.reshape((*dalpha.shape, *src.out_shape, *src.out_shape)),
+                        (*dalpha.dims, *src.out_dims, *[d + "_2" for d in src.out_dims]))
+        out._inherit(dalpha._coords)
+        return pred, self._cross_labels(out, src)
+
     def resample(self, sampler, **kws):
         """New model on resampled data."""
         return self.new_like(order=self.order, alpha0=self.alpha0, derivatives=self.derivatives,
