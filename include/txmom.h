@@ -703,7 +703,7 @@ int txm_influence_block_cov(const double *x, int64_t ldx_s, const double *u, con
  * set of samples: what a sum over bins, a ratio of two observables or a multi-output model needs.  The device array cov
  * [C][n_f][C][n_f] is symmetric as a (C n_f)^2 matrix, [c][i][c'][j] and [c'][j][c][i] holding the same bits; its blocks
  * c == c' are the cov of (f-9) within the two calls' rounding bounds (another summation order, not the same bits).  There
- * is no `mean` output.  Independent samples are assumed, as in (f-9); there is no blocked form yet.
+ * is no `mean` output.  Independent samples are assumed, as in (f-9); the blocked form for a correlated series is (f-13).
  * psi psi' depends on (q, q') only through r = q + q', so the sample pass needs no coefficients: it accumulates the
  * 2 n_q - 1 Gram matrices  G_r = sum_n w_n^2 du^r z_n z_n^T,  z_n = (dx_n0 .. dx_n,C-1, 1),  on the FP64 matrix pipe
  * (v_mfma_f64_16x16x4_f64) in tiles of 16 x 16 over the C + 1 logical columns, upper-triangle tile pairs only, one record
@@ -720,6 +720,38 @@ size_t txm_influence_cross_cov_ws_bytes(int64_t N, int64_t C, int n_f, int n_q);
 int txm_influence_cross_cov(const double *x, int64_t ldx_s, const double *u, const double *w, int64_t N, int64_t C,
                             int n_f, int n_q, double center_u, const double *center_x, const double *a, const double *b,
                             double *cov, void *ws, size_t ws_bytes, txm_stream stream);
+
+/* ---- (f-13) blocked (batch-means) delta-method covariance ACROSS the observable columns, with the blocking curve ---- */
+/* The operands of (f-11) with C <= 255.  With p_n, psi_k(n, c), the level-l blocks (the last may be short and is kept;
+ * levels with a single block are allowed) and the block sums z_j[c][k] = sum_{n in block j} p_n psi_k(n, c) of (f-11),
+ *     cov[l][c][i][c'][j'] = sum_j z_j[c][i] z_j[c'][j']      (l < n_levels;  c, c' < C;  i, j' < n_f)
+ *     mean[c][k]           = sum_n p_n psi_k(n, c)            (diagnostic: ~ 0)
+ * -- the covariance of ALL estimates of ALL columns of a correlated series whose correlation time `block` exceeds: what
+ * a sum over bins, a ratio of two observables or a multi-output model needs.  There is NO nb / (nb - 1) factor: block = 1,
+ * level 0 is the cov of (f-12) and the blocks c == c' are the cov[l][c] of (f-11), each within the two calls' rounding
+ * bounds (other summation orders, not the same bits).  The device array cov [n_levels][C][n_f][C][n_f] is, level by
+ * level, symmetric as a (C n_f)^2 matrix, [c][i][c'][j'] and [c'][j'][c][i] holding the same bits; mean is [C][n_f].
+ * Pass 1 is that of (f-11) -- the same kernel under the same plan -- and leaves the unnormalised block sums zt [nb][M],
+ * M = C n_f, nb = ceil(N / block), and the block weights in the workspace.  Two small kernels add the columns of zt and
+ * the weights in a fixed order (mean, W).  Per level: the pairs of the level below are merged in place
+ * (zt[j 2^l] += zt[j 2^l + 2^(l-1)]; a last unpaired block stays), then G = sum_b z_b z_b^T runs on the FP64 matrix pipe
+ * (v_mfma_f64_16x16x4_f64, the block axis as the k-axis, four blocks a step) in tiles of 16 x 16 grouped into macro tiles
+ * of 4 x 4 tiles, upper-triangle macro pairs and, inside a diagonal one, upper-triangle tiles only; one record of 16
+ * tiles per (workgroup, macro pair), the workgroups' records added in index order; a last kernel reads G at
+ * (row <= column) only, divides by W^2 and stores every entry with its mirror.  No floating-point atomics: two calls give
+ * the same bits.  A row of weight zero is selected out and may hold anything; a block of total weight zero contributes
+ * zero; total weight zero gives zeros.  First-order rounding bound per level:
+ * eps * sum_b beta_b(c, i) beta_b(c', j'),  beta_b(c, k) = sum_{n in b} p_n B_k(n, c),  B_k as in (f-9).
+ * Workspace: txm_influence_block_cross_cov_ws_bytes, host logic, 0 for bad arguments, the same for every n_levels (the
+ * merge is in place): pass 1's 8 nb (M + 1) bytes, at most 256 (M + 1) column-sum partials and at most
+ * max(4 workgroups per CU, macro pairs) + macro pairs records of 32 KiB (44 MB at M = 2295: 666 macro pairs), + 256.
+ * Null pointers, N < 1, C outside [1, 255], n_f or n_q outside [1, 9], ldx_s < C, a NaN center_u, block < 1 and n_levels
+ * outside [1, 32] return TXM_ERR_INVALID, a short workspace TXM_ERR_WORKSPACE, all before anything is enqueued. */
+size_t txm_influence_block_cross_cov_ws_bytes(int64_t N, int64_t C, int n_f, int n_q, int64_t block, int n_levels);
+int txm_influence_block_cross_cov(const double *x, int64_t ldx_s, const double *u, const double *w, int64_t N, int64_t C,
+                                  int n_f, int n_q, double center_u, const double *center_x, const double *a,
+                                  const double *b, int64_t block, int n_levels, double *cov, double *mean, void *ws,
+                                  size_t ws_bytes, txm_stream stream);
 
 #ifdef __cplusplus
 }

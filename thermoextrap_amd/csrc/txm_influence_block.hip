@@ -22,7 +22,7 @@
 // A row of weight zero is selected out (it may hold anything); a block of total weight zero gives zt = 0; W = 0 gives zeros.
 // First-order rounding bound: |cov - exact|[i][j'] <= few eps * sum_b beta_bi beta_bj',  beta_bk = sum_{n in b} p_n B_k(n),
 // B_k = sum_q (|a_kq| + |b_kq| |dx|) |du|^q.
-#include "txm_common.h"
+#include "txm_influence_block.h"
 
 namespace txm {
 
@@ -314,6 +314,21 @@ static int ib_launch_sums(const IbPlan &p, const double *x, int64_t ldx_s, const
   return TXM_OK;
 }
 
+int ib_block_sums(const double *x, int64_t ldx_s, const double *u, const double *w, int64_t N, int64_t C, int n_f, int n_q,
+                  double center_u, const double *center_x, const double *a, const double *b, int64_t block, double *zt,
+                  double *wb, hipStream_t st) {
+  const IbPlan p = ib_plan(x, ldx_s, N, C, n_q, block);
+  switch (n_q) {
+#define TXM_IB_CASE(Q) \
+  case Q: return ib_launch_sums<Q>(p, x, ldx_s, u, w, N, C, n_f, center_u, center_x, a, b, block, zt, wb, st);
+    TXM_IB_CASE(1) TXM_IB_CASE(2) TXM_IB_CASE(3) TXM_IB_CASE(4) TXM_IB_CASE(5)
+    TXM_IB_CASE(6) TXM_IB_CASE(7) TXM_IB_CASE(8) TXM_IB_CASE(9)
+#undef TXM_IB_CASE
+  }
+  set_error("influence_block_cov: n_q out of range");
+  return TXM_ERR_INVALID;
+}
+
 template <int NF>
 static int ib_launch_levels(double *zt, const double *wb, int64_t nb, int64_t C, int n_levels, double *cov, double *mean,
                             hipStream_t st) {
@@ -349,21 +364,14 @@ extern "C" int txm_influence_block_cov(const double *x, int64_t ldx_s, const dou
     set_error("influence_block_cov: workspace too small");
     return TXM_ERR_WORKSPACE;
   }
-  const IbPlan p = ib_plan(x, ldx_s, N, C, n_q, block);
+  const int64_t nb = cdiv(N, block);
   hipStream_t st = (hipStream_t)stream;
-  double *zt = (double *)ws, *wb = zt + (size_t)p.nb * C * n_f;
-  int rc = TXM_ERR_INVALID;
-  switch (n_q) {
-#define TXM_IB_CASE(Q) \
-  case Q: rc = ib_launch_sums<Q>(p, x, ldx_s, u, w, N, C, n_f, center_u, center_x, a, b, block, zt, wb, st); break;
-    TXM_IB_CASE(1) TXM_IB_CASE(2) TXM_IB_CASE(3) TXM_IB_CASE(4) TXM_IB_CASE(5)
-    TXM_IB_CASE(6) TXM_IB_CASE(7) TXM_IB_CASE(8) TXM_IB_CASE(9)
-#undef TXM_IB_CASE
-  }
+  double *zt = (double *)ws, *wb = zt + (size_t)nb * C * n_f;
+  const int rc = ib_block_sums(x, ldx_s, u, w, N, C, n_f, n_q, center_u, center_x, a, b, block, zt, wb, st);
   if (rc != TXM_OK) return rc;
   switch (n_f) {
 #define TXM_IB_CASE(F) \
-  case F: return ib_launch_levels<F>(zt, wb, p.nb, C, n_levels, cov, mean, st);
+  case F: return ib_launch_levels<F>(zt, wb, nb, C, n_levels, cov, mean, st);
     TXM_IB_CASE(1) TXM_IB_CASE(2) TXM_IB_CASE(3) TXM_IB_CASE(4) TXM_IB_CASE(5)
     TXM_IB_CASE(6) TXM_IB_CASE(7) TXM_IB_CASE(8) TXM_IB_CASE(9)
 #undef TXM_IB_CASE

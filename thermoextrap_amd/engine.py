@@ -920,7 +920,7 @@ def influence_cross_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: to
     p = w / sum w, ``cov[c, i, c', j] = sum_n p_n^2 psi_i(n, c) psi_j(n, c')`` -- every block of the (C n_f)^2 matrix,
     bitwise symmetric, from one pass over x on the FP64 matrix pipe.  x: (N, C) or (N,), copied to row-major if it is
     not; a, b: (C, n_f, n_q); center_x: (C,); C <= 255.  Returns ``cov [C, n_f, C, n_f]`` on the device.  Independent
-    samples are assumed (there is no blocked form)."""
+    samples are assumed; ``influence_block_cross_cov`` is the blocked form for a correlated series."""
     L = _L()
     x2, ls, _, u, w, N, C, _ = _operands(x, u, w, "rowmajor")
     for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
@@ -942,6 +942,46 @@ def influence_cross_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: to
         "txm_influence_cross_cov",
     )
     return cov
+
+
+def influence_block_cross_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: torch.Tensor, center_u: float,
+                              center_x: torch.Tensor, block: int, n_levels: int = 1,
+                              w: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Blocked (batch-means) delta-method covariance ACROSS the columns for a correlated series
+    (txm_influence_block_cross_cov): with the block sums ``z_j[c, k] = sum_{n in block j} p_n psi_k(n, c)`` of
+    ``influence_block_cov``, ``cov[l, c, i, c', j'] = sum_j z_j[c, i] z_j[c', j']`` over the contiguous blocks of
+    ``block * 2**l`` rows (a last short block is kept; no nb / (nb - 1) factor, so ``block=1`` is ``influence_cross_cov``'s
+    result and the blocks ``c == c'`` are ``influence_block_cov``'s, up to rounding) -- every level bitwise symmetric as
+    a (C n_f)^2 matrix.  One pass over x (``influence_block_cov``'s own), then a Gram over the block sums on the FP64
+    matrix pipe per level.  x: (N, C) or (N,), copied to row-major if it is not; a, b: (C, n_f, n_q); center_x: (C,);
+    C <= 255.  Returns ``(cov [n_levels, C, n_f, C, n_f], mean [C, n_f])`` on the device.  Not covered: a batched
+    (many-state) form, overlapping batch means."""
+    L = _L()
+    x2, ls, _, u, w, N, C, _ = _operands(x, u, w, "rowmajor")
+    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
+        _check_f64_cuda(t, name)
+    if a.dim() != 3 or a.shape[0] != C or b.shape != a.shape:
+        raise ValueError(f"a and b must both have shape ({C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
+    if center_x.shape != (C,):
+        raise ValueError(f"center_x must have shape ({C},), got {tuple(center_x.shape)}")
+    if C > CROSS_COV_MAX_COLUMNS:
+        raise ValueError(f"influence_block_cross_cov: C = {C} columns, the limit is {CROSS_COV_MAX_COLUMNS} (the result has "
+                         "(C n_f)^2 entries a level)")
+    block, n_levels = int(block), int(n_levels)
+    if block < 1 or not 1 <= n_levels <= 32:
+        raise ValueError(f"need block >= 1 and 1 <= n_levels <= 32, got block={block}, n_levels={n_levels}")
+    _, n_f, n_q = a.shape
+    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
+    cov = torch.empty((n_levels, C, n_f, C, n_f), dtype=F64, device="cuda")
+    mean = torch.empty((C, n_f), dtype=F64, device="cuda")
+    ws = workspace(L.txm_influence_block_cross_cov_ws_bytes(N, C, n_f, n_q, block, n_levels))
+    check(
+        L.txm_influence_block_cross_cov(_ptr(x2), ls, _ptr(u), _ptr(w), N, C, n_f, n_q, float(center_u), _ptr(center_x),
+                                        _ptr(a), _ptr(b), block, n_levels, _ptr(cov), _ptr(mean), _ptr(ws), ws.numel(),
+                                        _stream()),
+        "txm_influence_block_cross_cov",
+    )
+    return cov, mean
 
 
 TAYLOR_MODES ={"sum": 0, "cumsum": 1, "terms": 2}

@@ -680,9 +680,12 @@ class ExtrapModel(_Params):
         return pred, self._ds(std)
 
     # ---- the same across the observable columns ---------------------------------------------------------
-    def _derivs_cross_cov_device(self, order, minus_log):
+    def _derivs_cross_cov_device(self, order, minus_log, block=None):
         """``(cov [n_out, order + 1, n_out, order + 1] on the device, source)`` from ONE ``engine.influence_cross_cov``,
-        cached under a key of its own: the per-column entry ``("dcov", ...)`` is neither read nor written."""
+        cached under a key of its own: the per-column entry ``("dcov", ...)`` is neither read nor written.  With a
+        ``block`` it is the blocked estimator's (``_blocked_cross_cov_device``)."""
+        if block is not None:
+            return self._blocked_cross_cov_device(order, minus_log, block, curve=False)[:2]
         key = ("dxcov", order, minus_log)
         if key not in self._cache:
             x2, ut, wt, st, src = self._delta_operands()         # (first: an unsupported model says so, whatever its width)
@@ -694,6 +697,25 @@ class ExtrapModel(_Params):
             self._cache[key] = (cov, src)
         return self._cache[key]
 
+    def _blocked_cross_cov_device(self, order, minus_log, block, curve):
+        """``(cov, source, block_lengths, n_blocks)`` of the blocked cross estimator from ONE
+        ``engine.influence_block_cross_cov``: cov [n_out, order + 1, n_out, order + 1] at ``block`` alone, or with
+        ``curve`` [level, n_out, order + 1, n_out, order + 1] for every level of ``engine.block_levels``.  Cached under
+        keys that carry the block: the iid entry ``("dxcov", ...)`` is neither read nor written."""
+        block = _check_block_type(block)
+        key = ("dxcov_block", order, minus_log, block, bool(curve))
+        if key not in self._cache:
+            x2, ut, wt, st, src = self._delta_operands()         # (first: an unsupported model says so, whatever the block)
+            if x2.shape[1] > engine.CROSS_COV_MAX_COLUMNS:
+                raise ValueError(f"derivs_cross_cov / predict_cov: {x2.shape[1]} observable columns, the limit is "
+                                 f"{engine.CROSS_COV_MAX_COLUMNS} (the result has (columns * (order + 1))^2 entries)")
+            lengths, counts = engine.block_levels(x2.shape[0], block)
+            a, b, um, xm = self._delta_coefs(st, order, minus_log)
+            cov, _ = engine.influence_block_cross_cov(x2, ut, engine.to_device(a), engine.to_device(b), um,
+                                                      engine.to_device(xm), block, n_levels=len(lengths) if curve else 1, w=wt)
+            self._cache[key] = (cov if curve else cov[0], src, lengths, counts)
+        return self._cache[key]
+
     @staticmethod
     def _cross_labels(out, src):
         """The coordinates of the value dims on ``out``, and their copies under the ``_2`` names."""
@@ -701,7 +723,19 @@ class ExtrapModel(_Params):
         out._inherit({k + "_2": (tuple(d + "_2" for d in cd), cv) for k, (cd, cv) in src.coords.items()})
         return out
 
-    def derivs_cross_cov(self, order=None, norm=False, minus_log=None):
+    @classmethod
+    def _derivs_cross_cov_labelled(cls, host, src, order, norm):
+        """The host copy of a ``_derivs_cross_cov_device`` table (n_out, order + 1, n_out, order + 1) as
+        ``derivs_cross_cov`` returns it."""
+        host = host.transpose(1, 3, 0, 2)                                                    # (order, order_2, c, c')
+        if norm:
+            f = np.array([1.0 / math.factorial(i) for i in range(order + 1)])
+            host = host * f[:, None, None, None] * f[None, :, None, None]
+        out = DataArray(np.ascontiguousarray(host).reshape(order + 1, order + 1, *src.out_shape, *src.out_shape),
+                        ("order", "order_2", *src.out_dims, *[d + "_2" for d in src.out_dims]))
+        return cls._cross_labels(out, src)
+
+    def derivs_cross_cov(self, order=None, norm=False, minus_log=None, block=None):
         """Delta-method covariance of ``derivs(order)`` ACROSS the observable columns: dims
         ``(order, order_2, *val_dims, *[d + "_2" for d in val_dims])`` with
 
@@ -717,33 +751,54 @@ class ExtrapModel(_Params):
 
         The assumptions and the supported models are those of ``derivs_cov`` (first order, INDEPENDENT samples; anything
         else raises the same NotImplementedError), with at most 255 observable columns (ValueError beyond).  Out of
-        scope here: ``block=`` for correlated series, state collections and multi-state models, ``gpr_input``.  A
-        Dataset-valued observable comes back as ONE array over its stacked variable dimension -- the blocks between two
-        variables have no place in a Dataset."""
+        scope here: state collections and multi-state models, ``gpr_input``.  A Dataset-valued observable comes back as
+        ONE array over its stacked variable dimension -- the blocks between two variables have no place in a Dataset.
+
+        ``block=B`` (an int, ``1 <= B`` and ``2 B <= N``) is for a CORRELATED series kept whole, as in ``derivs_cov``:
+        ``V[i, j, c, c'] = sum_b z_bi(c) z_bj(c')`` with ``z_bk(c) = sum_{n in b} p_n psi_k(n, c)`` over the contiguous
+        blocks of B records (a last short one is kept) -- batch means, every record used, one pass over the samples and
+        a Gram over the block sums on the FP64 matrix pipe (txm_influence_block_cross_cov).  B must exceed the
+        correlation time (``cross_blocking_curve`` shows whether V has levelled off); no ``nb / (nb - 1)`` factor is
+        applied, so ``block=1`` is the iid result and the blocks ``c == c'`` are ``derivs_cov(block=B)``, both up to
+        rounding.  A non-integer block raises TypeError, one outside the range ValueError; ``block=None`` is the iid
+        path, untouched."""
         if minus_log is None:
             minus_log = self.minus_log
         if order is None:
             order = self.order
-        cov, src = self._derivs_cross_cov_device(order, bool(minus_log))
-        host = cov.cpu().numpy().transpose(1, 3, 0, 2)                                       # (order, order_2, c, c')
-        if norm:
-            f = np.array([1.0 / math.factorial(i) for i in range(order + 1)])
-            host = host * f[:, None, None, None] * f[None, :, None, None]
-        out = DataArray(np.ascontiguousarray(host).reshape(order + 1, order + 1, *src.out_shape, *src.out_shape),
-                        ("order", "order_2", *src.out_dims, *[d + "_2" for d in src.out_dims]))
-        return self._cross_labels(out, src)
+        cov, src = self._derivs_cross_cov_device(order, bool(minus_log), block)
+        return self._derivs_cross_cov_labelled(cov.cpu().numpy(), src, order, norm)
 
-    def predict_cov(self, alpha, order=None, minus_log=None, alpha_name=None):
+    def cross_blocking_curve(self, block, order=None, norm=False, minus_log=None):
+        """The blocking curve of ``derivs_cross_cov``: ``(V, block_lengths, n_blocks)`` with
+        ``V[l] = derivs_cross_cov(block=block * 2**l)`` (dims ``(level, order, order_2, *val_dims, *val_dims_2)``, the
+        level coordinates as in ``blocking_curve``), ``block_lengths[l] = block * 2**l`` and
+        ``n_blocks[l] = ceil(N / block_lengths[l])``, for every level that still has at least two blocks.  ONE engine
+        call: each level merges the pairs of the block sums of the level below and runs the Gram again.  V holds
+        ``levels * (C * (order + 1))**2`` doubles (C the number of observable columns): 10 levels of 255 columns at
+        order 4 are 130 MB -- take ``blocking_curve`` where the diagonal blocks are enough."""
+        if minus_log is None:
+            minus_log = self.minus_log
+        if order is None:
+            order = self.order
+        cov, src, lengths, counts = self._blocked_cross_cov_device(order, bool(minus_log), block, curve=True)
+        host = cov.cpu().numpy()
+        levels = [self._derivs_cross_cov_labelled(host[l], src, order, norm) for l in range(host.shape[0])]
+        out = concat(levels, dim=DataArray(lengths.copy(), "level"))
+        return out, lengths.copy(), counts.copy()
+
+    def predict_cov(self, alpha, order=None, minus_log=None, alpha_name=None, block=None):
         """``(prediction, cov)``: ``predict(alpha)`` and the delta-method covariance of the predicted columns,
         ``cov[alpha, c, c'] = sum_ij t_i t_j V[i, j, c, c']`` with ``t_k = (alpha - alpha0)^k / k!`` and
         ``V = derivs_cross_cov(order)``; cov has dims ``(*alpha dims, *val_dims, *[d + "_2" for d in val_dims])``.  Its
         diagonal ``c == c'`` is the square of ``predict_with_error``'s std; the rest is what the error bar of a sum, an
-        integral or a ratio of predicted columns needs.  Assumptions, supported models and limits: ``derivs_cross_cov``."""
+        integral or a ratio of predicted columns needs.  Assumptions, supported models and limits: ``derivs_cross_cov``;
+        ``block=B`` takes ``V = derivs_cross_cov(order, block=B)`` for a correlated series (the prediction is the same)."""
         if order is None:
             order = self.order
         if minus_log is None:
             minus_log = self.minus_log
-        cov, src = self._derivs_cross_cov_device(order, bool(minus_log))
+        cov, src = self._derivs_cross_cov_device(order, bool(minus_log), block)
         pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name)
         dalpha = xrwrap_alpha(alpha, name=alpha_name or self.alpha_name) - self.alpha0
         d = np.asarray(dalpha.values, dtype=np.float64).reshape(-1)
