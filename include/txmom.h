@@ -753,6 +753,38 @@ int txm_influence_block_cross_cov(const double *x, int64_t ldx_s, const double *
                                   const double *b, int64_t block, int n_levels, double *cov, double *mean, void *ws,
                                   size_t ws_bytes, txm_stream stream);
 
+/* ---- (f-14) the cross-column covariance of (f-12) for S independent states in one set of launches ---------------- */
+/* S states of C <= 255 columns each, x row-major with ONE pitch ldx_s >= C and a sample count PER STATE.  `states_host`
+ * is a HOST array of S records of (f-10) (w NULL for all states or for none); it is copied into the workspace by the
+ * call (not stream-capturable).  center_u [S], center_x [S][C], a and b [S][C][n_f][n_q] and cov [S][C][n_f][C][n_f] are
+ * device arrays.  For state s the definition is (f-12)'s on that state's operands:
+ *     cov[s][c][i][c'][j] = sum_n p_n^2 psi_i(n, c) psi_j(n, c')
+ * Three launches for all states: the state rides a grid axis of the sample, the sum and the finalize kernel.
+ * PLAN: the batch has a plan of its own, a function of (S, C, n_s, compute units) only.  With T = ceil((C + 1) / 16) and
+ * pairs = T (T + 1) / 2, a state may have  q = max(1, floor(8 CUs / (pairs S)))  sample workgroups and state s gets
+ * grid_x_s = min(ceil(n_s / 256), q) -- txm_influence_cross_cov_batched_grid(S, n_s, C), host logic, 0 for bad arguments.
+ * The launch is (pairs, max_s grid_x_s, S); a workgroup beyond its state's grid_x_s leaves at once; every state has its
+ * own slice of the workspace for its grid_x_s pairs partial records and its pairs summed records.
+ * BITS: inside a state everything is (f-12)'s -- the 4-sample steps of a wave, the wave-order sum, the index-order sum of
+ * the records, the finalize's fixed contraction order and the mirror store.  State s therefore equals
+ * txm_influence_cross_cov on that state alone BIT FOR BIT whenever both plans give it the same number of sample
+ * workgroups: whenever ceil(n_s / 256) <= q (q never exceeds the single call's cap), and always for S == 1.  A state whose
+ * budget q binds below its single plan has the same sums added in another order: the rounding bound of (f-12) holds for
+ * it, equal bits are not promised.  No floating-point atomics, two calls give the same bits, every cov[s] is bitwise
+ * symmetric as a (C n_f)^2 matrix.  Zero-weight rows are selected out and may hold anything; a state of total weight zero
+ * gives zeros for that state only.
+ * Workspace: txm_influence_cross_cov_batched_ws_bytes(S, n_max, C, n_f, n_q), n_max = max_s n_s, host logic, 0 for bad
+ * arguments, nondecreasing in n_max: S (min(ceil(n_max / 256), q) + 1) pairs records of 8 (256 (2 n_q - 1) + 8) bytes, the
+ * 256-byte-aligned state table and 256 bytes (30 MB for 64 states of 1e6 samples, 4 columns, order 3, on 256 CUs).
+ * Null pointers, S outside [1, 65535], any n < 1, C outside [1, 255], n_f or n_q outside [1, 9], ldx_s < C and mixed
+ * NULL / non-NULL w return TXM_ERR_INVALID, a short workspace TXM_ERR_WORKSPACE, all before anything is enqueued and with
+ * cov untouched.  center_u is a device array here: a NaN among its entries is NOT checked (it gives NaN for that state). */
+size_t txm_influence_cross_cov_batched_ws_bytes(int64_t S, int64_t n_max, int64_t C, int n_f, int n_q);
+int txm_influence_cross_cov_batched_grid(int64_t S, int64_t n, int64_t C);
+int txm_influence_cross_cov_batched(const txm_inf_state *states_host, int64_t S, int64_t ldx_s, int64_t C, int n_f, int n_q,
+                                    const double *center_u, const double *center_x, const double *a, const double *b,
+                                    double *cov, void *ws, size_t ws_bytes, txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,10 @@ SIGNATURES = {
     "txm_influence_cross_cov_ws_bytes": (c_size, [c_i64, c_i64, c_int, c_int]),
     "txm_influence_cross_cov": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, ct.c_double, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_influence_cross_cov_batched_ws_bytes": (c_size, [c_i64, c_i64, c_i64, c_int, c_int]),
+    "txm_influence_cross_cov_batched_grid": (c_int, [c_i64, c_i64, c_i64]),
+    "txm_influence_cross_cov_batched": (c_int, [ct.POINTER(InfState), c_i64, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "txm_influence_block_cross_cov_ws_bytes": (c_size, [c_i64, c_i64, c_int, c_int, c_i64, c_int]),
     "txm_influence_block_cross_cov": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, ct.c_double,
                                               c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_size,

@@ -32,6 +32,13 @@
 // to zero, not multiplied by zero) and may hold anything; total weight zero gives zeros.
 // Rounding: every product of the expansion is bounded by the matching product of B_k(n, c) = sum_q (|a| + |b| |dx|) |du|^q,
 // so the first-order bound is eps * sum_n p_n^2 B_i(n, c) B_j(n, c'),  p_n = w_n / sum w.
+//
+// txm_influence_cross_cov_batched runs the same three bodies for S states in ONE launch each, the state on
+// a grid axis, under a plan of its own: the states share the eight workgroups per CU (cx_batch_q), and every state has
+// its own slice of the workspace.  Inside a state nothing changes, so a state whose sample workgroups are as many as
+// cx_plan would give it alone has the single call's bits.
+#include <vector>
+
 #include "txm_common.h"
 
 namespace txm {
@@ -58,13 +65,21 @@ __device__ __forceinline__ void cx_pair(int p, int T, int &ti, int &tj) {
 
 __host__ __device__ __forceinline__ int cx_pair_index(int ti, int tj, int T) { return ti * T - ti * (ti - 1) / 2 + (tj - ti); }
 
-// partial [gridDim.y sample workgroups][gridDim.x tile pairs][cx_rec]
+// One state of a batched call as the kernels read it (built on the host from txm_inf_state and the batch's plan):
+// grid_x sample workgroups, its slice of the workspace at `off` doubles: grid_x * pairs records, then pairs summed ones.
+struct cx_dev_state {
+  const double *x, *u, *w;
+  int64_t n;
+  int64_t grid_x;
+  size_t off;
+};
+
+// Sample workgroup `by` of `ny` of one state.  partial [ny sample workgroups][gridDim.x tile pairs][cx_rec]
 template <int NQ, bool WEIGHTED>
-__global__ __launch_bounds__(CX_BLOCK) void influence_cross_kernel(const double *__restrict__ x, int64_t ldx_s,
-                                                                   const double *__restrict__ u,
-                                                                   const double *__restrict__ w, int64_t N, int C, int T,
-                                                                   double cu, const double *__restrict__ cx,
-                                                                   double *__restrict__ partial) {
+__device__ __forceinline__ void influence_cross_body(const double *__restrict__ x, int64_t ldx_s,
+                                                     const double *__restrict__ u, const double *__restrict__ w,
+                                                     int64_t N, int C, int T, double cu, const double *__restrict__ cx,
+                                                     int by, int ny, double *__restrict__ partial) {
   constexpr int R = 2 * NQ - 1, REC = cx_rec(NQ);
   __shared__ double red[4 * 256];
   __shared__ double sws[16];
@@ -84,8 +99,8 @@ __global__ __launch_bounds__(CX_BLOCK) void influence_cross_kernel(const double 
   double sw = 0.0;
 
   // wave wg of NW takes the 4-sample steps wg, wg + NW, ...; the loop bounds are wave-uniform
-  const int64_t NW = (int64_t)gridDim.y * 4, stride = NW * 4;
-  for (int64_t ib = ((int64_t)blockIdx.y * 4 + wave) * 4; ib < N; ib += CX_UNR * stride) {
+  const int64_t NW = (int64_t)ny * 4, stride = NW * 4;
+  for (int64_t ib = ((int64_t)by * 4 + wave) * 4; ib < N; ib += CX_UNR * stride) {
     double ui[CX_UNR], wi[CX_UNR], xa[CX_UNR], xb[CX_UNR];
     bool ok[CX_UNR];
 #pragma unroll
@@ -116,7 +131,7 @@ __global__ __launch_bounds__(CX_BLOCK) void influence_cross_kernel(const double 
   }
 
   // the four waves' tiles in wave order.  D layout: column = lane & 15, row = (lane >> 4) + 4 * reg
-  double *dst = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * REC;
+  double *dst = partial + ((size_t)by * gridDim.x + blockIdx.x) * REC;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
 #pragma unroll
@@ -136,9 +151,31 @@ __global__ __launch_bounds__(CX_BLOCK) void influence_cross_kernel(const double 
   }
 }
 
+template <int NQ, bool WEIGHTED>
+__global__ __launch_bounds__(CX_BLOCK) void influence_cross_kernel(const double *__restrict__ x, int64_t ldx_s,
+                                                                   const double *__restrict__ u,
+                                                                   const double *__restrict__ w, int64_t N, int C, int T,
+                                                                   double cu, const double *__restrict__ cx,
+                                                                   double *__restrict__ partial) {
+  influence_cross_body<NQ, WEIGHTED>(x, ldx_s, u, w, N, C, T, cu, cx, (int)blockIdx.y, (int)gridDim.y, partial);
+}
+
+// blockIdx.z = state; a workgroup beyond the state's own grid leaves at once
+template <int NQ, bool WEIGHTED>
+__global__ __launch_bounds__(CX_BLOCK) void influence_cross_batch_kernel(const cx_dev_state *__restrict__ tab,
+                                                                         int64_t ldx_s, int C, int T,
+                                                                         const double *__restrict__ cu,
+                                                                         const double *__restrict__ cx,
+                                                                         double *__restrict__ ws) {
+  const cx_dev_state s = tab[blockIdx.z];
+  if ((int64_t)blockIdx.y >= s.grid_x) return;
+  influence_cross_body<NQ, WEIGHTED>(s.x, ldx_s, s.u, s.w, s.n, C, T, cu[blockIdx.z], cx + (size_t)blockIdx.z * C,
+                                     (int)blockIdx.y, (int)s.grid_x, ws + s.off);
+}
+
 // G[e] = sum over the nblk workgroups, in index order, of partial[blk][e]      (e < per_blk = pairs * REC)
-__global__ __launch_bounds__(CX_BLOCK) void influence_cross_sum_kernel(const double *__restrict__ partial, int nblk,
-                                                                       size_t per_blk, double *__restrict__ G) {
+__device__ __forceinline__ void influence_cross_sum_body(const double *__restrict__ partial, int nblk, size_t per_blk,
+                                                         double *__restrict__ G) {
   const size_t e = (size_t)blockIdx.x * CX_BLOCK + threadIdx.x;
   if (e >= per_blk) return;
   double acc = 0.0;
@@ -146,12 +183,24 @@ __global__ __launch_bounds__(CX_BLOCK) void influence_cross_sum_kernel(const dou
   G[e] = acc;
 }
 
+__global__ __launch_bounds__(CX_BLOCK) void influence_cross_sum_kernel(const double *__restrict__ partial, int nblk,
+                                                                       size_t per_blk, double *__restrict__ G) {
+  influence_cross_sum_body(partial, nblk, per_blk, G);
+}
+
+// blockIdx.y = state: its grid_x records of per_blk doubles, the summed record behind them
+__global__ __launch_bounds__(CX_BLOCK) void influence_cross_sum_batch_kernel(const cx_dev_state *__restrict__ tab,
+                                                                             size_t per_blk, double *__restrict__ ws) {
+  const cx_dev_state s = tab[blockIdx.y];
+  double *partial = ws + s.off;
+  influence_cross_sum_body(partial, (int)s.grid_x, per_blk, partial + (size_t)s.grid_x * per_blk);
+}
+
 // cov [C n_f][C n_f]; a thread per (P, Q) = ((c, i), (c', j)), the threads with P <= Q compute and store both
 template <int NQ>
-__global__ __launch_bounds__(CX_BLOCK) void influence_cross_final_kernel(const double *__restrict__ G, int C, int T,
-                                                                         int n_f, const double *__restrict__ a,
-                                                                         const double *__restrict__ b,
-                                                                         double *__restrict__ cov) {
+__device__ __forceinline__ void influence_cross_final_body(const double *__restrict__ G, int C, int T, int n_f,
+                                                           const double *__restrict__ a, const double *__restrict__ b,
+                                                           double *__restrict__ cov) {
   constexpr int R = 2 * NQ - 1, REC = cx_rec(NQ);
   const size_t M = (size_t)C * n_f;
   const size_t e = (size_t)blockIdx.x * CX_BLOCK + threadIdx.x;
@@ -187,6 +236,28 @@ __global__ __launch_bounds__(CX_BLOCK) void influence_cross_final_kernel(const d
   const double v = W == 0.0 ? 0.0 : s / (W * W);
   cov[P * M + Q] = v;
   cov[Q * M + P] = v;
+}
+
+template <int NQ>
+__global__ __launch_bounds__(CX_BLOCK) void influence_cross_final_kernel(const double *__restrict__ G, int C, int T,
+                                                                         int n_f, const double *__restrict__ a,
+                                                                         const double *__restrict__ b,
+                                                                         double *__restrict__ cov) {
+  influence_cross_final_body<NQ>(G, C, T, n_f, a, b, cov);
+}
+
+// blockIdx.y = state: its summed records, its slices of a, b [S][C][n_f][NQ] and of cov [S][C n_f][C n_f]
+template <int NQ>
+__global__ __launch_bounds__(CX_BLOCK) void influence_cross_final_batch_kernel(const cx_dev_state *__restrict__ tab,
+                                                                               const double *__restrict__ ws,
+                                                                               size_t per_blk, int C, int T, int n_f,
+                                                                               const double *__restrict__ a,
+                                                                               const double *__restrict__ b,
+                                                                               double *__restrict__ cov) {
+  const cx_dev_state s = tab[blockIdx.y];
+  const size_t M = (size_t)C * n_f, sb = (size_t)blockIdx.y;
+  influence_cross_final_body<NQ>(ws + s.off + (size_t)s.grid_x * per_blk, C, T, n_f, a + sb * M * NQ, b + sb * M * NQ,
+                                 cov + sb * M * M);
 }
 
 struct CxPlan {
@@ -236,6 +307,40 @@ static int cx_launch(const CxPlan &p, const double *x, int64_t ldx_s, const doub
   return TXM_OK;
 }
 
+// The batch's own plan: q sample workgroups a state may have, so that all S states together stay at about
+// eight workgroups per CU; q never exceeds cx_plan's cap, so a state with ceil(n / CX_SHARE) <= q runs the single plan.
+static int64_t cx_batch_q(int64_t S, int pairs) {
+  const int64_t q = (int64_t)num_cus() * 8 / ((int64_t)pairs * S);
+  return q < 1 ? 1 : q;
+}
+
+static int64_t cx_batch_grid(int64_t S, int64_t n, int64_t C) {
+  const int T = (int)((C + 1 + 15) / 16);
+  const int64_t q = cx_batch_q(S, T * (T + 1) / 2), gx = n / CX_SHARE + (n % CX_SHARE != 0);  // (no overflow near 2^63)
+  return gx > q ? q : gx;
+}
+
+template <int NQ>
+static int cx_launch_batched(const cx_dev_state *tab, int64_t S, bool weighted, int T, int pairs, int64_t grid_max,
+                             int64_t ldx_s, int C, int n_f, const double *cu, const double *cx, const double *a,
+                             const double *b, double *cov, double *ws, hipStream_t st) {
+  const size_t per_blk = (size_t)pairs * cx_rec(NQ);
+  const dim3 grid(pairs, (unsigned)grid_max, (unsigned)S), block(CX_BLOCK);
+  if (weighted)
+    hipLaunchKernelGGL((influence_cross_batch_kernel<NQ, true>), grid, block, 0, st, tab, ldx_s, C, T, cu, cx, ws);
+  else
+    hipLaunchKernelGGL((influence_cross_batch_kernel<NQ, false>), grid, block, 0, st, tab, ldx_s, C, T, cu, cx, ws);
+  TXM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(influence_cross_sum_batch_kernel, dim3((unsigned)cdiv((int64_t)per_blk, CX_BLOCK), (unsigned)S), block,
+                     0, st, tab, per_blk, ws);
+  TXM_LAUNCH_CHECK();
+  const int64_t M = (int64_t)C * n_f;
+  hipLaunchKernelGGL((influence_cross_final_batch_kernel<NQ>), dim3((unsigned)cdiv(M * M, CX_BLOCK), (unsigned)S), block, 0,
+                     st, tab, ws, per_blk, C, T, n_f, a, b, cov);
+  TXM_LAUNCH_CHECK();
+  return TXM_OK;
+}
+
 }  // namespace txm
 
 using namespace txm;
@@ -270,5 +375,76 @@ extern "C" int txm_influence_cross_cov(const double *x, int64_t ldx_s, const dou
 #undef TXM_CX_CASE
   }
   set_error("influence_cross_cov: n_q out of range");
+  return TXM_ERR_INVALID;
+}
+
+static bool cx_batched_shape_ok(int64_t S, int64_t C, int n_f, int n_q) {
+  return S >= 1 && S <= 65535 && C >= 1 && C <= CX_MAXC && n_f >= 1 && n_f <= TXM_MAXK && n_q >= 1 && n_q <= TXM_MAXK;
+}
+
+extern "C" int txm_influence_cross_cov_batched_grid(int64_t S, int64_t n, int64_t C) {
+  if (S < 1 || S > 65535 || n < 1 || C < 1 || C > CX_MAXC) return 0;
+  return (int)cx_batch_grid(S, n, C);
+}
+
+extern "C" size_t txm_influence_cross_cov_batched_ws_bytes(int64_t S, int64_t n_max, int64_t C, int n_f, int n_q) {
+  if (!cx_batched_shape_ok(S, C, n_f, n_q) || n_max < 1) return 0;
+  const int T = (int)((C + 1 + 15) / 16), pairs = T * (T + 1) / 2;
+  const size_t records = (size_t)S * (size_t)(cx_batch_grid(S, n_max, C) + 1) * (size_t)pairs;
+  return align_up((size_t)S * sizeof(cx_dev_state), 256) + records * (size_t)cx_rec(n_q) * sizeof(double) + 256;
+}
+
+extern "C" int txm_influence_cross_cov_batched(const txm_inf_state *states_host, int64_t S, int64_t ldx_s, int64_t C,
+                                               int n_f, int n_q, const double *center_u, const double *center_x,
+                                               const double *a, const double *b, double *cov, void *ws, size_t ws_bytes,
+                                               txm_stream stream) {
+  TXM_REQUIRE(states_host && center_u && center_x && a && b && cov && ws, "influence_cross_cov_batched: null pointer");
+  TXM_REQUIRE(S >= 1 && S <= 65535, "influence_cross_cov_batched: S=%lld outside [1, 65535]", (long long)S);
+  TXM_REQUIRE(C >= 1 && C <= CX_MAXC, "influence_cross_cov_batched: C=%lld outside [1, %d] (the result has (C n_f)^2 entries)",
+              (long long)C, CX_MAXC);
+  TXM_REQUIRE(n_f >= 1 && n_f <= TXM_MAXK, "influence_cross_cov_batched: n_f=%d outside [1, %d]", n_f, TXM_MAXK);
+  TXM_REQUIRE(n_q >= 1 && n_q <= TXM_MAXK, "influence_cross_cov_batched: n_q=%d outside [1, %d]", n_q, TXM_MAXK);
+  TXM_REQUIRE(ldx_s >= C, "influence_cross_cov_batched: row pitch ldx_s < C");
+  const bool weighted = states_host[0].w != nullptr;
+  int64_t n_max = 0;
+  for (int64_t s = 0; s < S; ++s) {
+    const txm_inf_state &h = states_host[s];
+    TXM_REQUIRE(h.x && h.u, "influence_cross_cov_batched: state %lld has a null pointer", (long long)s);
+    TXM_REQUIRE((h.w != nullptr) == weighted, "influence_cross_cov_batched: weights for all states or for none");
+    TXM_REQUIRE(h.n >= 1, "influence_cross_cov_batched: state %lld has n=%lld < 1", (long long)s, (long long)h.n);
+    if (h.n > n_max) n_max = h.n;
+  }
+  const int T = (int)((C + 1 + 15) / 16), pairs = T * (T + 1) / 2;
+  const size_t rec = (size_t)cx_rec(n_q);
+  static thread_local std::vector<cx_dev_state> tab_host;
+  tab_host.resize((size_t)S);
+  size_t off = 0;
+  int64_t grid_max = 1;
+  for (int64_t s = 0; s < S; ++s) {
+    const txm_inf_state &h = states_host[s];
+    const int64_t gx = cx_batch_grid(S, h.n, C);
+    tab_host[(size_t)s] = cx_dev_state{h.x, h.u, h.w, h.n, gx, off};
+    off += (size_t)(gx + 1) * (size_t)pairs * rec;
+    if (gx > grid_max) grid_max = gx;
+  }
+  const size_t tab_bytes = align_up((size_t)S * sizeof(cx_dev_state), 256);
+  if (ws_bytes < txm_influence_cross_cov_batched_ws_bytes(S, n_max, C, n_f, n_q) || ws_bytes < tab_bytes + off * sizeof(double)) {
+    set_error("influence_cross_cov_batched: workspace too small");
+    return TXM_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  cx_dev_state *tab = (cx_dev_state *)ws;
+  TXM_HIP(hipMemcpyAsync(tab, tab_host.data(), (size_t)S * sizeof(cx_dev_state), hipMemcpyHostToDevice, st));
+  double *recs = (double *)((char *)ws + tab_bytes);
+  switch (n_q) {
+#define TXM_CX_CASE(Q)                                                                                                   \
+  case Q:                                                                                                                \
+    return cx_launch_batched<Q>(tab, S, weighted, T, pairs, grid_max, ldx_s, (int)C, n_f, center_u, center_x, a, b, cov, \
+                                recs, st);
+    TXM_CX_CASE(1) TXM_CX_CASE(2) TXM_CX_CASE(3) TXM_CX_CASE(4) TXM_CX_CASE(5)
+    TXM_CX_CASE(6) TXM_CX_CASE(7) TXM_CX_CASE(8) TXM_CX_CASE(9)
+#undef TXM_CX_CASE
+  }
+  set_error("influence_cross_cov_batched: n_q out of range");
   return TXM_ERR_INVALID;
 }

@@ -944,6 +944,71 @@ def influence_cross_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: to
     return cov
 
 
+def influence_cross_cov_batched(xs, us, a: torch.Tensor, b: torch.Tensor, center_u, center_x: torch.Tensor,
+                                ws=None) -> torch.Tensor:
+    """``influence_cross_cov`` of S independent states in ONE launch per kernel (txm_influence_cross_cov_batched).
+    xs[s]: (n_s, C) or (n_s,), us[s] (and ws[s]): (n_s,) -- the sample count may differ from state to state; a, b:
+    (S, C, n_f, n_q); center_u: S host floats or an (S,) tensor; center_x: (S, C); C <= 255.
+    Returns ``cov [S, C, n_f, C, n_f]`` on the device, every ``cov[s]`` bitwise symmetric as a (C n_f)^2 matrix.
+
+    The batch has a plan of its own (include/txmom.h (f-14)): the states share the device, each with at most
+    ``q = max(1, 8 CUs // (tile pairs * S))`` sample workgroups.  State s equals
+    ``influence_cross_cov(xs[s], us[s], a[s], b[s], center_u[s], center_x[s], w=ws[s])`` bit for bit when
+    ``ceil(n_s / 256) <= q``; a state the budget binds has the same sums in another order, within the same rounding bound.
+
+    The one launch needs every x row-major with one pitch; otherwise this loops over ``influence_cross_cov`` and stacks.
+    Pointer alignment does not matter (the kernel reads 8 bytes at a time)."""
+    L = _L()
+    S = len(xs)
+    if S < 1 or len(us) != S or (ws is not None and len(ws) != S):
+        raise ValueError("need the same number (>= 1) of x, u (and w) tensors")
+    if ws is not None and any(w is None for w in ws) and not all(w is None for w in ws):
+        raise ValueError("weights for all states or for none")
+    if ws is not None and ws[0] is None:
+        ws = None
+    ops = [_operands(xs[s], us[s], None if ws is None else ws[s], "rowmajor") for s in range(S)]
+    as_given = all(not _layout(x.unsqueeze(1) if x.dim() == 1 else x, "rowmajor")[0] for x in xs)
+    C = ops[0][6]
+    if any(o[6] != C for o in ops):
+        raise ValueError("every x must have the same number of columns")
+    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
+        _check_f64_cuda(t, name)
+    if a.dim() != 4 or tuple(a.shape[:2]) != (S, C) or b.shape != a.shape:
+        raise ValueError(f"a and b must both have shape ({S}, {C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
+    if tuple(center_x.shape) != (S, C):
+        raise ValueError(f"center_x must have shape ({S}, {C}), got {tuple(center_x.shape)}")
+    if C > CROSS_COV_MAX_COLUMNS:
+        raise ValueError(f"influence_cross_cov_batched: C = {C} columns, the limit is {CROSS_COV_MAX_COLUMNS} (the result "
+                         "has (C n_f)^2 entries per state)")
+    cu_dev = center_u.contiguous() if isinstance(center_u, torch.Tensor) else to_device(np.asarray(center_u, dtype=np.float64))
+    _check_f64_cuda(cu_dev, "center_u")
+    if tuple(cu_dev.shape) != (S,):
+        raise ValueError(f"center_u must hold {S} values, got shape {tuple(cu_dev.shape)}")
+    _, _, n_f, n_q = a.shape
+    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
+
+    # (x2, ls, lc, u, w, N, C, squeeze) per state: a one-row state has no pitch of its own
+    pitches = {o[1] for o in ops if o[5] > 1} or {ops[0][1]}
+    if not (as_given and len(pitches) == 1):
+        cu_host = center_u.cpu().numpy() if isinstance(center_u, torch.Tensor) else np.asarray(center_u, dtype=np.float64)
+        return torch.stack([influence_cross_cov(xs[s], us[s], a[s], b[s], float(cu_host[s]), center_x[s],
+                                                w=None if ws is None else ws[s]) for s in range(S)])
+
+    tab = (_lib.InfState * S)()
+    for s, (x2, _, _, u, w, N, _, _) in enumerate(ops):
+        tab[s].x, tab[s].u, tab[s].n = x2.data_ptr(), u.data_ptr(), N
+        tab[s].w = w.data_ptr() if w is not None else None
+    cov = torch.empty((S, C, n_f, C, n_f), dtype=F64, device="cuda")
+    wsb = workspace(L.txm_influence_cross_cov_batched_ws_bytes(S, max(o[5] for o in ops), C, n_f, n_q))
+    check(
+        L.txm_influence_cross_cov_batched(tab, S, pitches.pop(), C, n_f, n_q, _ptr(cu_dev), _ptr(center_x), _ptr(a), _ptr(b),
+                                          _ptr(cov), _ptr(wsb), wsb.numel(), _stream()),
+        "txm_influence_cross_cov_batched",
+    )
+    del ops
+    return cov
+
+
 def influence_block_cross_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: torch.Tensor, center_u: float,
                               center_x: torch.Tensor, block: int, n_levels: int = 1,
                               w: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:

@@ -750,8 +750,9 @@ class ExtrapModel(_Params):
         ``1 / (i! j!)`` factors of ``derivs(norm=True)``; ``minus_log`` acts per column as in ``derivs_cov``.
 
         The assumptions and the supported models are those of ``derivs_cov`` (first order, INDEPENDENT samples; anything
-        else raises the same NotImplementedError), with at most 255 observable columns (ValueError beyond).  Out of
-        scope here: state collections and multi-state models, ``gpr_input``.  A Dataset-valued observable comes back as
+        else raises the same NotImplementedError), with at most 255 observable columns (ValueError beyond).  State
+        collections and the multi-state models: ``StateCollection.derivs_cross_cov``; out of scope: ``gpr_input``.  A
+        Dataset-valued observable comes back as
         ONE array over its stacked variable dimension -- the blocks between two variables have no place in a Dataset.
 
         ``block=B`` (an int, ``1 <= B`` and ``2 B <= N``) is for a CORRELATED series kept whole, as in ``derivs_cov``:
@@ -985,6 +986,69 @@ class StateCollection(_Params):
             return [st._derivs_cov_device(order, bool(st.minus_log if minus_log is None else minus_log), blocks[s])[0].cpu().numpy()
                     for s, st in enumerate(self.states)], srcs
         return list(cov.cpu().numpy()), srcs
+
+    # ---- the same across the observable columns ---------------------------------------------------------
+    def _state_cross_covs(self, order=None, minus_log=None, block=None):
+        """``(covs, sources, orders)``: per state the host copy of its cross-column delta-method covariance
+        [n_out, order + 1, n_out, order + 1] (``ExtrapModel._derivs_cross_cov_device``).
+
+        Eligible states (``_delta_batch_eligible``, at most 255 columns, no ``block``): ONE copy of the stacked central
+        states to the host, the per-state coefficient algebra of ``_delta_coefs`` there, ONE
+        ``engine.influence_cross_cov_batched``.  The result is cached ON THE COLLECTION under
+        ``("dxcov_states", order, minus_log)``: the batch runs under a plan of its own, so a state with more samples than
+        its share of the device need not have the bits of its own call, and the states' ``("dxcov", ...)`` entries are
+        neither read nor written -- what a state's own ``derivs_cross_cov()`` returns does not depend on what was called
+        before it.  Other collections, and every call with ``block`` (``_blocks_per_state``), loop over the states."""
+        sts = self.states
+        blocks = self._blocks_per_state(block)
+        elig = self._delta_batch_eligible() if blocks is None else None
+        if elig is not None and int(np.prod(elig[0], dtype=np.int64)) <= engine.CROSS_COV_MAX_COLUMNS:
+            o = sts[0].order if order is None else order
+            ml = bool(sts[0].minus_log if minus_log is None else minus_log)
+            key = ("dxcov_states", o, ml)
+            if key not in self._cache:
+                ops = [st._delta_operands(device_state=True) for st in sts]         # raises what a state raises
+                host = torch.stack([op[3] for op in ops]).cpu().numpy()             # [S, C, 2, K]: one copy
+                co = [st._delta_coefs(host[s], o, ml) for s, st in enumerate(sts)]
+                cov = engine.influence_cross_cov_batched(
+                    [op[0] for op in ops], [op[1] for op in ops],
+                    engine.to_device(np.stack([c[0] for c in co])), engine.to_device(np.stack([c[1] for c in co])),
+                    np.array([c[2] for c in co]), engine.to_device(np.stack([c[3] for c in co])),
+                    ws=None if ops[0][2] is None else [op[2] for op in ops])
+                self._cache[key] = (cov.cpu().numpy(), [op[4] for op in ops])
+            host, srcs = self._cache[key]
+            return list(host), srcs, [o] * len(sts)
+        covs, srcs, orders = [], [], []
+        for s, st in enumerate(sts):
+            if not hasattr(st, "_derivs_cross_cov_device"):
+                raise NotImplementedError(f"derivs_cross_cov / predict_cov (delta-method covariance across columns): "
+                                          f"unsupported state {type(st).__name__}")
+            o = st.order if order is None else order
+            ml = bool(st.minus_log if minus_log is None else minus_log)
+            cov, src = st._derivs_cross_cov_device(o, ml, None if blocks is None else blocks[s])
+            covs.append(cov.cpu().numpy())
+            srcs.append(src)
+            orders.append(o)
+        return covs, srcs, orders
+
+    def derivs_cross_cov(self, order=None, norm=False, minus_log=None, block=None):
+        """Every state's ``ExtrapModel.derivs_cross_cov`` -- dims ``(order, order_2, *val_dims, *val_dims_2)`` -- joined
+        along the states, as ``derivs_cov`` joins its arrays.  The states are independent simulations: there are no blocks
+        between two states, and the covariance of anything linear in the states' derivatives is block diagonal in these.
+
+        States that share a column shape (at most 255 columns), order and derivatives object -- with ANY number of samples
+        each -- are served by one launch per kernel (txm_influence_cross_cov_batched) after one copy of their moments to
+        the host, and the result is cached on the collection.  A state's slice equals its own ``derivs_cross_cov()`` bit
+        for bit unless it has more samples than its share of the device (``256 * (8 CUs // (tile pairs * states))``);
+        then the same sums are added in another order, within the same rounding bound.  The states' own caches are not
+        touched.  Other collections loop over the states.
+
+        Assumptions: first order; independent states; independent samples within a state unless ``block`` is given (an
+        int for all states, or one entry per state: ``ExtrapModel.derivs_cross_cov(block=...)``, looped over the states).
+        A state that ``derivs_cov`` refuses raises its NotImplementedError, more than 255 columns ValueError."""
+        covs, srcs, orders = self._state_cross_covs(order, minus_log, block)
+        out = [ExtrapModel._derivs_cross_cov_labelled(covs[s], srcs[s], orders[s], norm) for s in range(len(self))]
+        return concat(out, dim=DataArray(np.asarray(self.alpha0), self.alpha_name))
 
     # states per launch of the batched path: the sampler table is [S * nrep][ntiles] and the grid carries the state on z
     _BATCH_MAX_REPS = 1 << 22
@@ -1419,6 +1483,43 @@ class ExtrapWeightedModel(StateCollection, PiecewiseMixin):
         std._inherit(src.coords)
         return pred, self[0]._ds(std)
 
+    def predict_cov(self, alpha, order=None, minus_log=None, alpha_name=None, method=None, bounded=False, block=None):
+        """``(predict(alpha, ...), cov)``: the blended prediction, bit for bit ``predict``'s, and the delta-method
+        covariance of the predicted columns, dims ``(*alpha dims, *val_dims, *[d + "_2" for d in val_dims])``:
+
+            cov[alpha, c, c'] = sum_i (w_i / sum w)^2 t_i' V_i[:, :, c, c'] t_i,    V_i = states[i].derivs_cross_cov(order)
+
+        with ``predict_with_error``'s weights and ``t``; its squared std is the diagonal ``c == c'`` up to rounding.  All
+        ``V_i`` come from one launch per kernel (``StateCollection.derivs_cross_cov``).  Assumptions: first order;
+        independent states; independent samples within a state unless ``block`` is given (an int, or one entry per
+        state)."""
+        self._check_alpha(alpha, bounded)
+        if order is None:
+            order = self.order
+        if alpha_name is None:
+            alpha_name = self.alpha_name
+        covs, srcs, _ = self._state_cross_covs(order, minus_log, block)      # (first: an unsupported state says so)
+        pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name, method=method, bounded=bounded)
+        al = xrwrap_alpha(alpha, name=alpha_name)
+        a0 = np.asarray(self.alpha0, dtype=np.float64)
+        fact = np.array([math.factorial(k) for k in range(order + 1)], dtype=np.float64)
+        pc = []
+        for a in np.asarray(al.values, dtype=np.float64).reshape(-1):
+            idx = [0, 1] if len(self) == 2 else self._indices_alpha(float(a), method)
+            dm = np.abs(a - a0[idx]) ** 20                                        # xr_weights_minkowski, m = 20
+            w = 1.0 - dm / dm.sum()
+            wn = w / w.sum()
+            v = 0.0
+            for wi, i in zip(wn, idx):
+                t = (a - a0[i]) ** np.arange(order + 1) / fact
+                v = v + wi * wi * np.einsum("i,cidj,j->cd", t, covs[i], t)
+            pc.append(v)
+        src = srcs[0]
+        out = DataArray(np.array(pc).reshape((*al.shape, *src.out_shape, *src.out_shape)),
+                        (*al.dims, *src.out_dims, *[d + "_2" for d in src.out_dims]))
+        out._inherit(al._coords)
+        return pred, ExtrapModel._cross_labels(out, src)
+
 
 class InterpModel(StateCollection):
     """One polynomial through the value and the first ``order`` derivatives at
@@ -1495,6 +1596,41 @@ class InterpModel(StateCollection):
         std = self._predict_std(alpha, order, minus_log, alpha_name, block)    # (first: an unsupported state says so)
         return self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name), std
 
+    def _predict_cov_from(self, alpha, order, alpha_name, covs, src):
+        """``cov[alpha, c, c'] = sum_s g_s' V_s[:, :, c, c'] g_s`` with the ``g`` of ``_predict_std`` and the states'
+        covariances handed in: ``covs[s]`` [n_out, order + 1, n_out, order + 1] on the host, one per state of THIS model
+        in order.  Labelled ``(*alpha dims, *val_dims, *val_dims_2)``."""
+        if len(covs) != len(self):
+            raise ValueError(f"{len(covs)} covariances for {len(self)} states")
+        inv = self._hermite_inverse(order)                              # [porder, state * (order + 1)]
+        al = xrwrap_alpha(alpha, name=alpha_name)
+        av = np.asarray(al.values, dtype=np.float64).reshape(-1)
+        g = (av[:, None] ** np.arange(inv.shape[0])[None, :]) @ inv     # (n_alpha, S (order + 1))
+        g = g.reshape(len(av), len(self), order + 1)
+        pc = sum(np.einsum("ai,cidj,aj->acd", g[:, s], covs[s], g[:, s]) for s in range(len(self)))
+        out = DataArray(pc.reshape((*al.shape, *src.out_shape, *src.out_shape)),
+                        (*al.dims, *src.out_dims, *[d + "_2" for d in src.out_dims]))
+        out._inherit(al._coords)
+        return ExtrapModel._cross_labels(out, src)
+
+    def predict_cov(self, alpha, order=None, minus_log=None, alpha_name=None, block=None):
+        """``(predict(alpha), cov)``: the interpolation, bit for bit ``predict``'s, and the delta-method covariance of the
+        predicted columns, dims ``(*alpha dims, *val_dims, *[d + "_2" for d in val_dims])``:
+
+            cov[alpha, c, c'] = sum_s g_s' V_s[:, :, c, c'] g_s,     V_s = states[s].derivs_cross_cov(order)
+
+        with ``g = (alpha^p) . hermite_inverse`` as in ``predict_with_error``, whose squared std is the diagonal
+        ``c == c'`` up to rounding.  All ``V_s`` come from one launch per kernel (``StateCollection.derivs_cross_cov``).
+        Assumptions: first order; independent states; independent samples within a state unless ``block`` is given (an
+        int, or one entry per state: the blocked ``V_s`` of correlated series kept whole)."""
+        if order is None:
+            order = self.order
+        if alpha_name is None:
+            alpha_name = self.alpha_name
+        covs, srcs, _ = self._state_cross_covs(order, minus_log, block)      # (first: an unsupported state says so)
+        pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name)
+        return pred, self._predict_cov_from(alpha, order, alpha_name, covs, srcs[0])
+
 
 class InterpModelPiecewise(StateCollection, PiecewiseMixin):
     """Two-state Hermite interpolation chosen per alpha (reference models.py:949-1006)."""
@@ -1542,6 +1678,33 @@ class InterpModelPiecewise(StateCollection, PiecewiseMixin):
             return pred, std_of((0, 1), alpha)
         seq = [float(a) for a in _alpha_seq(alpha)]
         outs = [std_of(self._indices_alpha(a, method), a) for a in seq]
+        if len(outs) == 1:
+            return pred, outs[0]
+        return pred, concat(outs, dim=DataArray(np.asarray(seq), alpha_name))
+
+    def predict_cov(self, alpha, order=None, minus_log=None, alpha_name=None, method=None, bounded=False, block=None):
+        """``(predict(alpha, ...), cov)``: for every alpha the two-state ``InterpModel`` that ``predict`` chooses
+        (``method``, ``bounded`` as there) and ``InterpModel.predict_cov``'s contraction over that pair's two
+        ``V_s = states[s].derivs_cross_cov(order)``; cov has dims ``(*alpha dims, *val_dims, *val_dims_2)``.  The
+        covariances of ALL states are taken once, at collection level (one launch per kernel), and handed to the pairs;
+        the pair models' caches hold no covariance.  Assumptions: first order; independent states; independent samples
+        within a state unless ``block`` is given (an int, or one entry per state)."""
+        self._check_alpha(alpha, bounded)
+        if order is None:
+            order = self.order
+        covs, srcs, _ = self._state_cross_covs(order, minus_log, block)      # (first: an unsupported state says so)
+        pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name, method=method, bounded=bounded)
+        if alpha_name is None:
+            alpha_name = self.alpha_name
+
+        def cov_of(idx, a):
+            pair = self.single_interpmodel(*idx)
+            return pair._predict_cov_from(a, order, alpha_name, [covs[int(i)] for i in idx], srcs[0])
+
+        if len(self) == 2:
+            return pred, cov_of((0, 1), alpha)
+        seq = [float(a) for a in _alpha_seq(alpha)]
+        outs = [cov_of(self._indices_alpha(a, method), a) for a in seq]
         if len(outs) == 1:
             return pred, outs[0]
         return pred, concat(outs, dim=DataArray(np.asarray(seq), alpha_name))
@@ -1667,6 +1830,16 @@ class MBARModel(StateCollection):
     def derivs_cov(self, order=None, norm=False, minus_log=None, block=None):
         raise NotImplementedError("derivs_cov (delta-method error bars of the states' derivatives): MBARModel predicts "
                                   "from the pooled samples, not from derivatives; its error bars are predict_with_error")
+
+    def derivs_cross_cov(self, order=None, norm=False, minus_log=None, block=None):
+        raise NotImplementedError("derivs_cross_cov (delta-method covariance of the states' derivatives across columns): "
+                                  "MBARModel predicts from the pooled samples, not from derivatives; its error bars are "
+                                  "predict_with_error")
+
+    def predict_cov(self, alpha, alpha_name=None, **kws):
+        raise NotImplementedError("predict_cov (delta-method covariance of the states' derivatives across columns): "
+                                  "MBARModel predicts from the pooled samples, not from derivatives; its error bars are "
+                                  "predict_with_error")
 
     def predict_with_error(self, alpha, alpha_name=None):
         """(mean, err): ``predict(alpha)`` bit for bit and its asymptotic standard deviation (pymbar's ``dA`` of
