@@ -27,11 +27,10 @@
 // state does not use leave at once.  So state s gets the bits of the single call on state s.
 #include <vector>
 
-#include "txm_common.h"
+#include "txm_influence_common.h"
 
 namespace txm {
 
-constexpr int INF_VEC2_MAXQ = 6;  // the largest n_q that takes two columns per lane
 constexpr int INF_BLOCK = 256;
 constexpr int INF_CH = 8;  // values per pass of the block reductions (8 * 256 doubles of LDS)
 
@@ -355,32 +354,21 @@ __global__ __launch_bounds__(INF_BLOCK) void influence_finalize_batch_kernel(
 // ---------------------------------------------------------------------------
 // host side
 
-struct InfPlan {
+struct InfPlan : InfLanes {
   bool rowmajor;
-  int vec, lpr_log2, cols_per_chunk, chunks, grid_x;
+  int grid_x;
   int64_t ld_series;
 };
 
 // One workgroup's share is 4 row slots: 4 * (256 >> lpr_log2) rows (row-major), 4 * 256 samples (series layout); the grid
 // grows by a workgroup per share up to 8 per CU and strides the rest.
-// two columns per lane (16-byte loads) while the sums of both columns fit the register file at two waves per SIMD
-static bool influence_vec2_ok(const double *x, int64_t ldx_s, int64_t C, int n_q) {
-  return (C % 2 == 0) && (ldx_s % 2 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && n_q <= INF_VEC2_MAXQ;
-}
-
 static InfPlan influence_plan_vec(bool vec2, int64_t ldx_s, int64_t ldx_c, int64_t N, int64_t C) {
   InfPlan p{};
   const int64_t cap = (int64_t)num_cus() * 8;
   p.rowmajor = ldx_c == 1 && !(C == 1 && ldx_s == 1);
   if (p.rowmajor) {
-    p.vec = vec2 ? 2 : 1;
-    const int64_t lanes = cdiv(C, p.vec);
-    int l2 = 0;
-    while ((1 << l2) < lanes && l2 < 8) ++l2;
-    p.lpr_log2 = l2;
-    p.cols_per_chunk = (1 << l2) * p.vec;
-    p.chunks = (int)cdiv(C, p.cols_per_chunk);
-    int64_t gx = cdiv(N, (int64_t)(INF_BLOCK >> l2) * 4);
+    static_cast<InfLanes &>(p) = inf_lanes(vec2, C);
+    int64_t gx = cdiv(N, (int64_t)(INF_BLOCK >> p.lpr_log2) * 4);
     p.grid_x = (int)(gx > cap ? cap : gx);
   } else {
     p.vec = 1;
@@ -397,7 +385,7 @@ static InfPlan influence_plan_vec(bool vec2, int64_t ldx_s, int64_t ldx_c, int64
 }
 
 static InfPlan influence_plan(const double *x, int64_t ldx_s, int64_t ldx_c, int64_t N, int64_t C, int n_q) {
-  return influence_plan_vec(influence_vec2_ok(x, ldx_s, C, n_q), ldx_s, ldx_c, N, C);
+  return influence_plan_vec(inf_vec2_ok(x, ldx_s, C, n_q), ldx_s, ldx_c, N, C);
 }
 
 static size_t influence_ws_bytes_impl(int64_t C, int n_q) {
@@ -506,13 +494,9 @@ extern "C" size_t txm_influence_cov_ws_bytes(int64_t N, int64_t C, int n_q) {
 extern "C" int txm_influence_cov(const double *x, int64_t ldx_s, int64_t ldx_c, const double *u, const double *w, int64_t N,
                                  int64_t C, int n_f, int n_q, double center_u, const double *center_x, const double *a,
                                  const double *b, double *cov, double *mean, void *ws, size_t ws_bytes, txm_stream stream) {
-  TXM_REQUIRE(x && u && center_x && a && b && cov && mean && ws, "influence_cov: null pointer");
-  TXM_REQUIRE(N >= 1 && C >= 1, "influence_cov: need N >= 1 and C >= 1 (N=%lld C=%lld)", (long long)N, (long long)C);
-  TXM_REQUIRE(C <= 65535, "influence_cov: C > 65535 unsupported");
-  TXM_REQUIRE(n_f >= 1 && n_f <= TXM_MAXK, "influence_cov: n_f=%d outside [1, %d]", n_f, TXM_MAXK);
-  TXM_REQUIRE(n_q >= 1 && n_q <= TXM_MAXK, "influence_cov: n_q=%d outside [1, %d]", n_q, TXM_MAXK);
-  TXM_REQUIRE(ldx_c == 1 || ldx_s == 1, "influence_cov: need ldx_c == 1 or ldx_s == 1");
-  TXM_REQUIRE(center_u == center_u, "influence_cov: center_u is NaN");
+  if (const int rc = inf_check_args("influence_cov", x && u && center_x && a && b && cov && mean && ws, N, C, 65535, "", n_f,
+                                    n_q, ldx_c == 1 || ldx_s == 1, "need ldx_c == 1 or ldx_s == 1", center_u))
+    return rc;
   const InfPlan p = influence_plan(x, ldx_s, ldx_c, N, C, n_q);
   if (p.rowmajor) TXM_REQUIRE(ldx_s >= C, "influence_cov: row pitch ldx_s < C");
   const size_t need = (size_t)p.chunks * p.grid_x * p.cols_per_chunk * (size_t)(3 * (2 * n_q - 1) + 2 * n_q) * sizeof(double);
@@ -522,15 +506,9 @@ extern "C" int txm_influence_cov(const double *x, int64_t ldx_s, int64_t ldx_c, 
   }
   hipStream_t st = (hipStream_t)stream;
   double *partial = (double *)ws;
-  switch (n_q) {
-#define TXM_INF_CASE(Q) \
-  case Q: return influence_launch<Q>(p, x, ldx_s, u, w, N, C, n_f, center_u, center_x, a, b, cov, mean, partial, st);
-    TXM_INF_CASE(1) TXM_INF_CASE(2) TXM_INF_CASE(3) TXM_INF_CASE(4) TXM_INF_CASE(5)
-    TXM_INF_CASE(6) TXM_INF_CASE(7) TXM_INF_CASE(8) TXM_INF_CASE(9)
-#undef TXM_INF_CASE
-  }
-  set_error("influence_cov: n_q out of range");
-  return TXM_ERR_INVALID;
+  return inf_dispatch(n_q, "influence_cov: n_q", [&](auto Q) {
+    return influence_launch<decltype(Q)::value>(p, x, ldx_s, u, w, N, C, n_f, center_u, center_x, a, b, cov, mean, partial, st);
+  });
 }
 
 extern "C" size_t txm_influence_cov_batched_ws_bytes(int64_t S, int64_t n_max, int64_t C, int n_q) {
@@ -543,23 +521,12 @@ extern "C" int txm_influence_cov_batched(const txm_inf_state *states_host, int64
                                          int n_q, const double *center_u, const double *center_x, const double *a,
                                          const double *b, double *cov, double *mean, void *ws, size_t ws_bytes,
                                          txm_stream stream) {
-  TXM_REQUIRE(states_host && center_u && center_x && a && b && cov && mean && ws, "influence_cov_batched: null pointer");
-  TXM_REQUIRE(S >= 1 && S <= 65535, "influence_cov_batched: S=%lld outside [1, 65535]", (long long)S);
-  TXM_REQUIRE(C >= 1 && C <= 65535, "influence_cov_batched: C=%lld outside [1, 65535]", (long long)C);
-  TXM_REQUIRE(n_f >= 1 && n_f <= TXM_MAXK, "influence_cov_batched: n_f=%d outside [1, %d]", n_f, TXM_MAXK);
-  TXM_REQUIRE(n_q >= 1 && n_q <= TXM_MAXK, "influence_cov_batched: n_q=%d outside [1, %d]", n_q, TXM_MAXK);
-  TXM_REQUIRE(ldx_s >= C, "influence_cov_batched: row pitch ldx_s < C");
-  const bool weighted = states_host[0].w != nullptr;
-  bool vec2 = true;
-  int64_t n_max = 0;
-  for (int64_t s = 0; s < S; ++s) {
-    const txm_inf_state &h = states_host[s];
-    TXM_REQUIRE(h.x && h.u, "influence_cov_batched: state %lld has a null pointer", (long long)s);
-    TXM_REQUIRE((h.w != nullptr) == weighted, "influence_cov_batched: weights for all states or for none");
-    TXM_REQUIRE(h.n >= 1, "influence_cov_batched: state %lld has n=%lld < 1", (long long)s, (long long)h.n);
-    vec2 = vec2 && influence_vec2_ok(h.x, ldx_s, C, n_q);
-    if (h.n > n_max) n_max = h.n;
-  }
+  bool weighted, vec2 = true;
+  int64_t n_max;
+  if (const int rc = inf_check_batch("influence_cov_batched", states_host && center_u && center_x && a && b && cov && mean && ws,
+                                     states_host, S, ldx_s, C, 65535, "", n_f, n_q, weighted, n_max))
+    return rc;
+  for (int64_t s = 0; s < S; ++s) vec2 = vec2 && inf_vec2_ok(states_host[s].x, ldx_s, C, n_q);
   // every state under the plan the single call makes for its own n (with the batch's column width); the launch takes
   // the widest state's grid
   static thread_local std::vector<inf_dev_state> tab_host;
@@ -582,15 +549,8 @@ extern "C" int txm_influence_cov_batched(const txm_inf_state *states_host, int64
   inf_dev_state *tab = (inf_dev_state *)ws;
   TXM_HIP(hipMemcpyAsync(tab, tab_host.data(), (size_t)S * sizeof(inf_dev_state), hipMemcpyHostToDevice, st));
   double *partial = (double *)((char *)ws + tab_bytes);
-  switch (n_q) {
-#define TXM_INF_CASE(Q)                                                                                                  \
-  case Q:                                                                                                                \
-    return influence_launch_batched<Q>(pmax, tab, S, weighted, ldx_s, C, n_f, center_u, center_x, a, b, cov, mean, partial, \
-                                       per_state, st);
-    TXM_INF_CASE(1) TXM_INF_CASE(2) TXM_INF_CASE(3) TXM_INF_CASE(4) TXM_INF_CASE(5)
-    TXM_INF_CASE(6) TXM_INF_CASE(7) TXM_INF_CASE(8) TXM_INF_CASE(9)
-#undef TXM_INF_CASE
-  }
-  set_error("influence_cov_batched: n_q out of range");
-  return TXM_ERR_INVALID;
+  return inf_dispatch(n_q, "influence_cov_batched: n_q", [&](auto Q) {
+    return influence_launch_batched<decltype(Q)::value>(pmax, tab, S, weighted, ldx_s, C, n_f, center_u, center_x, a, b, cov, mean,
+                                                        partial, per_state, st);
+  });
 }

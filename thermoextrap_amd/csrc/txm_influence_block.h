@@ -1,7 +1,7 @@
 // txm_influence_block.h -- pass 1 of the blocked delta-method covariance (txm_influence_block.hip), shared by
 // txm_influence_block_cov (f-11) and txm_influence_block_cross_cov (f-13): ONE kernel, ONE plan, the same bits in both.
 #pragma once
-#include "txm_common.h"
+#include "txm_influence_common.h"
 
 namespace txm {
 

@@ -26,7 +26,6 @@
 
 namespace txm {
 
-constexpr int IB_VEC2_MAXQ = 6;  // the largest n_q that takes two columns per lane (txm_influence.hip's limit)
 constexpr int IB_BLOCK = 256;
 constexpr int IB_CH = 8;  // values per pass of the workgroup reductions (8 * 256 doubles of LDS)
 
@@ -265,23 +264,16 @@ static bool ib_args_ok(int64_t N, int64_t C, int n_f, int n_q, int64_t block) {
   return N >= 1 && C >= 1 && C <= 65535 && n_f >= 1 && n_f <= TXM_MAXK && n_q >= 1 && n_q <= TXM_MAXK && block >= 1;
 }
 
-struct IbPlan {
-  int vec, lpr_log2, cols_per_chunk, chunks, rows, Bs, G, grid_x;
+struct IbPlan : InfLanes {
+  int rows, Bs, G, grid_x;
   int64_t nb;
   size_t lds_bytes;
 };
 
 static IbPlan ib_plan(const double *x, int64_t ldx_s, int64_t N, int64_t C, int n_q, int64_t block) {
   IbPlan p{};
-  const bool vec2 = (C % 2 == 0) && (ldx_s % 2 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && n_q <= IB_VEC2_MAXQ;
-  p.vec = vec2 ? 2 : 1;
-  const int64_t lanes = cdiv(C, p.vec);
-  int l2 = 0;
-  while ((1 << l2) < lanes && l2 < 8) ++l2;
-  p.lpr_log2 = l2;
-  p.cols_per_chunk = (1 << l2) * p.vec;
-  p.chunks = (int)cdiv(C, p.cols_per_chunk);
-  p.rows = IB_BLOCK >> l2;
+  static_cast<InfLanes &>(p) = inf_lanes(inf_vec2_ok(x, ldx_s, C, n_q), C);
+  p.rows = IB_BLOCK >> p.lpr_log2;
   p.Bs = block < p.rows ? (int)block : p.rows;
   p.G = p.rows / p.Bs;
   p.nb = cdiv(N, block);
@@ -300,7 +292,7 @@ static int ib_launch_sums(const IbPlan &p, const double *x, int64_t ldx_s, const
   hipLaunchKernelGGL((influence_block_sums_kernel<NQ, VEC, WT>), grid, blk, p.lds_bytes, st, x, ldx_s, u, w, N, C, cu, cx, a, b, \
                      n_f, block, p.nb, p.lpr_log2, p.Bs, p.G, zt, wb)
   if (p.vec == 2) {
-    if constexpr (NQ <= IB_VEC2_MAXQ) {
+    if constexpr (NQ <= INF_VEC2_MAXQ) {
       if (w) TXM_IB_RM(2, true); else TXM_IB_RM(2, false);
     } else {
       set_error("influence_block_cov: no two-column kernel for n_q=%d", NQ);
@@ -318,15 +310,9 @@ int ib_block_sums(const double *x, int64_t ldx_s, const double *u, const double 
                   double center_u, const double *center_x, const double *a, const double *b, int64_t block, double *zt,
                   double *wb, hipStream_t st) {
   const IbPlan p = ib_plan(x, ldx_s, N, C, n_q, block);
-  switch (n_q) {
-#define TXM_IB_CASE(Q) \
-  case Q: return ib_launch_sums<Q>(p, x, ldx_s, u, w, N, C, n_f, center_u, center_x, a, b, block, zt, wb, st);
-    TXM_IB_CASE(1) TXM_IB_CASE(2) TXM_IB_CASE(3) TXM_IB_CASE(4) TXM_IB_CASE(5)
-    TXM_IB_CASE(6) TXM_IB_CASE(7) TXM_IB_CASE(8) TXM_IB_CASE(9)
-#undef TXM_IB_CASE
-  }
-  set_error("influence_block_cov: n_q out of range");
-  return TXM_ERR_INVALID;
+  return inf_dispatch(n_q, "influence_block_cov: n_q", [&](auto Q) {
+    return ib_launch_sums<decltype(Q)::value>(p, x, ldx_s, u, w, N, C, n_f, center_u, center_x, a, b, block, zt, wb, st);
+  });
 }
 
 template <int NF>
@@ -351,15 +337,10 @@ extern "C" int txm_influence_block_cov(const double *x, int64_t ldx_s, const dou
                                        int n_f, int n_q, double center_u, const double *center_x, const double *a,
                                        const double *b, int64_t block, int n_levels, double *cov, double *mean, void *ws,
                                        size_t ws_bytes, txm_stream stream) {
-  TXM_REQUIRE(x && u && center_x && a && b && cov && mean && ws, "influence_block_cov: null pointer");
-  TXM_REQUIRE(N >= 1 && C >= 1, "influence_block_cov: need N >= 1 and C >= 1 (N=%lld C=%lld)", (long long)N, (long long)C);
-  TXM_REQUIRE(C <= 65535, "influence_block_cov: C > 65535 unsupported");
-  TXM_REQUIRE(n_f >= 1 && n_f <= TXM_MAXK, "influence_block_cov: n_f=%d outside [1, %d]", n_f, TXM_MAXK);
-  TXM_REQUIRE(n_q >= 1 && n_q <= TXM_MAXK, "influence_block_cov: n_q=%d outside [1, %d]", n_q, TXM_MAXK);
-  TXM_REQUIRE(ldx_s >= C, "influence_block_cov: row pitch ldx_s < C");
-  TXM_REQUIRE(center_u == center_u, "influence_block_cov: center_u is NaN");
-  TXM_REQUIRE(block >= 1, "influence_block_cov: block=%lld < 1", (long long)block);
-  TXM_REQUIRE(n_levels >= 1 && n_levels <= 32, "influence_block_cov: n_levels=%d outside [1, 32]", n_levels);
+  if (const int rc = inf_check_args("influence_block_cov", x && u && center_x && a && b && cov && mean && ws, N, C, 65535, "",
+                                    n_f, n_q, ldx_s >= C, "row pitch ldx_s < C", center_u))
+    return rc;
+  if (const int rc = inf_check_block("influence_block_cov", block, n_levels)) return rc;
   if (ws_bytes < txm_influence_block_cov_ws_bytes(N, C, n_f, n_q, block)) {
     set_error("influence_block_cov: workspace too small");
     return TXM_ERR_WORKSPACE;
@@ -369,13 +350,7 @@ extern "C" int txm_influence_block_cov(const double *x, int64_t ldx_s, const dou
   double *zt = (double *)ws, *wb = zt + (size_t)nb * C * n_f;
   const int rc = ib_block_sums(x, ldx_s, u, w, N, C, n_f, n_q, center_u, center_x, a, b, block, zt, wb, st);
   if (rc != TXM_OK) return rc;
-  switch (n_f) {
-#define TXM_IB_CASE(F) \
-  case F: return ib_launch_levels<F>(zt, wb, nb, C, n_levels, cov, mean, st);
-    TXM_IB_CASE(1) TXM_IB_CASE(2) TXM_IB_CASE(3) TXM_IB_CASE(4) TXM_IB_CASE(5)
-    TXM_IB_CASE(6) TXM_IB_CASE(7) TXM_IB_CASE(8) TXM_IB_CASE(9)
-#undef TXM_IB_CASE
-  }
-  set_error("influence_block_cov: n_f out of range");
-  return TXM_ERR_INVALID;
+  return inf_dispatch(n_f, "influence_block_cov: n_f", [&](auto F) {
+    return ib_launch_levels<decltype(F)::value>(zt, wb, nb, C, n_levels, cov, mean, st);
+  });
 }

@@ -29,8 +29,6 @@
 
 namespace txm {
 
-typedef double bx_v4d __attribute__((ext_vector_type(4)));
-
 constexpr int BX_BLOCK = 256;      // four waves
 constexpr int BX_MT = 4;           // tiles a side of a macro tile
 constexpr int BX_SHARE = 256;      // blocks a workgroup takes before the grid grows by one workgroup
@@ -39,18 +37,6 @@ constexpr int BX_MAXC = 255;       // as txm_influence_cross_cov
 constexpr int BX_REC = BX_MT * BX_MT * 256;  // doubles of one (workgroup, macro pair) record
 constexpr int BX_CS_COLS = 64;     // columns of a column-sum workgroup (four row slots)
 constexpr int BX_CS_MAXP = 256;    // row workgroups of the column sums at most
-
-// macro pair p of the upper triangle in row order: (0,0) (0,1) ... (0,TM-1) (1,1) ...
-__device__ __forceinline__ void bx_pair(int p, int TM, int &mi, int &mj) {
-  mi = 0;
-  while (p >= TM - mi) {
-    p -= TM - mi;
-    ++mi;
-  }
-  mj = mi + p;
-}
-
-__host__ __device__ __forceinline__ int bx_pair_index(int mi, int mj, int TM) { return mi * TM - mi * (mi - 1) / 2 + (mj - mi); }
 
 // part[blockIdx.y][M + 1]: the sums over the rows blockIdx.y * 4 + slot, + 4 gridDim.y, ... of zt's columns and (column M) wb,
 // the four row slots added in slot order
@@ -105,7 +91,7 @@ __global__ __launch_bounds__(BX_BLOCK) void influence_block_merge_kernel(double 
 template <bool DIAG>
 __device__ __forceinline__ void bx_accumulate(const double *__restrict__ zt, int64_t rs, int64_t nbl, int M, int ca, int cb,
                                               int nta, int ntb, int64_t ib0, int64_t stride, int k4,
-                                              bx_v4d (&acc)[BX_MT][BX_MT]) {
+                                              inf_v4d (&acc)[BX_MT][BX_MT]) {
   int oa[BX_MT], ob[BX_MT];  // the lane's column of tile t, or 0 where there is none
 #pragma unroll
   for (int t = 0; t < BX_MT; ++t) {
@@ -152,16 +138,16 @@ __global__ __launch_bounds__(BX_BLOCK) void influence_block_gram_kernel(const do
   __shared__ double red[4 * 256];
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, m = lane & 15, k4 = lane >> 4;
   int mi, mj;
-  bx_pair((int)blockIdx.x, TM, mi, mj);
+  inf_pair((int)blockIdx.x, TM, mi, mj);  // macro pair (mi <= mj)
   // logical columns of this lane's A rows and B columns in tile 0 of the macro pair; tiles of the pair that exist
   const int ca = 16 * BX_MT * mi + m, cb = 16 * BX_MT * mj + m;
   const int nta = min(BX_MT, T - BX_MT * mi), ntb = min(BX_MT, T - BX_MT * mj);
 
-  bx_v4d acc[BX_MT][BX_MT];
+  inf_v4d acc[BX_MT][BX_MT];
 #pragma unroll
   for (int ta = 0; ta < BX_MT; ++ta)
 #pragma unroll
-    for (int tb = 0; tb < BX_MT; ++tb) acc[ta][tb] = bx_v4d{0.0, 0.0, 0.0, 0.0};
+    for (int tb = 0; tb < BX_MT; ++tb) acc[ta][tb] = inf_v4d{0.0, 0.0, 0.0, 0.0};
 
   const int64_t stride = (int64_t)gridDim.y * 4 * 4, ib0 = ((int64_t)blockIdx.y * 4 + wave) * 4;
   if (mi == mj)
@@ -186,11 +172,7 @@ __global__ __launch_bounds__(BX_BLOCK) void influence_block_gram_kernel(const do
 // G[e] = sum over the nblk workgroups, in index order, of partial[blk][e]      (e < per_blk = macro pairs * BX_REC)
 __global__ __launch_bounds__(BX_BLOCK) void influence_block_gram_sum_kernel(const double *__restrict__ partial, int nblk,
                                                                             size_t per_blk, double *__restrict__ G) {
-  const size_t e = (size_t)blockIdx.x * BX_BLOCK + threadIdx.x;
-  if (e >= per_blk) return;
-  double acc = 0.0;
-  for (int b = 0; b < nblk; ++b) acc += partial[(size_t)b * per_blk + e];
-  G[e] = acc;
+  inf_sum_records(partial, nblk, per_blk, G);
 }
 
 // cov [M][M]; a thread per (P, Q), the threads with P <= Q store both
@@ -202,7 +184,7 @@ __global__ __launch_bounds__(BX_BLOCK) void influence_block_cross_final_kernel(c
   const size_t P = e / Ms, Q = e % Ms;
   if (P > Q) return;
   const int ti = (int)(P >> 4), tj = (int)(Q >> 4);
-  const double g = G[(size_t)bx_pair_index(ti / BX_MT, tj / BX_MT, TM) * BX_REC +
+  const double g = G[(size_t)inf_pair_index(ti / BX_MT, tj / BX_MT, TM) * BX_REC +
                      ((ti % BX_MT) * BX_MT + (tj % BX_MT)) * 256 + (P & 15) * 16 + (Q & 15)];
   const double W = wtot[0];
   const double v = W == 0.0 ? 0.0 : g / (W * W);
@@ -264,16 +246,11 @@ extern "C" int txm_influence_block_cross_cov(const double *x, int64_t ldx_s, con
                                              int64_t C, int n_f, int n_q, double center_u, const double *center_x,
                                              const double *a, const double *b, int64_t block, int n_levels, double *cov,
                                              double *mean, void *ws, size_t ws_bytes, txm_stream stream) {
-  TXM_REQUIRE(x && u && center_x && a && b && cov && mean && ws, "influence_block_cross_cov: null pointer");
-  TXM_REQUIRE(N >= 1 && C >= 1, "influence_block_cross_cov: need N >= 1 and C >= 1 (N=%lld C=%lld)", (long long)N,
-              (long long)C);
-  TXM_REQUIRE(C <= BX_MAXC, "influence_block_cross_cov: C > %d unsupported (the result has (C n_f)^2 entries a level)", BX_MAXC);
-  TXM_REQUIRE(n_f >= 1 && n_f <= TXM_MAXK, "influence_block_cross_cov: n_f=%d outside [1, %d]", n_f, TXM_MAXK);
-  TXM_REQUIRE(n_q >= 1 && n_q <= TXM_MAXK, "influence_block_cross_cov: n_q=%d outside [1, %d]", n_q, TXM_MAXK);
-  TXM_REQUIRE(ldx_s >= C, "influence_block_cross_cov: row pitch ldx_s < C");
-  TXM_REQUIRE(center_u == center_u, "influence_block_cross_cov: center_u is NaN");
-  TXM_REQUIRE(block >= 1, "influence_block_cross_cov: block=%lld < 1", (long long)block);
-  TXM_REQUIRE(n_levels >= 1 && n_levels <= 32, "influence_block_cross_cov: n_levels=%d outside [1, 32]", n_levels);
+  if (const int rc = inf_check_args("influence_block_cross_cov", x && u && center_x && a && b && cov && mean && ws, N, C, BX_MAXC,
+                                    " (the result has (C n_f)^2 entries a level)", n_f, n_q, ldx_s >= C, "row pitch ldx_s < C",
+                                    center_u))
+    return rc;
+  if (const int rc = inf_check_block("influence_block_cross_cov", block, n_levels)) return rc;
   if (ws_bytes < txm_influence_block_cross_cov_ws_bytes(N, C, n_f, n_q, block, n_levels)) {
     set_error("influence_block_cross_cov: workspace too small");
     return TXM_ERR_WORKSPACE;

@@ -39,11 +39,9 @@
 // cx_plan would give it alone has the single call's bits.
 #include <vector>
 
-#include "txm_common.h"
+#include "txm_influence_common.h"
 
 namespace txm {
-
-typedef double cx_v4d __attribute__((ext_vector_type(4)));
 
 constexpr int CX_BLOCK = 256;  // four waves
 constexpr int CX_SHARE = 256;  // samples a workgroup takes before the grid grows by one workgroup
@@ -52,18 +50,6 @@ constexpr int CX_UNR = 4;      // 4-sample steps a wave has in flight
 
 // doubles of one (workgroup, tile pair) record: R tiles of 16 x 16, then the total weight (padded to 8)
 __host__ __device__ constexpr int cx_rec(int n_q) { return (2 * n_q - 1) * 256 + 8; }
-
-// tile pair p of the upper triangle in row order: (0,0) (0,1) ... (0,T-1) (1,1) ...
-__device__ __forceinline__ void cx_pair(int p, int T, int &ti, int &tj) {
-  ti = 0;
-  while (p >= T - ti) {
-    p -= T - ti;
-    ++ti;
-  }
-  tj = ti + p;
-}
-
-__host__ __device__ __forceinline__ int cx_pair_index(int ti, int tj, int T) { return ti * T - ti * (ti - 1) / 2 + (tj - ti); }
 
 // One state of a batched call as the kernels read it (built on the host from txm_inf_state and the batch's plan):
 // grid_x sample workgroups, its slice of the workspace at `off` doubles: grid_x * pairs records, then pairs summed ones.
@@ -85,7 +71,7 @@ __device__ __forceinline__ void influence_cross_body(const double *__restrict__ 
   __shared__ double sws[16];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, k4 = lane >> 4;
   int ti, tj;
-  cx_pair((int)blockIdx.x, T, ti, tj);
+  inf_pair((int)blockIdx.x, T, ti, tj);  // tile pair (ti <= tj)
   const bool diag = ti == tj;
   // logical columns of this lane's A row and B column: < C an observable, C the ones, above it nothing
   const int ca = 16 * ti + m, cb = 16 * tj + m;
@@ -93,9 +79,9 @@ __device__ __forceinline__ void influence_cross_body(const double *__restrict__ 
   const double a_one = ca == C ? 1.0 : 0.0, b_one = cb == C ? 1.0 : 0.0;
   const double pa = a_x ? cx[ca] : 0.0, pb = b_x ? cx[cb] : 0.0;
 
-  cx_v4d acc[R];
+  inf_v4d acc[R];
 #pragma unroll
-  for (int r = 0; r < R; ++r) acc[r] = cx_v4d{0.0, 0.0, 0.0, 0.0};
+  for (int r = 0; r < R; ++r) acc[r] = inf_v4d{0.0, 0.0, 0.0, 0.0};
   double sw = 0.0;
 
   // wave wg of NW takes the 4-sample steps wg, wg + NW, ...; the loop bounds are wave-uniform
@@ -173,19 +159,10 @@ __global__ __launch_bounds__(CX_BLOCK) void influence_cross_batch_kernel(const c
                                      (int)blockIdx.y, (int)s.grid_x, ws + s.off);
 }
 
-// G[e] = sum over the nblk workgroups, in index order, of partial[blk][e]      (e < per_blk = pairs * REC)
-__device__ __forceinline__ void influence_cross_sum_body(const double *__restrict__ partial, int nblk, size_t per_blk,
-                                                         double *__restrict__ G) {
-  const size_t e = (size_t)blockIdx.x * CX_BLOCK + threadIdx.x;
-  if (e >= per_blk) return;
-  double acc = 0.0;
-  for (int b = 0; b < nblk; ++b) acc += partial[(size_t)b * per_blk + e];
-  G[e] = acc;
-}
-
+// the workgroups' records in index order (inf_sum_records): per_blk = pairs * REC
 __global__ __launch_bounds__(CX_BLOCK) void influence_cross_sum_kernel(const double *__restrict__ partial, int nblk,
                                                                        size_t per_blk, double *__restrict__ G) {
-  influence_cross_sum_body(partial, nblk, per_blk, G);
+  inf_sum_records(partial, nblk, per_blk, G);
 }
 
 // blockIdx.y = state: its grid_x records of per_blk doubles, the summed record behind them
@@ -193,7 +170,7 @@ __global__ __launch_bounds__(CX_BLOCK) void influence_cross_sum_batch_kernel(con
                                                                              size_t per_blk, double *__restrict__ ws) {
   const cx_dev_state s = tab[blockIdx.y];
   double *partial = ws + s.off;
-  influence_cross_sum_body(partial, (int)s.grid_x, per_blk, partial + (size_t)s.grid_x * per_blk);
+  inf_sum_records(partial, (int)s.grid_x, per_blk, partial + (size_t)s.grid_x * per_blk);
 }
 
 // cov [C n_f][C n_f]; a thread per (P, Q) = ((c, i), (c', j)), the threads with P <= Q compute and store both
@@ -210,7 +187,7 @@ __device__ __forceinline__ void influence_cross_final_body(const double *__restr
   const int c = (int)(P / n_f), i = (int)(P % n_f), d = (int)(Q / n_f), j = (int)(Q % n_f);  // c <= d
   // G_r at (row, col), row <= col, as logical columns: the ones are column C
   auto at = [&](int row, int col) {
-    return G + (size_t)cx_pair_index(row >> 4, col >> 4, T) * REC + (row & 15) * 16 + (col & 15);
+    return G + (size_t)inf_pair_index(row >> 4, col >> 4, T) * REC + (row & 15) * 16 + (col & 15);
   };
   const double *g11 = at(C, C), *g1d = at(d, C), *gc1 = at(c, C), *gcd = at(c, d);
   double t11[R], t1d[R], tc1[R], tcd[R];
@@ -354,28 +331,18 @@ extern "C" int txm_influence_cross_cov(const double *x, int64_t ldx_s, const dou
                                        int64_t C, int n_f, int n_q, double center_u, const double *center_x,
                                        const double *a, const double *b, double *cov, void *ws, size_t ws_bytes,
                                        txm_stream stream) {
-  TXM_REQUIRE(x && u && center_x && a && b && cov && ws, "influence_cross_cov: null pointer");
-  TXM_REQUIRE(N >= 1 && C >= 1, "influence_cross_cov: need N >= 1 and C >= 1 (N=%lld C=%lld)", (long long)N, (long long)C);
-  TXM_REQUIRE(C <= CX_MAXC, "influence_cross_cov: C > %d unsupported (the result has (C n_f)^2 entries)", CX_MAXC);
-  TXM_REQUIRE(n_f >= 1 && n_f <= TXM_MAXK, "influence_cross_cov: n_f=%d outside [1, %d]", n_f, TXM_MAXK);
-  TXM_REQUIRE(n_q >= 1 && n_q <= TXM_MAXK, "influence_cross_cov: n_q=%d outside [1, %d]", n_q, TXM_MAXK);
-  TXM_REQUIRE(ldx_s >= C, "influence_cross_cov: row pitch ldx_s < C");
-  TXM_REQUIRE(center_u == center_u, "influence_cross_cov: center_u is NaN");
+  if (const int rc = inf_check_args("influence_cross_cov", x && u && center_x && a && b && cov && ws, N, C, CX_MAXC,
+                                    " (the result has (C n_f)^2 entries)", n_f, n_q, ldx_s >= C, "row pitch ldx_s < C", center_u))
+    return rc;
   if (ws_bytes < txm_influence_cross_cov_ws_bytes(N, C, n_f, n_q)) {
     set_error("influence_cross_cov: workspace too small");
     return TXM_ERR_WORKSPACE;
   }
   const CxPlan p = cx_plan(N, C);
   hipStream_t st = (hipStream_t)stream;
-  switch (n_q) {
-#define TXM_CX_CASE(Q) \
-  case Q: return cx_launch<Q>(p, x, ldx_s, u, w, N, (int)C, n_f, center_u, center_x, a, b, cov, (double *)ws, st);
-    TXM_CX_CASE(1) TXM_CX_CASE(2) TXM_CX_CASE(3) TXM_CX_CASE(4) TXM_CX_CASE(5)
-    TXM_CX_CASE(6) TXM_CX_CASE(7) TXM_CX_CASE(8) TXM_CX_CASE(9)
-#undef TXM_CX_CASE
-  }
-  set_error("influence_cross_cov: n_q out of range");
-  return TXM_ERR_INVALID;
+  return inf_dispatch(n_q, "influence_cross_cov: n_q", [&](auto Q) {
+    return cx_launch<decltype(Q)::value>(p, x, ldx_s, u, w, N, (int)C, n_f, center_u, center_x, a, b, cov, (double *)ws, st);
+  });
 }
 
 static bool cx_batched_shape_ok(int64_t S, int64_t C, int n_f, int n_q) {
@@ -398,22 +365,12 @@ extern "C" int txm_influence_cross_cov_batched(const txm_inf_state *states_host,
                                                int n_f, int n_q, const double *center_u, const double *center_x,
                                                const double *a, const double *b, double *cov, void *ws, size_t ws_bytes,
                                                txm_stream stream) {
-  TXM_REQUIRE(states_host && center_u && center_x && a && b && cov && ws, "influence_cross_cov_batched: null pointer");
-  TXM_REQUIRE(S >= 1 && S <= 65535, "influence_cross_cov_batched: S=%lld outside [1, 65535]", (long long)S);
-  TXM_REQUIRE(C >= 1 && C <= CX_MAXC, "influence_cross_cov_batched: C=%lld outside [1, %d] (the result has (C n_f)^2 entries)",
-              (long long)C, CX_MAXC);
-  TXM_REQUIRE(n_f >= 1 && n_f <= TXM_MAXK, "influence_cross_cov_batched: n_f=%d outside [1, %d]", n_f, TXM_MAXK);
-  TXM_REQUIRE(n_q >= 1 && n_q <= TXM_MAXK, "influence_cross_cov_batched: n_q=%d outside [1, %d]", n_q, TXM_MAXK);
-  TXM_REQUIRE(ldx_s >= C, "influence_cross_cov_batched: row pitch ldx_s < C");
-  const bool weighted = states_host[0].w != nullptr;
-  int64_t n_max = 0;
-  for (int64_t s = 0; s < S; ++s) {
-    const txm_inf_state &h = states_host[s];
-    TXM_REQUIRE(h.x && h.u, "influence_cross_cov_batched: state %lld has a null pointer", (long long)s);
-    TXM_REQUIRE((h.w != nullptr) == weighted, "influence_cross_cov_batched: weights for all states or for none");
-    TXM_REQUIRE(h.n >= 1, "influence_cross_cov_batched: state %lld has n=%lld < 1", (long long)s, (long long)h.n);
-    if (h.n > n_max) n_max = h.n;
-  }
+  bool weighted;
+  int64_t n_max;
+  if (const int rc = inf_check_batch("influence_cross_cov_batched", states_host && center_u && center_x && a && b && cov && ws,
+                                     states_host, S, ldx_s, C, CX_MAXC, " (the result has (C n_f)^2 entries)", n_f, n_q,
+                                     weighted, n_max))
+    return rc;
   const int T = (int)((C + 1 + 15) / 16), pairs = T * (T + 1) / 2;
   const size_t rec = (size_t)cx_rec(n_q);
   static thread_local std::vector<cx_dev_state> tab_host;
@@ -436,15 +393,8 @@ extern "C" int txm_influence_cross_cov_batched(const txm_inf_state *states_host,
   cx_dev_state *tab = (cx_dev_state *)ws;
   TXM_HIP(hipMemcpyAsync(tab, tab_host.data(), (size_t)S * sizeof(cx_dev_state), hipMemcpyHostToDevice, st));
   double *recs = (double *)((char *)ws + tab_bytes);
-  switch (n_q) {
-#define TXM_CX_CASE(Q)                                                                                                   \
-  case Q:                                                                                                                \
-    return cx_launch_batched<Q>(tab, S, weighted, T, pairs, grid_max, ldx_s, (int)C, n_f, center_u, center_x, a, b, cov, \
-                                recs, st);
-    TXM_CX_CASE(1) TXM_CX_CASE(2) TXM_CX_CASE(3) TXM_CX_CASE(4) TXM_CX_CASE(5)
-    TXM_CX_CASE(6) TXM_CX_CASE(7) TXM_CX_CASE(8) TXM_CX_CASE(9)
-#undef TXM_CX_CASE
-  }
-  set_error("influence_cross_cov_batched: n_q out of range");
-  return TXM_ERR_INVALID;
+  return inf_dispatch(n_q, "influence_cross_cov_batched: n_q", [&](auto Q) {
+    return cx_launch_batched<decltype(Q)::value>(tab, S, weighted, T, pairs, grid_max, ldx_s, (int)C, n_f, center_u, center_x, a,
+                                                 b, cov, recs, st);
+  });
 }

@@ -772,6 +772,71 @@ def cov_over_rep(vals: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---- shared pieces of the six influence entry points ---------------------------------------------------------------------
+CROSS_COV_MAX_COLUMNS = 255  # include/txmom.h (f-12): C + 1 logical columns in at most 16 tiles a side
+
+
+def _influence_coefs(a, b, center_x, lead):
+    """``(a, b, center_x, n_f, n_q)``, checked and contiguous: a, b ``(*lead, n_f, n_q)`` and center_x ``lead``, with
+    ``lead = (C,)`` for one state -- the ``a.dim() != 3 or a.shape[0] != C`` check -- and ``(S, C)`` for a batch."""
+    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
+        _check_f64_cuda(t, name)
+    if a.dim() != len(lead) + 2 or tuple(a.shape[:len(lead)]) != lead or b.shape != a.shape:
+        raise ValueError(f"a and b must both have shape {str(lead)[:-1].rstrip(',')}, n_f, n_q), got {tuple(a.shape)} and "
+                         f"{tuple(b.shape)}")
+    if tuple(center_x.shape) != lead:
+        raise ValueError(f"center_x must have shape {lead}, got {tuple(center_x.shape)}")
+    return a.contiguous(), b.contiguous(), center_x.contiguous(), a.shape[-2], a.shape[-1]
+
+
+def _check_cross_columns(fn, C, per=""):
+    if C > CROSS_COV_MAX_COLUMNS:
+        raise ValueError(f"{fn}: C = {C} columns, the limit is {CROSS_COV_MAX_COLUMNS} (the result has (C n_f)^2 entries{per})")
+
+
+def _block_levels_args(block, n_levels):
+    block, n_levels = int(block), int(n_levels)
+    if block < 1 or not 1 <= n_levels <= 32:
+        raise ValueError(f"need block >= 1 and 1 <= n_levels <= 32, got block={block}, n_levels={n_levels}")
+    return block, n_levels
+
+
+def _influence_states(xs, us, ws, rule):
+    """``(ops, ws, S, C, pitches, tab)`` of a batched call: ``_operands`` of every state under ``rule`` (ws None when no
+    state has weights), the set of the states' row pitches (one entry: one launch can serve them) and the filled
+    ``_lib.InfState`` table."""
+    S = len(xs)
+    if S < 1 or len(us) != S or (ws is not None and len(ws) != S):
+        raise ValueError("need the same number (>= 1) of x, u (and w) tensors")
+    if ws is not None and any(w is None for w in ws) and not all(w is None for w in ws):
+        raise ValueError("weights for all states or for none")
+    if ws is not None and ws[0] is None:
+        ws = None
+    ops = [_operands(xs[s], us[s], None if ws is None else ws[s], rule) for s in range(S)]
+    C = ops[0][6]
+    if any(o[6] != C for o in ops):
+        raise ValueError("every x must have the same number of columns")
+    # (x2, ls, lc, u, w, N, C, squeeze) per state: a one-row state has no pitch of its own
+    pitches = {o[1] for o in ops if o[5] > 1} or {ops[0][1]}
+    tab = (_lib.InfState * S)()
+    for s, (x2, _, _, u, w, N, _, _) in enumerate(ops):
+        tab[s].x, tab[s].u, tab[s].n = x2.data_ptr(), u.data_ptr(), N
+        tab[s].w = w.data_ptr() if w is not None else None
+    return ops, ws, S, C, pitches, tab
+
+
+def _center_u_device(center_u, S):
+    cu_dev = center_u.contiguous() if isinstance(center_u, torch.Tensor) else to_device(np.asarray(center_u, dtype=np.float64))
+    _check_f64_cuda(cu_dev, "center_u")
+    if tuple(cu_dev.shape) != (S,):
+        raise ValueError(f"center_u must hold {S} values, got shape {tuple(cu_dev.shape)}")
+    return cu_dev
+
+
+def _center_u_host(center_u):
+    return center_u.cpu().numpy() if isinstance(center_u, torch.Tensor) else np.asarray(center_u, dtype=np.float64)
+
+
 def influence_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: torch.Tensor, center_u: float,
                   center_x: torch.Tensor, w: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """Delta-method covariance of n_f estimates per column from their influence polynomials (txm_influence_cov):
@@ -781,14 +846,7 @@ def influence_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: torch.Te
     ``sum w psi_k / sum w``.  One pass over x."""
     L = _L()
     x2, ls, lc, u, w, N, C, _ = _operands(x, u, w, "either")
-    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
-        _check_f64_cuda(t, name)
-    if a.dim() != 3 or a.shape[0] != C or b.shape != a.shape:
-        raise ValueError(f"a and b must both have shape ({C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
-    if center_x.shape != (C,):
-        raise ValueError(f"center_x must have shape ({C},), got {tuple(center_x.shape)}")
-    _, n_f, n_q = a.shape
-    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
+    a, b, center_x, n_f, n_q = _influence_coefs(a, b, center_x, (C,))
     cov = torch.empty((C, n_f, n_f), dtype=F64, device="cuda")
     mean = torch.empty((C, n_f), dtype=F64, device="cuda")
     ws = workspace(L.txm_influence_cov_ws_bytes(N, C, n_q))
@@ -812,44 +870,17 @@ def influence_cov_batched(xs, us, a: torch.Tensor, b: torch.Tensor, center_u, ce
     alignment; otherwise the single call would pick another kernel for some state, and this loops over ``influence_cov``
     so that the promise above holds."""
     L = _L()
-    S = len(xs)
-    if S < 1 or len(us) != S or (ws is not None and len(ws) != S):
-        raise ValueError("need the same number (>= 1) of x, u (and w) tensors")
-    if ws is not None and any(w is None for w in ws) and not all(w is None for w in ws):
-        raise ValueError("weights for all states or for none")
-    if ws is not None and ws[0] is None:
-        ws = None
-    ops = [_operands(xs[s], us[s], None if ws is None else ws[s], "either") for s in range(S)]
-    C = ops[0][6]
-    if any(o[6] != C for o in ops):
-        raise ValueError("every x must have the same number of columns")
-    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
-        _check_f64_cuda(t, name)
-    if a.dim() != 4 or tuple(a.shape[:2]) != (S, C) or b.shape != a.shape:
-        raise ValueError(f"a and b must both have shape ({S}, {C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
-    if tuple(center_x.shape) != (S, C):
-        raise ValueError(f"center_x must have shape ({S}, {C}), got {tuple(center_x.shape)}")
-    cu_dev = center_u.contiguous() if isinstance(center_u, torch.Tensor) else to_device(np.asarray(center_u, dtype=np.float64))
-    _check_f64_cuda(cu_dev, "center_u")
-    if tuple(cu_dev.shape) != (S,):
-        raise ValueError(f"center_u must hold {S} values, got shape {tuple(cu_dev.shape)}")
-    _, _, n_f, n_q = a.shape
-    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
-
-    # (x2, ls, lc, u, w, N, C, squeeze) per state: a one-row state has no pitch of its own
-    pitches = {o[1] for o in ops if o[5] > 1} or {ops[0][1]}
+    ops, ws, S, C, pitches, tab = _influence_states(xs, us, ws, "either")
+    a, b, center_x, n_f, n_q = _influence_coefs(a, b, center_x, (S, C))
+    cu_dev = _center_u_device(center_u, S)
     one_launch = (all(o[2] == 1 for o in ops) and len(pitches) == 1
                   and len({o[0].data_ptr() & 15 == 0 for o in ops}) == 1)
     if not one_launch:
-        cu_host = center_u.cpu().numpy() if isinstance(center_u, torch.Tensor) else np.asarray(center_u, dtype=np.float64)
+        cu_host = _center_u_host(center_u)
         parts = [influence_cov(xs[s], us[s], a[s], b[s], float(cu_host[s]), center_x[s], w=None if ws is None else ws[s])
                  for s in range(S)]
         return torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts])
 
-    tab = (_lib.InfState * S)()
-    for s, (x2, _, _, u, w, N, _, _) in enumerate(ops):
-        tab[s].x, tab[s].u, tab[s].n = x2.data_ptr(), u.data_ptr(), N
-        tab[s].w = w.data_ptr() if w is not None else None
     cov = torch.empty((S, C, n_f, n_f), dtype=F64, device="cuda")
     mean = torch.empty((S, C, n_f), dtype=F64, device="cuda")
     wsb = workspace(L.txm_influence_cov_batched_ws_bytes(S, max(o[5] for o in ops), C, n_q))
@@ -889,17 +920,8 @@ def influence_block_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: to
     pass over x."""
     L = _L()
     x2, ls, _, u, w, N, C, _ = _operands(x, u, w, "rowmajor")
-    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
-        _check_f64_cuda(t, name)
-    if a.dim() != 3 or a.shape[0] != C or b.shape != a.shape:
-        raise ValueError(f"a and b must both have shape ({C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
-    if center_x.shape != (C,):
-        raise ValueError(f"center_x must have shape ({C},), got {tuple(center_x.shape)}")
-    block, n_levels = int(block), int(n_levels)
-    if block < 1 or not 1 <= n_levels <= 32:
-        raise ValueError(f"need block >= 1 and 1 <= n_levels <= 32, got block={block}, n_levels={n_levels}")
-    _, n_f, n_q = a.shape
-    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
+    a, b, center_x, n_f, n_q = _influence_coefs(a, b, center_x, (C,))
+    block, n_levels = _block_levels_args(block, n_levels)
     cov = torch.empty((n_levels, C, n_f, n_f), dtype=F64, device="cuda")
     mean = torch.empty((C, n_f), dtype=F64, device="cuda")
     ws = workspace(L.txm_influence_block_cov_ws_bytes(N, C, n_f, n_q, block))
@@ -911,9 +933,6 @@ def influence_block_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: to
     return cov, mean
 
 
-CROSS_COV_MAX_COLUMNS = 255  # include/txmom.h (f-12): C + 1 logical columns in at most 16 tiles a side
-
-
 def influence_cross_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: torch.Tensor, center_u: float,
                         center_x: torch.Tensor, w: torch.Tensor | None = None) -> torch.Tensor:
     """Delta-method covariance ACROSS the columns (txm_influence_cross_cov): with psi_k(n, c) as in ``influence_cov`` and
@@ -923,17 +942,8 @@ def influence_cross_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor, b: to
     samples are assumed; ``influence_block_cross_cov`` is the blocked form for a correlated series."""
     L = _L()
     x2, ls, _, u, w, N, C, _ = _operands(x, u, w, "rowmajor")
-    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
-        _check_f64_cuda(t, name)
-    if a.dim() != 3 or a.shape[0] != C or b.shape != a.shape:
-        raise ValueError(f"a and b must both have shape ({C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
-    if center_x.shape != (C,):
-        raise ValueError(f"center_x must have shape ({C},), got {tuple(center_x.shape)}")
-    if C > CROSS_COV_MAX_COLUMNS:
-        raise ValueError(f"influence_cross_cov: C = {C} columns, the limit is {CROSS_COV_MAX_COLUMNS} (the result has "
-                         "(C n_f)^2 entries)")
-    _, n_f, n_q = a.shape
-    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
+    a, b, center_x, n_f, n_q = _influence_coefs(a, b, center_x, (C,))
+    _check_cross_columns("influence_cross_cov", C)
     cov = torch.empty((C, n_f, C, n_f), dtype=F64, device="cuda")
     ws = workspace(L.txm_influence_cross_cov_ws_bytes(N, C, n_f, n_q))
     check(
@@ -959,45 +969,16 @@ def influence_cross_cov_batched(xs, us, a: torch.Tensor, b: torch.Tensor, center
     The one launch needs every x row-major with one pitch; otherwise this loops over ``influence_cross_cov`` and stacks.
     Pointer alignment does not matter (the kernel reads 8 bytes at a time)."""
     L = _L()
-    S = len(xs)
-    if S < 1 or len(us) != S or (ws is not None and len(ws) != S):
-        raise ValueError("need the same number (>= 1) of x, u (and w) tensors")
-    if ws is not None and any(w is None for w in ws) and not all(w is None for w in ws):
-        raise ValueError("weights for all states or for none")
-    if ws is not None and ws[0] is None:
-        ws = None
-    ops = [_operands(xs[s], us[s], None if ws is None else ws[s], "rowmajor") for s in range(S)]
+    ops, ws, S, C, pitches, tab = _influence_states(xs, us, ws, "rowmajor")
+    a, b, center_x, n_f, n_q = _influence_coefs(a, b, center_x, (S, C))
+    _check_cross_columns("influence_cross_cov_batched", C, " per state")
+    cu_dev = _center_u_device(center_u, S)
     as_given = all(not _layout(x.unsqueeze(1) if x.dim() == 1 else x, "rowmajor")[0] for x in xs)
-    C = ops[0][6]
-    if any(o[6] != C for o in ops):
-        raise ValueError("every x must have the same number of columns")
-    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
-        _check_f64_cuda(t, name)
-    if a.dim() != 4 or tuple(a.shape[:2]) != (S, C) or b.shape != a.shape:
-        raise ValueError(f"a and b must both have shape ({S}, {C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
-    if tuple(center_x.shape) != (S, C):
-        raise ValueError(f"center_x must have shape ({S}, {C}), got {tuple(center_x.shape)}")
-    if C > CROSS_COV_MAX_COLUMNS:
-        raise ValueError(f"influence_cross_cov_batched: C = {C} columns, the limit is {CROSS_COV_MAX_COLUMNS} (the result "
-                         "has (C n_f)^2 entries per state)")
-    cu_dev = center_u.contiguous() if isinstance(center_u, torch.Tensor) else to_device(np.asarray(center_u, dtype=np.float64))
-    _check_f64_cuda(cu_dev, "center_u")
-    if tuple(cu_dev.shape) != (S,):
-        raise ValueError(f"center_u must hold {S} values, got shape {tuple(cu_dev.shape)}")
-    _, _, n_f, n_q = a.shape
-    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
-
-    # (x2, ls, lc, u, w, N, C, squeeze) per state: a one-row state has no pitch of its own
-    pitches = {o[1] for o in ops if o[5] > 1} or {ops[0][1]}
     if not (as_given and len(pitches) == 1):
-        cu_host = center_u.cpu().numpy() if isinstance(center_u, torch.Tensor) else np.asarray(center_u, dtype=np.float64)
+        cu_host = _center_u_host(center_u)
         return torch.stack([influence_cross_cov(xs[s], us[s], a[s], b[s], float(cu_host[s]), center_x[s],
                                                 w=None if ws is None else ws[s]) for s in range(S)])
 
-    tab = (_lib.InfState * S)()
-    for s, (x2, _, _, u, w, N, _, _) in enumerate(ops):
-        tab[s].x, tab[s].u, tab[s].n = x2.data_ptr(), u.data_ptr(), N
-        tab[s].w = w.data_ptr() if w is not None else None
     cov = torch.empty((S, C, n_f, C, n_f), dtype=F64, device="cuda")
     wsb = workspace(L.txm_influence_cross_cov_batched_ws_bytes(S, max(o[5] for o in ops), C, n_f, n_q))
     check(
@@ -1023,20 +1004,9 @@ def influence_block_cross_cov(x: torch.Tensor, u: torch.Tensor, a: torch.Tensor,
     (many-state) form, overlapping batch means."""
     L = _L()
     x2, ls, _, u, w, N, C, _ = _operands(x, u, w, "rowmajor")
-    for t, name in ((a, "a"), (b, "b"), (center_x, "center_x")):
-        _check_f64_cuda(t, name)
-    if a.dim() != 3 or a.shape[0] != C or b.shape != a.shape:
-        raise ValueError(f"a and b must both have shape ({C}, n_f, n_q), got {tuple(a.shape)} and {tuple(b.shape)}")
-    if center_x.shape != (C,):
-        raise ValueError(f"center_x must have shape ({C},), got {tuple(center_x.shape)}")
-    if C > CROSS_COV_MAX_COLUMNS:
-        raise ValueError(f"influence_block_cross_cov: C = {C} columns, the limit is {CROSS_COV_MAX_COLUMNS} (the result has "
-                         "(C n_f)^2 entries a level)")
-    block, n_levels = int(block), int(n_levels)
-    if block < 1 or not 1 <= n_levels <= 32:
-        raise ValueError(f"need block >= 1 and 1 <= n_levels <= 32, got block={block}, n_levels={n_levels}")
-    _, n_f, n_q = a.shape
-    a, b, center_x = a.contiguous(), b.contiguous(), center_x.contiguous()
+    a, b, center_x, n_f, n_q = _influence_coefs(a, b, center_x, (C,))
+    _check_cross_columns("influence_block_cross_cov", C, " a level")
+    block, n_levels = _block_levels_args(block, n_levels)
     cov = torch.empty((n_levels, C, n_f, C, n_f), dtype=F64, device="cuda")
     mean = torch.empty((C, n_f), dtype=F64, device="cuda")
     ws = workspace(L.txm_influence_block_cross_cov_ws_bytes(N, C, n_f, n_q, block, n_levels))

@@ -21,8 +21,9 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib, engine
+from . import _delta, _lib, engine
 from . import symbolic as S
+from ._delta import check_block_type as _check_block_type
 from .data import AbstractData, _Params, xrwrap_alpha
 from .moments import IndexSampler
 from .xrlite import DataArray, concat, is_dataset, is_labelled
@@ -408,14 +409,6 @@ def taylor_series_norm(order, order_dim="order"):
     return out
 
 
-def _check_block_type(block) -> int:
-    """A block length of the blocked error bars as a Python int; TypeError for anything that is not an integer (its
-    range depends on the number of records: ``engine.block_levels`` raises the ValueError)."""
-    if isinstance(block, bool) or not isinstance(block, (int, np.integer)):
-        raise TypeError(f"block must be an integer number of records, got {type(block).__name__}")
-    return int(block)
-
-
 class ExtrapModel(_Params):
     """Taylor-series extrapolation about ``alpha0`` (reference models.py:433-576)."""
 
@@ -576,37 +569,21 @@ class ExtrapModel(_Params):
         return np.ascontiguousarray(a), np.ascontiguousarray(b), um, xm
 
     def _derivs_cov_device(self, order, minus_log, block=None):
-        if block is not None:
-            return self._blocked_cov_device(order, minus_log, block, curve=False)[:2]
-        key = ("dcov", order, minus_log)
-        if key not in self._cache:
-            x2, ut, wt, st, src = self._delta_operands()
-            a, b, um, xm = self._delta_coefs(st, order, minus_log)
-            cov, _ = engine.influence_cov(x2, ut, engine.to_device(a), engine.to_device(b), um, engine.to_device(xm), w=wt)
-            self._cache[key] = (cov, src)
-        return self._cache[key]
+        """``(cov [n_out, order + 1, order + 1] on the device, source)`` of ``derivs_cov`` (``_delta.extrap_table``): the
+        iid entry ``("dcov", ...)``, or with a ``block`` the blocked estimator's, cached under a key of its
+        own."""
+        return _delta.extrap_table(self, order, minus_log, False, block)[:2]
 
     def _blocked_cov_device(self, order, minus_log, block, curve):
-        """``(cov, source, block_lengths, n_blocks)`` of the blocked estimator from ONE
-        ``engine.influence_block_cov``: cov [n_out, order + 1, order + 1] at ``block`` alone, or with ``curve``
-        [level, n_out, order + 1, order + 1] for every level of ``engine.block_levels``.  Cached under keys of their own
-        (the block is part of them): the iid entry ``("dcov", ...)`` is neither read nor written."""
-        block = _check_block_type(block)
-        key = ("dcov_block", order, minus_log, block, bool(curve))
-        if key not in self._cache:
-            x2, ut, wt, st, src = self._delta_operands()         # (first: an unsupported model says so, whatever the block)
-            lengths, counts = engine.block_levels(x2.shape[0], block)
-            a, b, um, xm = self._delta_coefs(st, order, minus_log)
-            cov, _ = engine.influence_block_cov(x2, ut, engine.to_device(a), engine.to_device(b), um, engine.to_device(xm),
-                                                block, n_levels=len(lengths) if curve else 1, w=wt)
-            self._cache[key] = (cov if curve else cov[0], src, lengths, counts)
-        return self._cache[key]
+        """``(cov, source, block_lengths, n_blocks)`` of the blocked estimator: cov at ``block`` alone, or
+        with ``curve`` [level, ...] for every level of ``engine.block_levels``."""
+        return _delta.extrap_table(self, order, minus_log, False, _check_block_type(block), curve)
 
     @staticmethod
     def _derivs_cov_labelled(host, src, order, norm):
         """The host copy of a ``_derivs_cov_device`` table (n_out, order + 1, order + 1) as ``derivs_cov`` returns it."""
         if norm:
-            f = np.array([1.0 / math.factorial(i) for i in range(order + 1)])
+            f = _delta.taylor_norm(order)
             host = host * f[None, :, None] * f[None, None, :]
         out = DataArray(np.ascontiguousarray(np.moveaxis(host, 0, -1)).reshape(order + 1, order + 1, *src.out_shape),
                         ("order", "order_2", *src.out_dims))
@@ -653,11 +630,9 @@ class ExtrapModel(_Params):
             minus_log = self.minus_log
         if order is None:
             order = self.order
-        cov, src, lengths, counts = self._blocked_cov_device(order, bool(minus_log), block, curve=True)
-        host = cov.cpu().numpy()
-        levels = [self._derivs_cov_labelled(host[l], src, order, norm) for l in range(host.shape[0])]
-        out = concat(levels, dim=DataArray(lengths.copy(), "level"))
-        return self._ds(out), lengths.copy(), counts.copy()
+        out, lengths, counts = _delta.blocking_levels(self._blocked_cov_device(order, bool(minus_log), block, curve=True),
+                                                      lambda host, src: self._derivs_cov_labelled(host, src, order, norm))
+        return self._ds(out), lengths, counts
 
     def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None, block=None):
         """``(prediction, std)``: ``predict(alpha)`` and its delta-method standard deviation ``sqrt(t' V t)``,
@@ -671,57 +646,23 @@ class ExtrapModel(_Params):
         cov, src = self._derivs_cov_device(order, bool(minus_log), block)
         pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name)
         dalpha = xrwrap_alpha(alpha, name=alpha_name or self.alpha_name) - self.alpha0
-        d = np.asarray(dalpha.values, dtype=np.float64).reshape(-1)
-        t = np.stack([d**k / math.factorial(k) for k in range(order + 1)], axis=1)            # (n_alpha, order + 1)
+        t = _delta.taylor_vectors(dalpha, order)                                              # (n_alpha, order + 1)
         var = np.einsum("ai,cij,aj->ac", t, cov.cpu().numpy(), t)
-        std = DataArray(np.sqrt(np.maximum(var, 0.0)).reshape((*dalpha.shape, *src.out_shape)), (*dalpha.dims, *src.out_dims))
-        std._inherit(dalpha._coords)
-        std._inherit(src.coords)
-        return pred, self._ds(std)
+        return pred, self._ds(_delta.label_std(var, dalpha, src))
 
     # ---- the same across the observable columns ---------------------------------------------------------
     def _derivs_cross_cov_device(self, order, minus_log, block=None):
         """``(cov [n_out, order + 1, n_out, order + 1] on the device, source)`` from ONE ``engine.influence_cross_cov``,
         cached under a key of its own: the per-column entry ``("dcov", ...)`` is neither read nor written.  With a
         ``block`` it is the blocked estimator's (``_blocked_cross_cov_device``)."""
-        if block is not None:
-            return self._blocked_cross_cov_device(order, minus_log, block, curve=False)[:2]
-        key = ("dxcov", order, minus_log)
-        if key not in self._cache:
-            x2, ut, wt, st, src = self._delta_operands()         # (first: an unsupported model says so, whatever its width)
-            if x2.shape[1] > engine.CROSS_COV_MAX_COLUMNS:
-                raise ValueError(f"derivs_cross_cov / predict_cov: {x2.shape[1]} observable columns, the limit is "
-                                 f"{engine.CROSS_COV_MAX_COLUMNS} (the result has (columns * (order + 1))^2 entries)")
-            a, b, um, xm = self._delta_coefs(st, order, minus_log)
-            cov = engine.influence_cross_cov(x2, ut, engine.to_device(a), engine.to_device(b), um, engine.to_device(xm), w=wt)
-            self._cache[key] = (cov, src)
-        return self._cache[key]
+        return _delta.extrap_table(self, order, minus_log, True, block)[:2]
 
     def _blocked_cross_cov_device(self, order, minus_log, block, curve):
-        """``(cov, source, block_lengths, n_blocks)`` of the blocked cross estimator from ONE
-        ``engine.influence_block_cross_cov``: cov [n_out, order + 1, n_out, order + 1] at ``block`` alone, or with
-        ``curve`` [level, n_out, order + 1, n_out, order + 1] for every level of ``engine.block_levels``.  Cached under
-        keys that carry the block: the iid entry ``("dxcov", ...)`` is neither read nor written."""
-        block = _check_block_type(block)
-        key = ("dxcov_block", order, minus_log, block, bool(curve))
-        if key not in self._cache:
-            x2, ut, wt, st, src = self._delta_operands()         # (first: an unsupported model says so, whatever the block)
-            if x2.shape[1] > engine.CROSS_COV_MAX_COLUMNS:
-                raise ValueError(f"derivs_cross_cov / predict_cov: {x2.shape[1]} observable columns, the limit is "
-                                 f"{engine.CROSS_COV_MAX_COLUMNS} (the result has (columns * (order + 1))^2 entries)")
-            lengths, counts = engine.block_levels(x2.shape[0], block)
-            a, b, um, xm = self._delta_coefs(st, order, minus_log)
-            cov, _ = engine.influence_block_cross_cov(x2, ut, engine.to_device(a), engine.to_device(b), um,
-                                                      engine.to_device(xm), block, n_levels=len(lengths) if curve else 1, w=wt)
-            self._cache[key] = (cov if curve else cov[0], src, lengths, counts)
-        return self._cache[key]
+        """``(cov, source, block_lengths, n_blocks)`` of the blocked cross estimator: cov at ``block`` alone,
+        or with ``curve`` [level, ...] for every level of ``engine.block_levels``."""
+        return _delta.extrap_table(self, order, minus_log, True, _check_block_type(block), curve)
 
-    @staticmethod
-    def _cross_labels(out, src):
-        """The coordinates of the value dims on ``out``, and their copies under the ``_2`` names."""
-        out._inherit(src.coords)
-        out._inherit({k + "_2": (tuple(d + "_2" for d in cd), cv) for k, (cd, cv) in src.coords.items()})
-        return out
+    _cross_labels = staticmethod(_delta.cross_labels)
 
     @classmethod
     def _derivs_cross_cov_labelled(cls, host, src, order, norm):
@@ -729,7 +670,7 @@ class ExtrapModel(_Params):
         ``derivs_cross_cov`` returns it."""
         host = host.transpose(1, 3, 0, 2)                                                    # (order, order_2, c, c')
         if norm:
-            f = np.array([1.0 / math.factorial(i) for i in range(order + 1)])
+            f = _delta.taylor_norm(order)
             host = host * f[:, None, None, None] * f[None, :, None, None]
         out = DataArray(np.ascontiguousarray(host).reshape(order + 1, order + 1, *src.out_shape, *src.out_shape),
                         ("order", "order_2", *src.out_dims, *[d + "_2" for d in src.out_dims]))
@@ -782,11 +723,8 @@ class ExtrapModel(_Params):
             minus_log = self.minus_log
         if order is None:
             order = self.order
-        cov, src, lengths, counts = self._blocked_cross_cov_device(order, bool(minus_log), block, curve=True)
-        host = cov.cpu().numpy()
-        levels = [self._derivs_cross_cov_labelled(host[l], src, order, norm) for l in range(host.shape[0])]
-        out = concat(levels, dim=DataArray(lengths.copy(), "level"))
-        return out, lengths.copy(), counts.copy()
+        return _delta.blocking_levels(self._blocked_cross_cov_device(order, bool(minus_log), block, curve=True),
+                                      lambda host, src: self._derivs_cross_cov_labelled(host, src, order, norm))
 
     def predict_cov(self, alpha, order=None, minus_log=None, alpha_name=None, block=None):
         """``(prediction, cov)``: ``predict(alpha)`` and the delta-method covariance of the predicted columns,
@@ -802,13 +740,9 @@ class ExtrapModel(_Params):
         cov, src = self._derivs_cross_cov_device(order, bool(minus_log), block)
         pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name)
         dalpha = xrwrap_alpha(alpha, name=alpha_name or self.alpha_name) - self.alpha0
-        d = np.asarray(dalpha.values, dtype=np.float64).reshape(-1)
-        t = np.stack([d**k / math.factorial(k) for k in range(order + 1)], axis=1)            # (n_alpha, order + 1)
+        t = _delta.taylor_vectors(dalpha, order)                                              # (n_alpha, order + 1)
         pc = np.einsum("ai,cidj,aj->acd", t, cov.cpu().numpy(), t)
-        out = DataArray(pc.reshape((*dalpha.shape, *src.out_shape, *src.out_shape)),
-                        (*dalpha.dims, *src.out_dims, *[d + "_2" for d in src.out_dims]))
-        out._inherit(dalpha._coords)
-        return pred, self._cross_labels(out, src)
+        return pred, _delta.label_cov(pc, dalpha, src)
 
     def resample(self, sampler, **kws):
         """New model on resampled data."""
@@ -910,11 +844,8 @@ class StateCollection(_Params):
         """Fill every state's ``("dcov", order, minus_log)`` cache -- what ``ExtrapModel._derivs_cov_device`` computes,
         bit for bit -- and return ``(cov [S, n_out, order + 1, order + 1] on the device, sources, order)``.
         Eligible states (``_delta_batch_eligible``): ONE copy of the stacked central states to the host, the
-        coefficient algebra there, ONE ``engine.influence_cov_batched``.  Otherwise a loop over the states.
-
-        The host algebra runs state by state although symbolic.influence_coefs broadcasts: the single path hands it
-        ``<u>`` as a Python float, and ``float ** int`` need not round like ``ndarray ** int`` (it matters in the raw
-        form, which expands about zero), so only the per-state call is certain to give the single call's coefficients.
+        per-state coefficient algebra there, ONE ``engine.influence_cov_batched`` (``_delta.states_tables``, which says
+        why the algebra runs state by state).  Otherwise a loop over the states.
 
         With ``block`` (``_blocks_per_state``) the states are looped on the single blocked entry point, each with its own
         block length; the iid caches are neither read nor written."""
@@ -926,18 +857,11 @@ class StateCollection(_Params):
             key = ("dcov", o, ml)
             todo = [st for st in sts if key not in st._cache]
             if todo and o <= todo[0].data.order:
-                ops = [st._delta_operands(device_state=True) for st in todo]       # raises what a state raises
-                host = torch.stack([op[3] for op in ops]).cpu().numpy()            # [S, C, 2, K]: one copy
-                co = [st._delta_coefs(host[s], o, ml) for s, st in enumerate(todo)]
-                cov, _ = engine.influence_cov_batched(
-                    [op[0] for op in ops], [op[1] for op in ops],
-                    engine.to_device(np.stack([c[0] for c in co])), engine.to_device(np.stack([c[1] for c in co])),
-                    np.array([c[2] for c in co]), engine.to_device(np.stack([c[3] for c in co])),
-                    ws=None if ops[0][2] is None else [op[2] for op in ops])
+                cov, srcs = _delta.states_tables(todo, o, ml, cross=False)
                 for s, st in enumerate(todo):
-                    st._cache[key] = (cov[s], ops[s][4])
+                    st._cache[key] = (cov[s], srcs[s])
                 if len(todo) == len(sts):
-                    return cov, [op[4] for op in ops], o
+                    return cov, srcs, o
             parts = [st._derivs_cov_device(o, ml) for st in sts]
             return torch.stack([p_[0] for p_ in parts]), [p_[1] for p_ in parts], o
         parts, orders = [], []
@@ -1007,15 +931,8 @@ class StateCollection(_Params):
             ml = bool(sts[0].minus_log if minus_log is None else minus_log)
             key = ("dxcov_states", o, ml)
             if key not in self._cache:
-                ops = [st._delta_operands(device_state=True) for st in sts]         # raises what a state raises
-                host = torch.stack([op[3] for op in ops]).cpu().numpy()             # [S, C, 2, K]: one copy
-                co = [st._delta_coefs(host[s], o, ml) for s, st in enumerate(sts)]
-                cov = engine.influence_cross_cov_batched(
-                    [op[0] for op in ops], [op[1] for op in ops],
-                    engine.to_device(np.stack([c[0] for c in co])), engine.to_device(np.stack([c[1] for c in co])),
-                    np.array([c[2] for c in co]), engine.to_device(np.stack([c[3] for c in co])),
-                    ws=None if ops[0][2] is None else [op[2] for op in ops])
-                self._cache[key] = (cov.cpu().numpy(), [op[4] for op in ops])
+                cov, srcs = _delta.states_tables(sts, o, ml, cross=True)
+                self._cache[key] = (cov.cpu().numpy(), srcs)
             host, srcs = self._cache[key]
             return list(host), srcs, [o] * len(sts)
         covs, srcs, orders = [], [], []
@@ -1464,24 +1381,8 @@ class ExtrapWeightedModel(StateCollection, PiecewiseMixin):
         covs, srcs = self._state_covs(order, minus_log, block)         # (first: an unsupported state says so)
         pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name, method=method, bounded=bounded)
         al = xrwrap_alpha(alpha, name=alpha_name)
-        a0 = np.asarray(self.alpha0, dtype=np.float64)
-        fact = np.array([math.factorial(k) for k in range(order + 1)], dtype=np.float64)
-        var = []
-        for a in np.asarray(al.values, dtype=np.float64).reshape(-1):
-            idx = [0, 1] if len(self) == 2 else self._indices_alpha(float(a), method)
-            dm = np.abs(a - a0[idx]) ** 20                                        # xr_weights_minkowski, m = 20
-            w = 1.0 - dm / dm.sum()
-            wn = w / w.sum()
-            v = 0.0
-            for wi, i in zip(wn, idx):
-                t = (a - a0[i]) ** np.arange(order + 1) / fact
-                v = v + wi * wi * np.einsum("i,cij,j->c", t, covs[i], t)
-            var.append(v)
-        src = srcs[0]
-        std = DataArray(np.sqrt(np.maximum(np.array(var), 0.0)).reshape((*al.shape, *src.out_shape)), (*al.dims, *src.out_dims))
-        std._inherit(al._coords)
-        std._inherit(src.coords)
-        return pred, self[0]._ds(std)
+        var = _delta.minkowski_contract(self, al, order, method, covs, "i,cij,j->c")
+        return pred, self[0]._ds(_delta.label_std(var, al, srcs[0]))
 
     def predict_cov(self, alpha, order=None, minus_log=None, alpha_name=None, method=None, bounded=False, block=None):
         """``(predict(alpha, ...), cov)``: the blended prediction, bit for bit ``predict``'s, and the delta-method
@@ -1501,24 +1402,7 @@ class ExtrapWeightedModel(StateCollection, PiecewiseMixin):
         covs, srcs, _ = self._state_cross_covs(order, minus_log, block)      # (first: an unsupported state says so)
         pred = self.predict(alpha, order=order, minus_log=minus_log, alpha_name=alpha_name, method=method, bounded=bounded)
         al = xrwrap_alpha(alpha, name=alpha_name)
-        a0 = np.asarray(self.alpha0, dtype=np.float64)
-        fact = np.array([math.factorial(k) for k in range(order + 1)], dtype=np.float64)
-        pc = []
-        for a in np.asarray(al.values, dtype=np.float64).reshape(-1):
-            idx = [0, 1] if len(self) == 2 else self._indices_alpha(float(a), method)
-            dm = np.abs(a - a0[idx]) ** 20                                        # xr_weights_minkowski, m = 20
-            w = 1.0 - dm / dm.sum()
-            wn = w / w.sum()
-            v = 0.0
-            for wi, i in zip(wn, idx):
-                t = (a - a0[i]) ** np.arange(order + 1) / fact
-                v = v + wi * wi * np.einsum("i,cidj,j->cd", t, covs[i], t)
-            pc.append(v)
-        src = srcs[0]
-        out = DataArray(np.array(pc).reshape((*al.shape, *src.out_shape, *src.out_shape)),
-                        (*al.dims, *src.out_dims, *[d + "_2" for d in src.out_dims]))
-        out._inherit(al._coords)
-        return pred, ExtrapModel._cross_labels(out, src)
+        return pred, _delta.label_cov(_delta.minkowski_contract(self, al, order, method, covs, "i,cidj,j->cd"), al, srcs[0])
 
 
 class InterpModel(StateCollection):
@@ -1566,17 +1450,9 @@ class InterpModel(StateCollection):
     def _predict_std(self, alpha, order, minus_log, alpha_name, block=None):
         """Delta-method standard deviation of ``predict(alpha)`` (see ``predict_with_error``)."""
         covs, srcs = self._state_covs(order, minus_log, block)              # [S][n_out, order + 1, order + 1]
-        inv = self._hermite_inverse(order)                              # [porder, state * (order + 1)]
         al = xrwrap_alpha(alpha, name=alpha_name)
-        av = np.asarray(al.values, dtype=np.float64).reshape(-1)
-        g = (av[:, None] ** np.arange(inv.shape[0])[None, :]) @ inv     # (n_alpha, S (order + 1))
-        g = g.reshape(len(av), len(self), order + 1)
-        var = sum(np.einsum("ai,cij,aj->ac", g[:, s], covs[s], g[:, s]) for s in range(len(self)))
-        src = srcs[0]
-        std = DataArray(np.sqrt(np.maximum(var, 0.0)).reshape((*al.shape, *src.out_shape)), (*al.dims, *src.out_dims))
-        std._inherit(al._coords)
-        std._inherit(src.coords)
-        return self[0]._ds(std)
+        var = _delta.hermite_contract(self._hermite_inverse(order), al, order, covs, "ai,cij,aj->ac")
+        return self[0]._ds(_delta.label_std(var, al, srcs[0]))
 
     def predict_with_error(self, alpha, order=None, minus_log=None, alpha_name=None, block=None):
         """``(predict(alpha), std)``: the interpolation, bit for bit ``predict``'s, and its delta-method standard
@@ -1602,16 +1478,8 @@ class InterpModel(StateCollection):
         in order.  Labelled ``(*alpha dims, *val_dims, *val_dims_2)``."""
         if len(covs) != len(self):
             raise ValueError(f"{len(covs)} covariances for {len(self)} states")
-        inv = self._hermite_inverse(order)                              # [porder, state * (order + 1)]
         al = xrwrap_alpha(alpha, name=alpha_name)
-        av = np.asarray(al.values, dtype=np.float64).reshape(-1)
-        g = (av[:, None] ** np.arange(inv.shape[0])[None, :]) @ inv     # (n_alpha, S (order + 1))
-        g = g.reshape(len(av), len(self), order + 1)
-        pc = sum(np.einsum("ai,cidj,aj->acd", g[:, s], covs[s], g[:, s]) for s in range(len(self)))
-        out = DataArray(pc.reshape((*al.shape, *src.out_shape, *src.out_shape)),
-                        (*al.dims, *src.out_dims, *[d + "_2" for d in src.out_dims]))
-        out._inherit(al._coords)
-        return ExtrapModel._cross_labels(out, src)
+        return _delta.label_cov(_delta.hermite_contract(self._hermite_inverse(order), al, order, covs, "ai,cidj,aj->acd"), al, src)
 
     def predict_cov(self, alpha, order=None, minus_log=None, alpha_name=None, block=None):
         """``(predict(alpha), cov)``: the interpolation, bit for bit ``predict``'s, and the delta-method covariance of the
@@ -1674,13 +1542,7 @@ class InterpModelPiecewise(StateCollection, PiecewiseMixin):
             return pair._predict_std(a, pair.order if order is None else order, minus_log, alpha_name,
                                      None if blocks is None else [blocks[int(i)] for i in idx])
 
-        if len(self) == 2:
-            return pred, std_of((0, 1), alpha)
-        seq = [float(a) for a in _alpha_seq(alpha)]
-        outs = [std_of(self._indices_alpha(a, method), a) for a in seq]
-        if len(outs) == 1:
-            return pred, outs[0]
-        return pred, concat(outs, dim=DataArray(np.asarray(seq), alpha_name))
+        return pred, _delta.per_alpha_pairs(self, alpha, alpha_name, method, std_of)
 
     def predict_cov(self, alpha, order=None, minus_log=None, alpha_name=None, method=None, bounded=False, block=None):
         """``(predict(alpha, ...), cov)``: for every alpha the two-state ``InterpModel`` that ``predict`` chooses
@@ -1701,13 +1563,7 @@ class InterpModelPiecewise(StateCollection, PiecewiseMixin):
             pair = self.single_interpmodel(*idx)
             return pair._predict_cov_from(a, order, alpha_name, [covs[int(i)] for i in idx], srcs[0])
 
-        if len(self) == 2:
-            return pred, cov_of((0, 1), alpha)
-        seq = [float(a) for a in _alpha_seq(alpha)]
-        outs = [cov_of(self._indices_alpha(a, method), a) for a in seq]
-        if len(outs) == 1:
-            return pred, outs[0]
-        return pred, concat(outs, dim=DataArray(np.asarray(seq), alpha_name))
+        return pred, _delta.per_alpha_pairs(self, alpha, alpha_name, method, cov_of)
 
 
 class MBAROverlap(NamedTuple):
