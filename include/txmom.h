@@ -785,6 +785,40 @@ int txm_influence_cross_cov_batched(const txm_inf_state *states_host, int64_t S,
                                     const double *center_u, const double *center_x, const double *a, const double *b,
                                     double *cov, void *ws, size_t ws_bytes, txm_stream stream);
 
+/* ---- (f-15) PerturbModel error bars: delta-method variance, Kish n_eff and the free-energy difference of (f-4) ---- */
+/* The operands of (f-4) without bootstrap counts, the reweighted means  mean [n_alpha][C]  (device; (f-4)'s output -- the
+ * sums are centred on the GIVEN mean, so nothing cancels), a block length `block` = B >= 1 and n_levels in [1, 32].  With
+ *     w_na = e^{-dalpha[a] (u_n - uref[a])}   (uref[a] from (f-4)'s own extremes pre-pass: the same weights),
+ *     W_a = sum_n w_na,  p_na = w_na / W_a,
+ * level-l block j covers the rows [j B 2^l, min(N, (j + 1) B 2^l)) -- the last block may be short and is kept -- and
+ *     var[l][a][c]  = sum_j z_j^2,  z_j = sum_{n in block j} p_na (x[n][c] - mean[a][c])
+ *     neff[a]       = W_a^2 / sum_n w_na^2                                 (Kish effective sample number)
+ *     lnq[a]        = ln(W_a / N) - dalpha[a] uref[a] = ln < e^{-dalpha[a] u} >   (minus the free-energy difference)
+ *     var_lnq[l][a] = sum_j (sum_{n in j} p_na - n_j / N)^2,  n_j the rows of block j
+ * -- the infinitesimal-jackknife (first-order delta-method) variances of the ratio estimator of (f-4) and of lnq, with
+ * time blocks as clusters when B > 1 (batch means: for a correlated series, B beyond its correlation time).  There is NO
+ * nb / (nb - 1) factor: block = 1, level 0 is the iid  sum_n p_n^2 (x_n - m)^2  and  var_lnq = 1 / neff - 1 / N.
+ * var [n_levels][n_alpha][C], neff [n_alpha], lnq [n_alpha], var_lnq [n_levels][n_alpha] are device arrays; dalpha_host
+ * is a host array, n_alpha <= 8.  Levels with a single block are allowed and computed (block > N too: one block).
+ * block == 1 && n_levels == 1 (iid): ONE pass in (f-4)'s layout, the n_alpha exponentials of a row shared between its
+ * lanes, sum w, sum w^2 and sum (w (x - m))^2 in registers, per-workgroup partials added in a fixed order by a finalize;
+ * nothing of size N is stored.  Otherwise (blocked): every level-0 block is summed by one workgroup in a fixed order, so
+ * its bits do not depend on the launch width, into the workspace as [nb][n_alpha][C + 1] (the extra slot: sum_{n in b} w)
+ * plus [nb][n_alpha][2] (sum w, sum w^2); a second kernel (a workgroup per (column, alpha)) adds W in a fixed order and
+ * merges the pairs of the level below in place, level by level.  No floating-point atomics; two calls give the same bits.
+ * A row whose weight underflows contributes zero.  First-order rounding bound with kappa_n = 1 + |dalpha (u_n - uref)|
+ * (the exponent's rounding is the weight's relative error):  var: eps sum_j (sum_{n in j} p_n kappa_n |x_n - m|)^2,
+ * var_lnq: eps sum_j (sum_{n in j} p_n kappa_n + n_j / N)^2, neff and lnq: eps kappa-bar (p-weighted mean) relative / absolute.
+ * Workspace: txm_perturb_cov_ws_bytes, host logic, 0 for bad arguments: the pre-pass head, then iid  8 CUs workgroups x
+ * (8 n_alpha (padded columns + 2)) bytes, blocked  8 nb n_alpha (C + 1) + 16 nb n_alpha  bytes with nb = ceil(N / block),
+ * and 256 bytes.  Null pointers, N < 1, C outside [1, 65535], ldx_s < C, n_alpha outside [1, 8], block < 1 and n_levels
+ * outside [1, 32] return TXM_ERR_INVALID, a short workspace TXM_ERR_WORKSPACE, all before anything is enqueued. */
+size_t txm_perturb_cov_ws_bytes(int64_t N, int64_t C, int32_t n_alpha, int64_t block, int32_t n_levels);
+int txm_perturb_cov(const double *x, int64_t ldx_s, const double *u, int64_t N, int64_t C,
+                    const double *dalpha_host, int32_t n_alpha, const double *mean, int64_t block, int32_t n_levels,
+                    double *var, double *neff, double *lnq, double *var_lnq, void *ws, size_t ws_bytes,
+                    txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

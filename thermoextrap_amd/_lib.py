@@ -137,6 +137,9 @@ SIGNATURES = {
     "txm_perturb_ws_bytes": (c_size, [c_i64, c_i64, ct.c_int32, c_i64]),
     "txm_perturb": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, ct.POINTER(ct.c_double), ct.c_int32, c_void_p,
                             c_i64, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_perturb_cov_ws_bytes": (c_size, [c_i64, c_i64, ct.c_int32, c_i64, ct.c_int32]),
+    "txm_perturb_cov": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, ct.POINTER(ct.c_double), ct.c_int32, c_void_p,
+                                c_i64, ct.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "txm_mbar_ws_bytes": (c_size, [ct.c_int32, c_i64, ct.c_int32]),
     "txm_mbar_eval": (c_int, [ct.POINTER(MbarState), ct.c_int32, ct.POINTER(ct.c_double), ct.POINTER(ct.c_double),
                               ct.c_double, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),

@@ -1079,6 +1079,54 @@ def perturb(x: torch.Tensor, u: torch.Tensor, dalphas, freq: torch.Tensor | None
     return res[..., 0] if squeeze else res
 
 
+class PerturbCov(NamedTuple):
+    """What ``perturb_cov`` returns, all on the device: ``mean`` (n_alpha, C) is ``perturb``'s output, ``var``
+    (n_levels, n_alpha, C) its delta-method variance per level, ``neff`` (n_alpha,) Kish's effective sample number,
+    ``lnq`` (n_alpha,) ``ln <e^{-dalpha u}>`` and ``var_lnq`` (n_levels, n_alpha) its variance.  The C axis is dropped for
+    1-D x."""
+
+    mean: torch.Tensor
+    var: torch.Tensor
+    neff: torch.Tensor
+    lnq: torch.Tensor
+    var_lnq: torch.Tensor
+
+
+def perturb_cov(x: torch.Tensor, u: torch.Tensor, dalphas, block: int = 1, n_levels: int = 1) -> PerturbCov:
+    """Delta-method (infinitesimal-jackknife) variance of ``perturb``'s averages (txm_perturb_cov): with
+    ``p_na = w_na / sum_n w_na`` the normalised weights ``e^{-dalpha_a u_n}``, ``var[l, a, c] = sum_j z_j^2`` over the
+    sums ``z_j = sum_{n in block j} p_na (x_nc - mean_ac)`` of the contiguous blocks of ``block * 2**l`` rows (a last
+    short block is kept; no nb / (nb - 1) factor; ``block=1, n_levels=1`` is the iid ``sum_n p_n^2 (x_n - m)^2``),
+    ``neff = (sum w)^2 / sum w^2``, ``lnq = ln <e^{-dalpha u}>`` and ``var_lnq[l, a] = sum_j (sum_{n in j} p_na -
+    n_j / N)^2``.  ``perturb`` gives the means, then one more pass over the samples per 8 dalphas.  x: (N, C) row-major
+    or (N,)."""
+    L = _L()
+    block, n_levels = _block_levels_args(block, n_levels)
+    x2, ls, _, u, _, N, C, squeeze = _operands(x, u, None, "rowmajor")
+    da = np.atleast_1d(np.asarray(dalphas, dtype=np.float64))
+    mean = perturb(x2, u, da)                                                              # (n_alpha, C)
+    parts = []
+    for i0, chunk in _eight_per_pass(da):
+        na = len(chunk)
+        var = torch.empty((n_levels, na, C), dtype=F64, device="cuda")
+        neff = torch.empty(na, dtype=F64, device="cuda")
+        lnq = torch.empty(na, dtype=F64, device="cuda")
+        var_lnq = torch.empty((n_levels, na), dtype=F64, device="cuda")
+        ws = workspace(L.txm_perturb_cov_ws_bytes(N, C, na, block, n_levels))
+        check(
+            L.txm_perturb_cov(_ptr(x2), ls, _ptr(u), N, C, chunk.ctypes.data_as(ct.POINTER(ct.c_double)), na,
+                              _ptr(mean[i0:i0 + na]), block, n_levels, _ptr(var), _ptr(neff), _ptr(lnq), _ptr(var_lnq),
+                              _ptr(ws), ws.numel(), _stream()),
+            "txm_perturb_cov",
+        )
+        parts.append((var, neff, lnq, var_lnq))
+    var = torch.cat([p[0] for p in parts], dim=1)
+    if squeeze:
+        mean, var = mean[..., 0], var[..., 0]
+    return PerturbCov(mean, var, torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]),
+                      torch.cat([p[3] for p in parts], dim=1))
+
+
 # ---------------------------------------------------------------------------
 # MBAR (MBARModel; reference models.py:1049-1111, which wraps pymbar)
 # ---------------------------------------------------------------------------

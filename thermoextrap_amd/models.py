@@ -1277,6 +1277,104 @@ class PerturbModel(_Params):
         return type(self)(alpha0=self.alpha0, data=self.data.resample(sampler=sampler, **kws),
                           alpha_name=self.alpha_name)
 
+    # ---- delta-method error bars, effective samples, free energies --------------------------------------
+    def _refuse_resampled(self, what):
+        if getattr(self.data, "_resampled", None) is not None:
+            raise NotImplementedError(f"{what}: this PerturbModel holds resampled data; take the error bars of the "
+                                      "PerturbModel it was resampled from")
+
+    def _perturb_cov(self, what, alpha, alpha_name, block, n_levels=1):
+        """``(engine.PerturbCov, alpha, alpha_name, other dims, their shape)`` of one ``engine.perturb_cov`` on the
+        operands ``predict`` passes to ``engine.perturb`` -- or NotImplementedError for a resampled model."""
+        from .moments import _dev_and_dims
+
+        self._refuse_resampled(what)
+        data = self.data
+        if alpha_name is None:
+            alpha_name = self.alpha_name
+        alpha = xrwrap_alpha(alpha, name=alpha_name)
+        dalpha = np.atleast_1d(np.asarray(alpha.values, dtype=float) - self.alpha0)
+        rec = data.rec_dim
+        ut, udims = _dev_and_dims(data._uv if hasattr(data, "_uv") else data.uv)
+        xt, xdims = _dev_and_dims(data._xv if hasattr(data, "_xv") else data.xv)
+        if udims != (rec,):
+            raise NotImplementedError("uv must be 1-D along the record dim")
+        others = [d for d in xdims if d != rec]
+        x2 = xt.movedim(xdims.index(rec), 0)
+        cshape = list(x2.shape[1:])
+        x2 = x2.reshape(x2.shape[0], -1) if x2.dim() > 1 else x2
+        block = 1 if block is None else _check_block_type(block)
+        res = engine.perturb_cov(x2, ut, dalpha, block=block, n_levels=n_levels)
+        return res, alpha, alpha_name, others, cshape
+
+    @staticmethod
+    def _alpha_labelled(vals, alpha, alpha_name, dims=()):
+        """vals (n_alpha, ...) with ``predict``'s labelling: the alpha axis dropped for a scalar alpha."""
+        if alpha.ndim == 0:
+            return DataArray(vals[0], list(dims), coords={alpha_name: alpha.values})
+        return DataArray(vals, [alpha_name, *dims], coords={alpha_name: alpha.values})
+
+    def predict_with_error(self, alpha, alpha_name=None, block=None):
+        """``(value, std)``: ``predict(alpha)`` bit for bit and its delta-method (infinitesimal-jackknife) standard
+        deviation, both with ``predict``'s dims: ``std^2 = sum_n p_n^2 (x_n - <x>(alpha))^2`` with ``p_n`` the normalised
+        weights ``e^{-(alpha - alpha0) u_n}`` -- one more pass over the samples per 8 alphas (txm_perturb_cov), no
+        replicates, no sampling noise.
+
+        Assumptions: first order (what the multinomial bootstrap ``resample`` estimates, without its noise); INDEPENDENT
+        samples unless ``block`` is given; no 1 / n_eff correction.  The bar is unreliable once ``effective_samples`` is
+        small: exponential reweighting degrades silently when the target leaves the sampled energies, and that method
+        is how to see it.  ``block=B`` (an int; ``None`` means 1) is for a CORRELATED series kept whole: the records are
+        cut into contiguous blocks of B (a last short one is kept) and ``std^2 = sum_b (sum_{n in b} p_n (x_n - <x>))^2``
+        -- batch means, B beyond the correlation time (``timeseries.block_length`` proposes one, ``blocking_curve`` shows
+        whether the variance has levelled off).  A resampled model raises NotImplementedError."""
+        res, alpha, alpha_name, others, cshape = self._perturb_cov("predict_with_error (delta-method error bars)", alpha,
+                                                                   alpha_name, block)
+        na = len(res.neff)
+        val = res.mean.cpu().numpy().reshape(na, *cshape)
+        std = np.sqrt(np.maximum(res.var[0].cpu().numpy(), 0.0)).reshape(na, *cshape)
+        return self._alpha_labelled(val, alpha, alpha_name, others), self._alpha_labelled(std, alpha, alpha_name, others)
+
+    def effective_samples(self, alpha, alpha_name=None):
+        """Kish's effective sample number at every alpha, ``(sum_n w_n)^2 / sum_n w_n^2`` with
+        ``w_n = e^{-(alpha - alpha0) u_n}``: N at ``alpha0``, towards 1 when a few samples carry the average (then
+        neither the prediction nor its error bar means much)."""
+        res, alpha, alpha_name, _, _ = self._perturb_cov("effective_samples", alpha, alpha_name, None)
+        return self._alpha_labelled(res.neff.cpu().numpy(), alpha, alpha_name)
+
+    def free_energy(self, alpha, alpha_name=None, block=None):
+        """``(f, df)`` relative to ``alpha0`` (``MBARModel.free_energy(alpha)``'s convention; the Zwanzig / EXP estimator,
+        MBAR with one state): ``f = -ln <e^{-(alpha - alpha0) u}>`` and its delta-method standard deviation
+        ``df^2 = sum_n (p_n - 1 / N)^2 = 1 / n_eff - 1 / N``, or with ``block=B`` the batch-means form
+        ``sum_b (sum_{n in b} p_n - n_b / N)^2`` for a correlated series.  The assumptions of ``predict_with_error``
+        apply."""
+        res, alpha, alpha_name, _, _ = self._perturb_cov("free_energy", alpha, alpha_name, block)
+        f = -res.lnq.cpu().numpy()
+        df = np.sqrt(np.maximum(res.var_lnq[0].cpu().numpy(), 0.0))
+        return self._alpha_labelled(f, alpha, alpha_name), self._alpha_labelled(df, alpha, alpha_name)
+
+    def blocking_curve(self, alpha, block, alpha_name=None):
+        """The blocking curve of Flyvbjerg & Petersen (1989) for ``predict_with_error``: ``(var, block_lengths, n_blocks)``
+        with ``var[l] = predict_with_error(alpha, block=block * 2**l)[1] ** 2`` (dims ``(level, alpha, *val_dims)``),
+        ``block_lengths[l] = block * 2**l`` and ``n_blocks[l] = ceil(N / block_lengths[l])``, for every level that still
+        has at least two blocks.  ONE kernel call per 8 alphas: block sums are additive, so each level merges the pairs
+        of the level below.  Where var stops growing with the block length the blocks are longer than the correlation
+        time; the last levels are noisy (relative standard deviation about ``sqrt(2 / (n_blocks - 1))``) and biased by
+        ``-1 / n_blocks``."""
+        from .moments import _dev_and_dims
+
+        block = _check_block_type(block)
+        self._refuse_resampled("blocking_curve")
+        data = self.data
+        ut, _ = _dev_and_dims(data._uv if hasattr(data, "_uv") else data.uv)
+        lengths, counts = engine.block_levels(int(ut.shape[0]), block)
+        res, alpha, alpha_name, others, cshape = self._perturb_cov("blocking_curve", alpha, alpha_name, block,
+                                                                   n_levels=len(lengths))
+        host = res.var.cpu().numpy()
+        na = host.shape[1]
+        out = concat([self._alpha_labelled(host[l].reshape(na, *cshape), alpha, alpha_name, others)
+                      for l in range(host.shape[0])], dim=DataArray(lengths.copy(), "level"))
+        return out, lengths.copy(), counts.copy()
+
 
 # ---------------------------------------------------------------------------
 # Multi-state models (reference models.py:710-1007).  Host algebra on top of
