@@ -819,6 +819,52 @@ int txm_perturb_cov(const double *x, int64_t ldx_s, const double *u, int64_t N, 
                     double *var, double *neff, double *lnq, double *var_lnq, void *ws, size_t ws_bytes,
                     txm_stream stream);
 
+/* ---- (f-16) timeseries: the lag sums of (f-7) for S states in one set of launches, the centred rows kept ---------- */
+/* S states of C columns each, x row-major with ONE pitch ldx_s >= C, a record count PER STATE.  Two calls:
+ *   txm_lag_rows_batched  centres and transposes all states in ONE launch (the state rides a grid axis; workgroups past a
+ *       state's n leave at once) into the caller-held buffer `rows` of exactly txm_lag_rows_batched_bytes(n, S, C) bytes:
+ *       a head of one 64-byte record per state, padded to 256 bytes -- n, ldd = 16 ceil(n / 16), the chunk length
+ *       1008 ceil(n / (1008 * 512)), the chunk count, the row offset -- then per state [1 + C][ldd] contiguous rows of
+ *       a - center, the very values (f-7)'s pre-pass writes: 8 (1 + C) sum_s ldd_s bytes.
+ *   txm_lag_sums_batched  the lag sums of n_items (state, pair) items (pair as in (f-7); any order, any subset, a state as
+ *       often as it has pairs listed) for the lags t0 .. t0 + nlags - 1, from the rows of the first call: one launch of
+ *       the auto instance, one of the cross instance (each only if the kind occurs) and one chunk sum.  The item rides
+ *       grid.y, grid.x is the largest chunk count among the listed states, workgroups past their state's chunk count leave
+ *       at once.  out (device): [n_items][nlags].  `n_host` (HOST, [S]) must be the record counts the rows were made with.
+ * The rows stay valid for any number of sums calls: a scan over lag blocks pays the centring pass once.
+ * BITS: every state keeps the chunking of (f-7) for its own n, a workgroup's (chunk, pair, lag tile) work is the same
+ * device function in both entry points, the four waves' tiles are added in wave order and the chunks in index order.  Row
+ * i of `out` therefore equals txm_lag_sums(x_s, ldx_s, u_s, n_s, C, center_s, {pair_i}, 1, t0, nlags, ...) BIT FOR BIT,
+ * whatever else is in the batch and however the items are cut into calls.  No floating-point atomics; two calls give the
+ * same bits.
+ * `states_host` and `items_host` are HOST arrays; the calls copy their tables into `rows` / `ws` (not stream-capturable).
+ * Workspace of the sums call: txm_lag_sums_batched_ws_bytes = the item table (16 bytes per item, padded to 256) plus
+ * 8 nlags sum_items chunks(n_state) bytes of partials -- per-item offsets, a prefix sum of the items' chunk counts, not
+ * the largest chunk count for every item (1 MB per item and 256 lags at n = 1e6).  The *_bytes functions are host logic
+ * and return 0 for bad arguments.
+ * Null pointers, S outside [1, 65535], any n outside [1, 2^36], C outside [0, 16383], x == NULL with C > 0, ldx_s < C,
+ * n_items outside [1, 65535], an item's state outside [0, S) or pair outside [0, 2 C], t0 not a multiple of 256, nlags not a
+ * multiple of 256 in [256, 4096] and a rows_bytes other than txm_lag_rows_batched_bytes(n, S, C) return TXM_ERR_INVALID, a
+ * short workspace TXM_ERR_WORKSPACE, all before anything is enqueued. */
+typedef struct txm_lag_state {
+  const double *x;      /* [n][ldx_s]; NULL iff C == 0 */
+  const double *u;      /* [n] */
+  const double *center; /* device, [1 + C]: <u>, <x_0> .. <x_{C-1}> */
+  int64_t n;
+} txm_lag_state;
+typedef struct txm_lag_item {
+  int32_t state;
+  int32_t pair;
+} txm_lag_item;
+size_t txm_lag_rows_batched_bytes(const int64_t *n_host, int64_t S, int64_t C);
+int txm_lag_rows_batched(const txm_lag_state *states_host, int64_t S, int64_t ldx_s, int64_t C, void *rows,
+                         size_t rows_bytes, txm_stream stream);
+size_t txm_lag_sums_batched_ws_bytes(const int64_t *n_host, int64_t S, int64_t C, const txm_lag_item *items_host,
+                                     int64_t n_items, int32_t nlags);
+int txm_lag_sums_batched(const void *rows, size_t rows_bytes, const int64_t *n_host, int64_t S, int64_t C,
+                         const txm_lag_item *items_host, int64_t n_items, int64_t t0, int32_t nlags, double *out, void *ws,
+                         size_t ws_bytes, txm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

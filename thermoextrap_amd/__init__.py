@@ -25,6 +25,7 @@ _LAZY = {
     "statistical_inefficiency": "timeseries", "statistical_inefficiencies": "timeseries", "subsample_correlated_data": "timeseries",
     "normalized_fluctuation_correlation_function": "timeseries", "decorrelate": "timeseries",
     "detect_equilibration": "timeseries", "detect_equilibrations": "timeseries", "equilibrate": "timeseries",
+    "statistical_inefficiencies_states": "timeseries", "decorrelate_states": "timeseries", "block_lengths": "timeseries",
 }
 _MODULES = {"stack", "distributed", "gpr_input", "beta", "data", "models", "moments", "idealgas", "symbolic", "engine", "xrlite", "volume", "volume_idealgas", "lnpi", "timeseries"}
 

@@ -53,6 +53,18 @@ class MbarBootState(ct.Structure):
     _fields_ = [("spec", SamplerSpec), ("counts", c_void_p)]
 
 
+class LagState(ct.Structure):
+    """txm_lag_state (include/txmom.h): one state's series and centres for txm_lag_rows_batched."""
+
+    _fields_ = [("x", c_void_p), ("u", c_void_p), ("center", c_void_p), ("n", c_i64)]
+
+
+class LagItem(ct.Structure):
+    """txm_lag_item (include/txmom.h): one (state, pair) of txm_lag_sums_batched."""
+
+    _fields_ = [("state", ct.c_int32), ("pair", ct.c_int32)]
+
+
 class Atom(ct.Structure):
     _fields_ = [("src", ct.c_int32), ("pad", ct.c_int32), ("offset", c_i64), ("s_rep", c_i64), ("s_val", c_i64)]
 
@@ -161,6 +173,11 @@ SIGNATURES = {
     "txm_lag_origin_sums_ws_bytes": (c_size, [c_i64, c_i64, ct.c_int32, c_i64, ct.c_int32]),
     "txm_lag_origin_sums": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, ct.POINTER(ct.c_int32), ct.c_int32,
                                     c_i64, c_i64, ct.c_int32, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_lag_rows_batched_bytes": (c_size, [ct.POINTER(c_i64), c_i64, c_i64]),
+    "txm_lag_rows_batched": (c_int, [ct.POINTER(LagState), c_i64, c_i64, c_i64, c_void_p, c_size, c_void_p]),
+    "txm_lag_sums_batched_ws_bytes": (c_size, [ct.POINTER(c_i64), c_i64, c_i64, ct.POINTER(LagItem), c_i64, ct.c_int32]),
+    "txm_lag_sums_batched": (c_int, [c_void_p, c_size, ct.POINTER(c_i64), c_i64, c_i64, ct.POINTER(LagItem), c_i64, c_i64,
+                                     ct.c_int32, c_void_p, c_void_p, c_size, c_void_p]),
     "txm_influence_cov_ws_bytes": (c_size, [c_i64, c_i64, c_int]),
     "txm_influence_cov": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, ct.c_double, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),

@@ -52,6 +52,7 @@
 // Every delta comes from the segment sums, not from X_j(0), so a lag block needs no other block: R_j(t) has the same bits
 // whichever 256-aligned (t0, nlags) block it is computed in.
 #include <cstring>
+#include <vector>
 
 #include "txm_common.h"
 
@@ -102,24 +103,16 @@ __global__ __launch_bounds__(LG_BLOCK) void lag_center_kernel(const double *__re
   }
 }
 
-// partial: [chunk][n_pairs][nlags]
+// One workgroup's share of the lag sums: the samples [cb, ce) of the pair (da, db), the NT lag tiles from lag tg on, written
+// to dst[NT * 256].  Shared by lag_kernel and lag_batched_kernel: a (chunk, pair, tile group) has the same bits in both.
 template <int NT, bool CROSS>
-__global__ __launch_bounds__(LG_BLOCK) void lag_kernel(const double *__restrict__ d, int64_t ldd, int64_t n, int C,
-                                                       const int32_t *__restrict__ pairs, int64_t chunk_len,
-                                                       int64_t t0, int nlags, double *__restrict__ partial) {
+__device__ __forceinline__ void lag_chunk(const double *__restrict__ da, const double *__restrict__ db, int64_t n, int64_t cb,
+                                          int64_t ce, int64_t tg, double *__restrict__ dst, double *smem) {
   constexpr int NB = LG_L + 256 * NT;  // the b window of a stage (a multiple of 16)
   constexpr int NBP = NB + NB / 16;    // ... with one pad double per 16
-  extern __shared__ double smem[];
-  const int p = pairs[blockIdx.y];
-  if ((p > C) != CROSS) return;        // the other instance's pair
-  const double *__restrict__ da = d + (int64_t)(CROSS ? p - C : p) * ldd;
-  const double *__restrict__ db = CROSS ? d : da;
   double *sa0 = smem, *sb0 = sa0 + LG_A, *sa1 = sb0 + NBP, *sb1 = sa1 + LG_A;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int m = lane & 15, k = lane >> 4;
-  const int64_t cb = (int64_t)blockIdx.x * chunk_len;
-  const int64_t ce = cb + chunk_len < n ? cb + chunk_len : n;
-  const int64_t tg = t0 + (int64_t)blockIdx.z * (256 * NT);
   lg_v4d acc[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) acc[j] = lg_v4d{0.0, 0.0, 0.0, 0.0};
@@ -166,7 +159,6 @@ __global__ __launch_bounds__(LG_BLOCK) void lag_kernel(const double *__restrict_
 #pragma unroll
     for (int r = 0; r < 4; ++r) smem[(wave * NT + j) * 256 + 16 * m + k + 4 * r] = acc[j][r];
   __syncthreads();
-  double *dst = partial + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * nlags + (size_t)blockIdx.z * (256 * NT);
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     double v = smem[j * 256 + tid];
@@ -176,6 +168,23 @@ __global__ __launch_bounds__(LG_BLOCK) void lag_kernel(const double *__restrict_
   }
 }
 
+// partial: [chunk][n_pairs][nlags]
+template <int NT, bool CROSS>
+__global__ __launch_bounds__(LG_BLOCK) void lag_kernel(const double *__restrict__ d, int64_t ldd, int64_t n, int C,
+                                                       const int32_t *__restrict__ pairs, int64_t chunk_len,
+                                                       int64_t t0, int nlags, double *__restrict__ partial) {
+  extern __shared__ double smem[];
+  const int p = pairs[blockIdx.y];
+  if ((p > C) != CROSS) return;        // the other instance's pair
+  const double *__restrict__ da = d + (int64_t)(CROSS ? p - C : p) * ldd;
+  const double *__restrict__ db = CROSS ? d : da;
+  const int64_t cb = (int64_t)blockIdx.x * chunk_len;
+  const int64_t ce = cb + chunk_len < n ? cb + chunk_len : n;
+  const int64_t tg = t0 + (int64_t)blockIdx.z * (256 * NT);
+  double *dst = partial + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * nlags + (size_t)blockIdx.z * (256 * NT);
+  lag_chunk<NT, CROSS>(da, db, n, cb, ce, tg, dst, smem);
+}
+
 __global__ __launch_bounds__(LG_BLOCK) void lag_sum_kernel(const double *__restrict__ partial, int nchunks, int C,
                                                            const int32_t *__restrict__ pairs, int n_pairs, int nlags,
                                                            double *__restrict__ out) {
@@ -183,6 +192,84 @@ __global__ __launch_bounds__(LG_BLOCK) void lag_sum_kernel(const double *__restr
   double acc = 0.0;
   for (int ch = 0; ch < nchunks; ++ch) acc += partial[((size_t)ch * n_pairs + slot) * nlags + t];
   out[(size_t)slot * nlags + t] = pairs[slot] > C ? acc : 2.0 * acc;
+}
+
+// ---- S states in one set of launches (txm_lag_rows_batched, txm_lag_sums_batched) ----
+// The head of the rows buffer: one record per state, written by the rows call and read by every kernel of both calls.
+struct lg_state_rec {
+  int64_t n, ldd, chunk_len, nchunks, row_off;  // row_off: the state's first row, in doubles from the end of the head
+  const double *x, *u, *center;                 // (the rows call's operands: only lag_center_batched_kernel reads them)
+};
+// One (state, pair) of a sums call; part_off: the items before it hold this many chunks (a prefix sum made on the host).
+struct lg_item_rec {
+  int32_t state, pair;
+  int64_t part_off;
+};
+
+static inline size_t lg_rows_head(int64_t S) { return align_up((size_t)S * sizeof(lg_state_rec), 256); }
+
+// lag_center_kernel with the state on grid.z: the same subtraction, the rows of state s at rows + row_off.
+__global__ __launch_bounds__(LG_BLOCK) void lag_center_batched_kernel(const lg_state_rec *__restrict__ tab, int64_t ldx,
+                                                                      int64_t C, double *__restrict__ rows) {
+  __shared__ double tile[32][65];
+  const lg_state_rec st = tab[blockIdx.z];
+  const int64_t n = st.n, ldd = st.ldd;
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  if (r0 >= n) return;                 // past this state's records
+  const double *__restrict__ x = st.x, *__restrict__ u = st.u, *__restrict__ center = st.center;
+  double *__restrict__ d = rows + st.row_off;
+  const int tid = threadIdx.x;
+  if (blockIdx.y == 0 && tid < 64 && r0 + tid < n) d[r0 + tid] = u[r0 + tid] - center[0];
+  const int64_t c0 = (int64_t)blockIdx.y * 32;
+  if (c0 >= C) return;
+#pragma unroll
+  for (int pass = 0; pass < 8; ++pass) {
+    const int r = (tid >> 5) + 8 * pass, c = tid & 31;
+    if (r0 + r < n && c0 + c < C) tile[c][r] = x[(r0 + r) * ldx + c0 + c] - center[1 + c0 + c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int pass = 0; pass < 8; ++pass) {
+    const int c = (tid >> 6) + 4 * pass, r = tid & 63;
+    if (r0 + r < n && c0 + c < C) d[(1 + c0 + c) * ldd + r0 + r] = tile[c][r];
+  }
+}
+
+// partial: [item][chunk of the item's state][nlags], item i from chunk row items[i].part_off on
+template <int NT, bool CROSS>
+__global__ __launch_bounds__(LG_BLOCK) void lag_batched_kernel(const lg_state_rec *__restrict__ tab,
+                                                               const double *__restrict__ rows,
+                                                               const lg_item_rec *__restrict__ items, int C, int64_t t0,
+                                                               int nlags, double *__restrict__ partial) {
+  extern __shared__ double smem[];
+  const lg_item_rec it = items[blockIdx.y];
+  const int p = it.pair;
+  if ((p > C) != CROSS) return;        // the other instance's pair
+  const lg_state_rec st = tab[it.state];
+  if ((int64_t)blockIdx.x >= st.nchunks) return;  // a shorter state than the one that sets grid.x
+  const double *__restrict__ d = rows + st.row_off;
+  const double *__restrict__ da = d + (int64_t)(CROSS ? p - C : p) * st.ldd;
+  const double *__restrict__ db = CROSS ? d : da;
+  const int64_t n = st.n;
+  const int64_t cb = (int64_t)blockIdx.x * st.chunk_len;
+  const int64_t ce = cb + st.chunk_len < n ? cb + st.chunk_len : n;
+  const int64_t tg = t0 + (int64_t)blockIdx.z * (256 * NT);
+  double *dst = partial + ((size_t)it.part_off + blockIdx.x) * nlags + (size_t)blockIdx.z * (256 * NT);
+  lag_chunk<NT, CROSS>(da, db, n, cb, ce, tg, dst, smem);
+}
+
+// out: [item][nlags]; the chunks of an item in index order, the auto pairs doubled
+__global__ __launch_bounds__(LG_BLOCK) void lag_sum_batched_kernel(const double *__restrict__ partial,
+                                                                   const lg_state_rec *__restrict__ tab,
+                                                                   const lg_item_rec *__restrict__ items, int C, int nlags,
+                                                                   double *__restrict__ out) {
+  const int t = blockIdx.x * LG_BLOCK + threadIdx.x;
+  const lg_item_rec it = items[blockIdx.y];
+  const int nchunks = (int)tab[it.state].nchunks;
+  const double *__restrict__ p = partial + (size_t)it.part_off * nlags + t;
+  double acc = 0.0;
+  for (int ch = 0; ch < nchunks; ++ch) acc += p[(size_t)ch * nlags];
+  out[(size_t)blockIdx.y * nlags + t] = it.pair > C ? acc : 2.0 * acc;
 }
 
 // partial: [segment][series][Q, X][nlags].  Segment j is [j nskip, (j + 1) nskip), the last one runs to n.
@@ -396,6 +483,139 @@ extern "C" int txm_lag_sums(const double *x, int64_t ldx_s, const double *u, int
 #undef TXM_LG
   hipLaunchKernelGGL(lag_sum_kernel, dim3((unsigned)(nlags / LG_BLOCK), (unsigned)n_pairs), dim3(LG_BLOCK), 0, st, partial,
                      (int)nchunks, (int)C, pairs, (int)n_pairs, (int)nlags, out);
+  TXM_LAUNCH_CHECK();
+  return TXM_OK;
+}
+
+// ---- the batched entry points ------------------------------------------------------------------------------
+namespace txm {
+static bool lg_batch_shape_ok(const int64_t *n_host, int64_t S, int64_t C) {
+  if (!n_host || S < 1 || S > 65535 || C < 0 || C > 16383) return false;
+  for (int64_t s = 0; s < S; ++s)
+    if (n_host[s] < 1 || n_host[s] > ((int64_t)1 << 36)) return false;
+  return true;
+}
+static inline size_t lg_items_head(int64_t n_items) { return align_up((size_t)n_items * sizeof(lg_item_rec), 256); }
+}  // namespace txm
+
+extern "C" size_t txm_lag_rows_batched_bytes(const int64_t *n_host, int64_t S, int64_t C) {
+  if (!lg_batch_shape_ok(n_host, S, C)) return 0;
+  size_t rows = 0;
+  for (int64_t s = 0; s < S; ++s) rows += (size_t)(1 + C) * (size_t)lg_ldd(n_host[s]);
+  return lg_rows_head(S) + rows * sizeof(double);
+}
+
+extern "C" int txm_lag_rows_batched(const txm_lag_state *states_host, int64_t S, int64_t ldx_s, int64_t C, void *rows,
+                                    size_t rows_bytes, txm_stream stream) {
+  TXM_REQUIRE(states_host && rows, "lag_rows_batched: null pointer");
+  TXM_REQUIRE(S >= 1 && S <= 65535, "lag_rows_batched: S = %lld outside [1, 65535]", (long long)S);
+  TXM_REQUIRE(C >= 0 && C <= 16383, "lag_rows_batched: C = %lld outside [0, 16383]", (long long)C);
+  TXM_REQUIRE(C == 0 || ldx_s >= C, "lag_rows_batched: row pitch ldx_s = %lld < C = %lld", (long long)ldx_s, (long long)C);
+  static thread_local std::vector<lg_state_rec> tab_host;
+  tab_host.resize((size_t)S);
+  int64_t off = 0, n_max = 1;
+  for (int64_t s = 0; s < S; ++s) {
+    const txm_lag_state &h = states_host[s];
+    TXM_REQUIRE(h.u && h.center, "lag_rows_batched: null pointer (u or center of state %lld)", (long long)s);
+    TXM_REQUIRE(h.n >= 1 && h.n <= ((int64_t)1 << 36), "lag_rows_batched: n = %lld of state %lld outside [1, 2^36]",
+                (long long)h.n, (long long)s);
+    TXM_REQUIRE(C == 0 || h.x, "lag_rows_batched: null x of state %lld with C = %lld columns", (long long)s, (long long)C);
+    const int64_t ldd = lg_ldd(h.n), chunk_len = lg_chunk_len(h.n);
+    tab_host[(size_t)s] = lg_state_rec{h.n, ldd, chunk_len, cdiv(h.n, chunk_len), off, h.x, h.u, h.center};
+    off += (1 + C) * ldd;
+    if (h.n > n_max) n_max = h.n;
+  }
+  const size_t head = lg_rows_head(S);
+  TXM_REQUIRE(rows_bytes == head + (size_t)off * sizeof(double),
+              "lag_rows_batched: rows_bytes = %zu is not txm_lag_rows_batched_bytes = %zu", rows_bytes,
+              head + (size_t)off * sizeof(double));
+  hipStream_t st = (hipStream_t)stream;
+  lg_state_rec *tab = (lg_state_rec *)rows;
+  TXM_HIP(hipMemcpyAsync(tab, tab_host.data(), (size_t)S * sizeof(lg_state_rec), hipMemcpyHostToDevice, st));
+  const int64_t cblocks = C > 0 ? cdiv(C, 32) : 1;
+  hipLaunchKernelGGL(lag_center_batched_kernel, dim3((unsigned)cdiv(n_max, 64), (unsigned)cblocks, (unsigned)S),
+                     dim3(LG_BLOCK), 0, st, tab, ldx_s, C, (double *)((char *)rows + head));
+  TXM_LAUNCH_CHECK();
+  return TXM_OK;
+}
+
+extern "C" size_t txm_lag_sums_batched_ws_bytes(const int64_t *n_host, int64_t S, int64_t C, const txm_lag_item *items_host,
+                                                int64_t n_items, int32_t nlags) {
+  if (!lg_batch_shape_ok(n_host, S, C) || !items_host || n_items < 1 || n_items > 65535) return 0;
+  if (nlags < 256 || nlags > LG_MAX_LAGS || nlags % 256 != 0) return 0;
+  size_t chunks = 0;
+  for (int64_t i = 0; i < n_items; ++i) {
+    const txm_lag_item &it = items_host[i];
+    if (it.state < 0 || it.state >= S || it.pair < 0 || it.pair > 2 * C) return 0;
+    chunks += (size_t)cdiv(n_host[it.state], lg_chunk_len(n_host[it.state]));
+  }
+  return lg_items_head(n_items) + chunks * (size_t)nlags * sizeof(double);
+}
+
+extern "C" int txm_lag_sums_batched(const void *rows, size_t rows_bytes, const int64_t *n_host, int64_t S, int64_t C,
+                                    const txm_lag_item *items_host, int64_t n_items, int64_t t0, int32_t nlags, double *out,
+                                    void *ws, size_t ws_bytes, txm_stream stream) {
+  TXM_REQUIRE(rows && n_host && items_host && out && ws, "lag_sums_batched: null pointer");
+  TXM_REQUIRE(S >= 1 && S <= 65535, "lag_sums_batched: S = %lld outside [1, 65535]", (long long)S);
+  TXM_REQUIRE(C >= 0 && C <= 16383, "lag_sums_batched: C = %lld outside [0, 16383]", (long long)C);
+  for (int64_t s = 0; s < S; ++s)
+    TXM_REQUIRE(n_host[s] >= 1 && n_host[s] <= ((int64_t)1 << 36), "lag_sums_batched: n = %lld of state %lld outside [1, 2^36]",
+                (long long)n_host[s], (long long)s);
+  TXM_REQUIRE(n_items >= 1 && n_items <= 65535, "lag_sums_batched: n_items = %lld outside [1, 65535]", (long long)n_items);
+  TXM_REQUIRE(t0 >= 0 && t0 % 256 == 0 && t0 <= ((int64_t)1 << 36),
+              "lag_sums_batched: t0 = %lld is not a multiple of 256 in [0, 2^36]", (long long)t0);
+  TXM_REQUIRE(nlags >= 256 && nlags % 256 == 0 && nlags <= LG_MAX_LAGS,
+              "lag_sums_batched: nlags = %d is not a multiple of 256 in [256, %d]", (int)nlags, LG_MAX_LAGS);
+  static thread_local std::vector<lg_item_rec> items;
+  items.resize((size_t)n_items);
+  int64_t chunks = 0, grid_x = 1;
+  bool any_auto = false, any_cross = false;
+  for (int64_t i = 0; i < n_items; ++i) {
+    const txm_lag_item &it = items_host[i];
+    TXM_REQUIRE(it.state >= 0 && it.state < S, "lag_sums_batched: state index %d (item %lld) outside [0, S = %lld)",
+                (int)it.state, (long long)i, (long long)S);
+    TXM_REQUIRE(it.pair >= 0 && it.pair <= 2 * C, "lag_sums_batched: pair index %d (item %lld) outside [0, 2 C = %lld]",
+                (int)it.pair, (long long)i, (long long)(2 * C));
+    const int64_t nch = cdiv(n_host[it.state], lg_chunk_len(n_host[it.state]));
+    items[(size_t)i] = lg_item_rec{it.state, it.pair, chunks};
+    chunks += nch;
+    if (nch > grid_x) grid_x = nch;
+    (it.pair > C ? any_cross : any_auto) = true;
+  }
+  TXM_REQUIRE(rows_bytes == txm_lag_rows_batched_bytes(n_host, S, C),
+              "lag_sums_batched: rows_bytes = %zu is not txm_lag_rows_batched_bytes = %zu of these states", rows_bytes,
+              txm_lag_rows_batched_bytes(n_host, S, C));
+  const size_t head = lg_items_head(n_items);
+  if (ws_bytes < head + (size_t)chunks * (size_t)nlags * sizeof(double)) {
+    set_error("lag_sums_batched: workspace too small");
+    return TXM_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const lg_state_rec *tab = (const lg_state_rec *)rows;
+  const double *d = (const double *)((const char *)rows + lg_rows_head(S));
+  lg_item_rec *items_dev = (lg_item_rec *)ws;
+  double *partial = (double *)((char *)ws + head);
+  TXM_HIP(hipMemcpyAsync(items_dev, items.data(), (size_t)n_items * sizeof(lg_item_rec), hipMemcpyHostToDevice, st));
+  const int nt = lg_tiles(nlags);
+  const dim3 grid((unsigned)grid_x, (unsigned)n_items, (unsigned)(nlags / (256 * nt))), block(LG_BLOCK);
+#define TXM_LGB(NT_, X_)                                                                                              \
+  hipLaunchKernelGGL((lag_batched_kernel<NT_, X_>), grid, block, lg_lds_bytes(NT_, X_), st, tab, d, items_dev, (int)C, \
+                     t0, (int)nlags, partial)
+  if (any_auto) {
+    if (nt == 4) TXM_LGB(4, false);
+    else if (nt == 2) TXM_LGB(2, false);
+    else TXM_LGB(1, false);
+    TXM_LAUNCH_CHECK();
+  }
+  if (any_cross) {
+    if (nt == 4) TXM_LGB(4, true);
+    else if (nt == 2) TXM_LGB(2, true);
+    else TXM_LGB(1, true);
+    TXM_LAUNCH_CHECK();
+  }
+#undef TXM_LGB
+  hipLaunchKernelGGL(lag_sum_batched_kernel, dim3((unsigned)(nlags / LG_BLOCK), (unsigned)n_items), dim3(LG_BLOCK), 0, st,
+                     partial, tab, items_dev, (int)C, (int)nlags, out);
   TXM_LAUNCH_CHECK();
   return TXM_OK;
 }

@@ -1596,3 +1596,120 @@ def lag_origin_sums(x: torch.Tensor | None, u: torch.Tensor, series, nskip: int,
         if part is not out:
             out[:, :, off:off + step] = part
     return out, mean
+
+
+# ---------------------------------------------------------------------------
+# lag sums of a state collection (timeseries.statistical_inefficiencies_states): the centred rows of all states from one
+# launch, kept over the lag blocks of a scan; every (state, pair) of a block from one launch set
+# ---------------------------------------------------------------------------
+LAG_MAX_ITEMS = 65535  # (state, pair) items per library call (the item rides grid.y)
+
+
+def lag_chunks(n: int) -> int:
+    """The number of sample chunks the lag kernels cut a series of n records into (txm_lagsum.hip: lg_chunk_len)."""
+    n = int(n)
+    return -(-n // (LAG_STAGE * max(1, -(-n // (LAG_STAGE * 512)))))
+
+
+def lag_sums_batched_ws_bytes(ns, items, nlags: int) -> int:
+    """txm_lag_sums_batched_ws_bytes restated on the host: the item table (16 bytes per item, padded to 256) and one
+    partial per (item, chunk of its state, lag)."""
+    return -(-16 * len(items) // 256) * 256 + 8 * int(nlags) * sum(lag_chunks(ns[s]) for s, _ in items)
+
+
+def lag_item_slices(ns, items, nlags: int, budget: int) -> list[slice]:
+    """The cuts of ``items`` [(state, pair), ...] into library calls: consecutive runs, each as long as its workspace
+    (``lag_sums_batched_ws_bytes``) fits ``budget`` and it has at most 65535 items -- at least one item, fitting or not."""
+    out, a, chunks = [], 0, 0
+    per = 8 * int(nlags)
+    for i, (s, _) in enumerate(items):
+        c = lag_chunks(ns[s])
+        k = i - a + 1
+        if i > a and (k > LAG_MAX_ITEMS or -(-16 * k // 256) * 256 + per * (chunks + c) > budget):
+            out.append(slice(a, i))
+            a, chunks = i, 0
+        chunks += c
+    if len(items) > a:
+        out.append(slice(a, len(items)))
+    return out
+
+
+class LagRows(NamedTuple):
+    """What ``lag_rows_batched`` returns and ``lag_sums_batched`` takes: the rows buffer of txm_lag_rows_batched, the record
+    counts it was made with, the column count and the centres (S tensors of (1 + C,))."""
+
+    rows: torch.Tensor
+    ns: np.ndarray
+    C: int
+    centers: list
+
+
+def lag_rows_batched(xs, us, centers=None) -> LagRows:
+    """The centred, transposed series of S states from ONE launch, for any number of ``lag_sums_batched`` calls.  xs: S
+    tensors (n_s, C) sharing C (None, or a list of None, for the energies alone), us: S tensors (n_s,).  ``centers``: S
+    tensors (1 + C,); None takes ``lag_center`` of every state -- S small reductions, and the very means ``lag_sums``
+    takes, so that every lag sum equals the single-state call's bit for bit."""
+    L = _L()
+    S = len(us)
+    if S == 0:
+        raise ValueError("no states")
+    xs = [None] * S if xs is None else list(xs)
+    if len(xs) != S:
+        raise ValueError(f"{len(xs)} sample matrices for {S} energy series")
+    args = [_lag_series_args(x, u) for x, u in zip(xs, us)]
+    C = args[0][3]
+    if any(a[3] != C for a in args):
+        raise ValueError(f"the states differ in their column count: {sorted({a[3] for a in args})}")
+    x2s = [a[0] for a in args]
+    ls = 0
+    if C:                                            # one row pitch for the launch (a single row has none of its own)
+        pitches = {a[4] for a in args if a[2] > 1}
+        ls = pitches.pop() if len(pitches) == 1 else C
+        if pitches:
+            x2s = [x2.contiguous() for x2 in x2s]
+    u2s = [a[1] for a in args]
+    if centers is None:
+        centers = [lag_center(None if x is None else (x.unsqueeze(1) if x.dim() == 1 else x), u) for x, u in zip(xs, u2s)]
+    centers = list(centers)
+    if len(centers) != S:
+        raise ValueError(f"{len(centers)} centres for {S} states")
+    for c in centers:
+        _check_f64_cuda(c, "center")
+        if c.shape != (1 + C,):
+            raise ValueError(f"center must have shape ({1 + C},), got {tuple(c.shape)}")
+    centers = [c.contiguous() for c in centers]
+    ns = np.ascontiguousarray([a[2] for a in args], dtype=np.int64)
+    tab = (_lib.LagState * S)(*[_lib.LagState(x2.data_ptr() if C else None, u.data_ptr(), c.data_ptr(), int(n))
+                                for x2, u, c, n in zip(x2s, u2s, centers, ns)])
+    nbytes = L.txm_lag_rows_batched_bytes(ns.ctypes.data_as(ct.POINTER(ct.c_int64)), S, C)
+    if nbytes == 0:
+        raise ValueError(f"lag_rows_batched: {S} states of {C} columns and {int(ns.min())} .. {int(ns.max())} records are out of range")
+    rows = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    check(L.txm_lag_rows_batched(tab, S, ls, C, _ptr(rows), nbytes, _stream()), "txm_lag_rows_batched")
+    return LagRows(rows, ns, C, centers)
+
+
+def lag_sums_batched(handle: LagRows, items, t0: int, nlags: int) -> torch.Tensor:
+    """R(t), t = t0 .. t0 + nlags - 1, of every (state, pair) of ``items`` (pair as in ``lag_sums``; any order, any subset)
+    from the rows of ``lag_rows_batched``: (len(items), nlags), row i bit for bit ``lag_sums`` of that state and pair
+    with the handle's centre.  The item list is cut into several library calls where the partials (one per item, chunk
+    and lag) would exceed ``workspace_budget()``, and at 65535 items; the cuts change no bits."""
+    L = _L()
+    items = [(int(s), int(p)) for s, p in items]
+    if not items:
+        raise ValueError("items must be a non-empty list of (state, pair)")
+    S, C, ns = len(handle.ns), handle.C, handle.ns
+    for s, p in items:
+        if not (0 <= s < S and 0 <= p <= 2 * C):
+            raise ValueError(f"item ({s}, {p}) outside {S} states x pairs [0, {2 * C}]")
+    t0, nlags = int(t0), int(nlags)
+    out = torch.empty((len(items), nlags), dtype=F64, device="cuda")
+    np_ns = ns.ctypes.data_as(ct.POINTER(ct.c_int64))
+    for sl in lag_item_slices(ns, items, nlags, workspace_budget()):
+        part = items[sl]
+        tab = (_lib.LagItem * len(part))(*[_lib.LagItem(s, p) for s, p in part])
+        nws = L.txm_lag_sums_batched_ws_bytes(np_ns, S, C, tab, len(part), nlags)
+        ws = workspace(nws, tag="lag")
+        check(L.txm_lag_sums_batched(_ptr(handle.rows), handle.rows.numel(), np_ns, S, C, tab, len(part), t0, nlags,
+                                     _ptr(out[sl.start:sl.stop]), _ptr(ws), ws.numel(), _stream()), "txm_lag_sums_batched")
+    return out

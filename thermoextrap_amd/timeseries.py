@@ -12,6 +12,11 @@ energy) pair, the largest of them as g, ``subsample_correlated_data`` with it, a
   detect_equilibration                 pymbar.timeseries' function of that name: where the initial transient ends;
   detect_equilibrations(uv, xv)        the same for the energy and every observable column in one set of launches;
   equilibrate(uv, xv, w)               drops the transient on the device; its output feeds decorrelate unchanged.
+  statistical_inefficiencies_states, decorrelate_states, block_lengths
+      the same for a COLLECTION of states (lists of uv, xv; one column count, any record counts): the centred series of all
+      states made once and kept over the scan, one set of launches and one copy per lag block for every state
+      (engine.lag_rows_batched, lag_sums_batched -> txm_lag_rows_batched, txm_lag_sums_batched); every result equals the
+      single-state function's in every field.
 
 The estimator.  dA = A - mean(A), dB = B - mean(B) (B = A when omitted), sigma^2 = mean(dA dB) (0 raises ValueError),
 
@@ -491,3 +496,157 @@ def equilibrate(uv, xv, w=None, *, t0: int | None = None, **kw):
         outs = [None if a is None else DataArray(a.cpu().numpy(), d) for a, d in zip(outs, dims)]
     info = {"t0": t0, "n": int(u.shape[0] - t0), "equilibration": eq}
     return outs[0], outs[1], outs[2], info
+
+
+# ---------------------------------------------------------------------------
+# a collection of states: the same estimator, every state's lag sums from one set of launches per lag block
+# ---------------------------------------------------------------------------
+def scan_lag_sums_states(fetch: Callable[[list, int, int], np.ndarray], ns, pair_ids_per_state, *, fast: bool = False,
+                         mintime: int = 3, max_lag: int | None = None, names=None):
+    """``scan_lag_sums`` for S states at once.  ``fetch(items, t0, nlags)`` returns R(t0 .. t0 + nlags - 1) of the listed
+    (state, pair) items as a (len(items), nlags) float64 array.  The common block sequence (0, 256), (256, 256), (512, 512),
+    ... is walked once, ONE fetch per block over every pair that is still active; a state takes part in a block only if
+    it is block 0 or t0 < n_s - 1 (``lag_blocks(n_s)``'s own rule), so each state sees exactly the blocks, and its pairs
+    exactly the loop, of ``scan_lag_sums(fetch_s, n_s, pair_ids_s)``.  Returns a list of (g, stop) per state, in the order
+    of that state's pair ids.  ``names``: per state the names of its pairs; the ValueErrors (sigma^2 == 0, ``max_lag``)
+    name the pair and the state."""
+    ns = [int(n) for n in ns]
+    S = len(ns)
+    pids = [[int(p) for p in ps] for ps in pair_ids_per_state]
+    if len(pids) != S:
+        raise ValueError(f"{len(pids)} pair lists for {S} states")
+    names = [None] * S if names is None else list(names)
+    if len(names) != S:
+        raise ValueError(f"{len(names)} name lists for {S} states")
+    names = [[f"{nm} of state {s}" for nm in (nl if nl is not None else [f"pair {p}" for p in pids[s]])] for s, nl in enumerate(names)]
+    g = [np.ones(len(p)) for p in pids]
+    t = [np.ones(len(p), dtype=np.int64) for p in pids]
+    inc = [np.ones(len(p), dtype=np.int64) for p in pids]
+    sig2 = [np.zeros(len(p)) for p in pids]
+    active = [list(range(len(p))) for p in pids]
+    t0, nl = 0, LAG_BLOCK
+    while True:
+        states = [s for s in range(S) if active[s] and (t0 == 0 or t0 < ns[s] - 1)]
+        if not states:
+            break
+        items = [(s, pids[s][k]) for s in states for k in active[s]]
+        R = np.asarray(fetch(items, t0, nl), dtype=np.float64)
+        if R.shape != (len(items), nl):
+            raise ValueError(f"fetch returned {R.shape}, expected {(len(items), nl)}")
+        row = 0
+        for s in states:
+            n, still = ns[s], []
+            for k in active[s]:
+                if t0 == 0:
+                    sig2[s][k] = R[row, 0] / (2.0 * n)
+                    if sig2[s][k] == 0.0:
+                        raise ValueError(f"sample covariance sigma_AB^2 = 0 for {names[s][k]}: cannot compute the statistical inefficiency")
+                tk, ik, gk, done = _scan_block(R[row], t0, nl, n, sig2[s][k], int(t[s][k]), int(inc[s][k]), g[s][k], fast, mintime,
+                                               max_lag, names[s][k])
+                t[s][k], inc[s][k], g[s][k] = tk, ik, gk
+                if not done and tk < n - 1:
+                    still.append(k)
+                row += 1
+            active[s] = still
+        t0 += nl
+        nl = min(t0, LAG_MAX_LAGS)
+    return [(np.maximum(g[s], 1.0), t[s]) for s in range(S)]
+
+
+def _prepare_states(uvs, xvs):
+    """[(u, x, kind)] of ``_prepare`` per state; ValueError for an empty collection, lists of unequal length and states that
+    differ in their column count."""
+    uvs = list(uvs)
+    xvs = [None] * len(uvs) if xvs is None else list(xvs)
+    if not uvs:
+        raise ValueError("no states")
+    if len(xvs) != len(uvs):
+        raise ValueError(f"{len(uvs)} energy series and {len(xvs)} observable arrays")
+    st = [_prepare(uv, xv) for uv, xv in zip(uvs, xvs)]
+    cols = [0 if x is None else x.shape[1] for _, x, _ in st]
+    if len(set(cols)) > 1:
+        raise ValueError(f"the states differ in their column count: {cols}")
+    return st, cols[0]
+
+
+def _inefficiencies_states(st, C, fast, mintime, max_lag):
+    from . import engine
+
+    S = len(st)
+    rows = engine.lag_rows_batched(None if C == 0 else [x for _, x, _ in st], [u for u, _, _ in st])
+
+    def fetch(items, t0, nlags):
+        return engine.lag_sums_batched(rows, items, t0, nlags).cpu().numpy()
+
+    res = scan_lag_sums_states(fetch, [u.shape[0] for u, _, _ in st], [range(2 * C + 1)] * S, fast=fast, mintime=mintime,
+                               max_lag=max_lag, names=[_pair_names(C)] * S)
+    return [Inefficiencies(float(g[0]), g[1:1 + C].copy(), g[1 + C:].copy(), float(g.max()), int(stop[0]),
+                           stop[1:1 + C].copy(), stop[1 + C:].copy()) for g, stop in res]
+
+
+def statistical_inefficiencies_states(uvs, xvs, *, fast: bool = False, mintime: int = 3, max_lag: int | None = None) -> list:
+    """``statistical_inefficiencies`` of every state of a collection: uvs a list of energy series (rec), xvs a list of
+    (rec, val) arrays sharing the column count (None: the energies alone); the record counts may differ.  The centred series
+    of all states are made once (one launch) and kept for the whole scan; every lag block is one set of launches and one
+    device-to-host copy for all states.  Element s equals ``statistical_inefficiencies(uvs[s], xvs[s], ...)`` in every
+    field: the lag sums and the means have the same bits and the host loop is the same loop."""
+    st, C = _prepare_states(uvs, xvs)
+    return _inefficiencies_states(st, C, fast, mintime, max_lag)
+
+
+def block_lengths(uvs, xvs, factor: float = 10.0, **kw) -> list:
+    """``block_length`` of every state of a collection, from one ``statistical_inefficiencies_states``: what
+    ``StateCollection.derivs_cov(block=[...])`` and ``derivs_cross_cov(block=[...])`` take."""
+    if not factor > 0:
+        raise ValueError(f"factor must be positive, got {factor}")
+    return [max(1, int(math.ceil(float(factor) * i.g_max))) for i in statistical_inefficiencies_states(uvs, xvs, **kw)]
+
+
+def decorrelate_states(uvs, xvs, ws=None, *, g=None, conservative: bool = False, **kw) -> list:
+    """``decorrelate`` of every state of a collection: a list of (uv, xv, w, info) of the kinds and dims ``decorrelate``
+    returns.  ``g``: None (estimated for all states by ``statistical_inefficiencies_states``; further keywords go there), one
+    number for every state, or one number per state.  The gather is one ``index_select`` per state."""
+    import torch
+
+    from .moments import DeviceDataArray
+    from .xrlite import DataArray
+
+    if xvs is None:
+        raise TypeError("xvs is required")
+    st, C = _prepare_states(uvs, xvs)
+    S = len(st)
+    ws = [None] * S if ws is None else list(ws)
+    if len(ws) != S:
+        raise ValueError(f"{S} states and {len(ws)} weight arrays")
+    wts = []
+    for (u, _, _), w in zip(st, ws):
+        wt = None
+        if w is not None:
+            wt, _ = _device_series(w, 1, "w")
+            if wt.shape != u.shape:
+                raise ValueError(f"w has {wt.shape[0]} records, uv {u.shape[0]}")
+        wts.append(wt)
+    ineffs = [None] * S
+    if g is None:
+        ineffs = _inefficiencies_states(st, C, kw.pop("fast", False), kw.pop("mintime", 3), kw.pop("max_lag", None))
+        if kw:
+            raise TypeError(f"unexpected keywords {sorted(kw)}")
+        gs = [i.g_max for i in ineffs]
+    else:
+        if kw:
+            raise TypeError(f"keywords {sorted(kw)} only apply when g is estimated")
+        gs = [float(g)] * S if np.ndim(g) == 0 else [float(v) for v in g]
+        if len(gs) != S:
+            raise ValueError(f"{S} states and {len(gs)} values of g")
+    out = []
+    dims = [("rec",), ("rec", "val"), ("rec",)]
+    for (u, x, kind), wt, gk, ineff in zip(st, wts, gs, ineffs):
+        idx = subsample_correlated_data(u.shape[0], gk, conservative=conservative)
+        di = torch.as_tensor(idx).to("cuda")
+        arrs = [u.index_select(0, di), x.index_select(0, di), None if wt is None else wt.index_select(0, di)]
+        if kind == "device":
+            arrs = [None if a is None else DeviceDataArray(a, d) for a, d in zip(arrs, dims)]
+        else:
+            arrs = [None if a is None else DataArray(a.cpu().numpy(), d) for a, d in zip(arrs, dims)]
+        out.append((arrs[0], arrs[1], arrs[2], {"g": float(gk), "indices": idx, "n": int(idx.size), "inefficiencies": ineff}))
+    return out
