@@ -1,4 +1,4 @@
-"""Differential tests of the FP64 bootstrap, resample_kernel / resample_finalize_kernel of txm_resample.hip -- the kernel that
+"""Differential tests of the FP64 bootstrap, resample_kernel / resample_finalize_kernel of txm_resample_fp64.hip -- the kernel that
 serves order 8, explicit frequency tables, series shorter than one sampler tile and every window the int8 precision guard
 hands back, and the yardstick of every int8 test -- against the long-double two-pass definition (oracle.truth_cov_multi) on
 the same float64 inputs, on every path of its dispatch: every instantiation <K, NBLK, WEIGHTED, EXPLICIT, SMALLN, MODE, PACK>
@@ -64,7 +64,7 @@ def off_pivot_rtol(order):
     return 4.0 ** order * 3e-13
 
 
-# ---- the dispatch, restated (plan_resample, plan_batched, run_resample of txm_resample.hip) ----------------------------------
+# ---- the dispatch, restated (plan_resample, plan_batched of txm_resample.hip; run_resample of txm_resample_fp64.hip) ---------
 def chunk_tiles(ntiles, div):
     nc = min(max(ntiles // div, 8), 1024)
     nc = cdiv(min(nc, ntiles), 8) * 8

@@ -88,7 +88,7 @@ static __global__ void pivot_rows_kernel(const double *__restrict__ u, int64_t l
 
 // ---------------------------------------------------------------------------
 // Weighted pivots (the reduce entry points with w != NULL; the kernels above stay what they are for the unweighted calls
-// and for txm_resample.hip).  The sums are accumulated about the pivot and an off-pivot of delta weighted sigmas costs
+// and for the bootstrap calls of txm_resample.hip).  The sums are accumulated about the pivot and an off-pivot of delta weighted sigmas costs
 // about (1 + delta)^order in accuracy, so with weights the pivot has to sit near the WEIGHTED mean: reweighting weights
 // exp(-dbeta u) or a mask put it many weighted sigmas from the unweighted one.  Rule, per series (one block each):
 //   1. weighted mean of ns = min(N, 1024) samples spread evenly over the series, rows floor(k N / ns) -- NOT the stride

@@ -1,738 +1,17 @@
-// txm_resample.hip -- sample-level bootstrap of central comoments
+// txm_resample.hip -- sample-level bootstrap of central comoments, the host side
 // (cmomy.wrap_resample_vals as called from thermoextrap data.py:1803-1810,
-// 1354-1366).
-//
-// out[r] = comoment state of the data with weights w_i * f[r][i].  With the
-// pivot-shifted monomials m[i][c][j] = (x_ic - px_c) (u_i - pu)^j this is a
-// dense contraction over samples
-//        S1[r][c][j] = sum_i f[r][i] * w_i * du_i^j * dx_ic
-//        S0[r][j]    = sum_i f[r][i] * w_i * du_i^j
-// i.e. ~2*K*(C+1) flop per (replicate, sample) against 8*(C+1) bytes per
-// sample read once: FP64-bound for nrep >~ 12, so it runs on the FP64 matrix
-// pipe.  Per wave and per 4 samples:
-//        A_j (16 reps x 4 samples)  = f * w * du^j      one f64 per lane
-//        B   (4 samples x 16 cols)  = dx                one f64 per lane
-//        D_j (16 reps x 16 cols)   += A_j * B           v_mfma_f64_16x16x4_f64
-// so the power index j rides on the A operand (one multiply per j) and B is
-// loaded once per column block; S0 is the row-sum of A_j, kept on the VALU.
-// The MFMA broadcasts f over columns and dx over replicates for free, and the
-// VALU (Philox draws, LDS histogram, u-row sums) co-executes with the matrix
-// pipe of the other resident wave.
-//
-// f comes either from the Philox stage-3 stream (scale mode; the wave fills a
-// private [1024 samples][16 reps] u8 tile in LDS, never touching HBM) or from an
-// explicit int64 freq table (parity mode).
-#include <type_traits>
-
+// 1354-1366): the plans (workspace and pre-pass block layouts), the rules that choose a kernel, the size and path
+// queries, and txm_resample_vals / txm_resample_vals_batched[_opts], which drive the five bootstrap kernels --
+// the FP64 kernel and the finalize kernels (txm_resample_fp64.hip) and the int8 kernels (txm_resample_i8.hip, _i8t.hip,
+// _i8g.hip, _i8gn.hip) behind the count-table generator (txm_count_table.hip).
 #include <stdlib.h>
 
 #include "txm_sampler.h"
 #include "txm_pivot.h"
-#include "txm_resample_i8.h"
+#include "txm_resample_fp64.h"
 #include "txm_i8g.h"
 
 namespace txm {
-
-typedef double v4f64 __attribute__((ext_vector_type(4)));
-
-constexpr int RS_BLOCK = 256;          // 4 waves
-constexpr int RS_WAVES = RS_BLOCK / 64;
-constexpr int RS_REPS = 16;            // replicates per wave (MFMA M)
-// f tile of one wave: u8 counts, layout [sample slot 0..1023][rep 0..15] (16 KiB).
-// A draw of slot `off` for replicate rr is one ds_add_u32 of (1 << 8*(rr&3)) at byte
-// off*16 + (rr & ~3): one shift-add of VALU work per draw.  The contraction reads
-// one byte per step (ds_read_u8, immediate offset): no VALU unpacking.
-// On gfx950 the FP64 MFMA shares the VALU datapath (tools/mfma_f64_peak4.hip:
-// every VALU instruction costs 4.5-8 cycles of matrix-pipe time), so the design
-// rule of this kernel is: as few VALU instructions per MFMA as possible.
-constexpr int RS_QUARTER = SM_T / 4;                  // 256 samples per lane-group per tile
-constexpr int RS_TILE_BYTES = SM_T * RS_REPS;         // 16384 bytes per wave
-// steps per register-prefetch group: as many as the VGPR budget (2 waves/SIMD,
-// 256 VGPRs) allows next to the K*NBLK accumulator tiles.
-constexpr int RS_EXP_BUDGET = 160;
-constexpr int rs_group(int K, int NBLK, bool weighted, bool explicit_, int pack = 1) {
-  const int per_step = 2 + 2 * NBLK + (weighted ? 2 : 0) + (explicit_ ? 10 : 0);
-  for (int g = 8; g > 2; g >>= 1)
-    if ((K + pack - 1) / pack * NBLK * 8 + 2 * g * per_step <= RS_EXP_BUDGET) return g;
-  return 2;
-}
-
-struct ResampleArgs {
-  const double *x;
-  int64_t ldx_s;
-  const double *u;
-  const double *w;
-  int64_t N;
-  int64_t C;
-  int64_t nrep;
-  const int64_t *freq;      // parity mode
-  const uint32_t *counts;   // scale mode: [nrep][ntiles]
-  uint32_t k0, k1;          // philox key
-  uint32_t rep_base;        // replicate r of the call draws stream replicate rep_base + r (txm_sampler_spec.rep0)
-  int64_t ntiles;
-  uint32_t last_tile_size;
-  const double *pivot;      // [1 + C]
-  double *part_x;           // [n_chunks][nrep_pad][C_pad][K]
-  double *part_u;           // [n_chunks][nrep_pad][K]
-  int n_chunks;             // multiple of 8
-  int n_rbg;                // replicate-block groups (4 blocks of 16 reps each)
-  int64_t tiles_per_chunk;
-  int64_t nrep_pad;         // n_rbg * 64
-  int64_t C_pad;            // col groups * NBLK * 16
-  // listed mode (precision-guard fallback of the int8 path): chunk c contracts the runs list[c], list[c + n_chunks], ...
-  // of sub_tiles tiles each instead of its contiguous share; n_list[0] = number of runs (0: the launch is a no-op)
-  const uint32_t *list;
-  const uint32_t *n_list;
-  int sub_tiles;
-  int64_t col_off;          // x already points at the column group; its pivots start at pivot[1 + col_off]
-  // batched mode (txm_resample_vals_batched): blockIdx.z = state s of S state points of one shape.  x/u/w come
-  // from batch[s]; pivot, the partial sums, counts / freq rows and the sampler's replicate ids are those of the
-  // single-state layout shifted by s (replicate s * nrep + r of one sampler over S * nrep replicates)
-  const txm_state_ptrs *batch;
-  // listed mode of a BATCHED int8 call: the fallback runs of state blockIdx.z, operands from the int8 path's state table
-  const I8State *i8states = nullptr;
-  // L2-sharing hint (nullptr: off).  The waves that contract one sample chunk -- 4 per workgroup x the replicate
-  // groups of the chunk, placed on one XCD by the block map -- read the same samples; left alone they drift apart
-  // by many tiles and every one of them streams the chunk from HBM again (measured: 19x the algorithmic bytes).
-  // Each wave publishes the number of tiles it has finished in progress[group][slot] and, before the next tile,
-  // sleeps (bounded) while it is more than RS_LEAD tiles ahead of the slowest STARTED, UNFINISHED wave of its
-  // group.  Purely a performance hint: every wait is bounded and no result depends on it.
-  uint32_t *progress;       // [groups = n_chunks * colgroups (* S)][64], zeroed by the launcher
-};
-constexpr uint32_t RS_LEAD = 1;          // tiles a wave may run ahead of its group
-constexpr int RS_THROTTLE_SPINS = 48;    // x ~0.3 us: bound of one wait
-
-// One wave: 16 replicates x (NBLK*16 columns) x one chunk of tiles.
-//
-// MFMA operand roles for step s of a tile (lane = (row = lane & 15, kk = lane >> 4)):
-//   sample    i  = tile_base + kk * 256 + s          (each kk owns a contiguous quarter)
-//   A (rep = row, k = kk)   = f[rep][i] * w_i * du_i^j
-//   B (k = kk,  col = row)  = x[i][col] - px[col]
-// A lane therefore walks CONTIGUOUS samples: u/w/freq come as 16-byte loads of
-// 8 consecutive steps, f as one 8-byte LDS read per 8 steps, and the loads of
-// group g+1 are issued before the 8*K*NBLK MFMAs of group g (register double
-// buffer), so HBM/L2 latency hides under the matrix pipe.
-// Stage 3 of the sampler for a FULL tile and the 16 replicates of one wave, with the
-// minimum of VALU work (the stream itself is the one oracle/philox_oracle.c defines:
-// draw d of (r, t) = 10-bit field d % 12 of Philox call d / 12 -- which lane runs a
-// call is free).  Replicates are taken in pairs: calls 0..63 of each go to one wave
-// iteration each, and their remaining calls 64..95 (n - 768 draws, ~1/3 of a wave)
-// share a third iteration, 32 lanes per replicate.  Fields past the replicate's
-// draw count add 0 instead of being branched around.
-template <bool ALL_VALID>
-__device__ __forceinline__ void tile_calls(uint32_t *tw, uint32_t k0, uint32_t k1, uint32_t r, uint32_t t,
-                                           uint32_t c, uint32_t n, uint32_t inc, uint32_t wsel) {
-  const uint32_t first = c * 12u;
-  if (!ALL_VALID && first >= n) return;  // ALL_VALID: 12 (c + 1) <= n by construction, no branch
-  // call index in the second counter word: the tile's and the replicate's share of rounds 1-3 is wave-uniform
-  const Philox4 o = philox4x32_10(t, c, r, 3u, k0, k1);
-  const uint32_t nd = n - first;
-#pragma unroll
-  for (int wi = 0; wi < 4; ++wi) {
-    const uint32_t word = o.w[wi];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const uint32_t f = (word >> (10 * k)) & 1023u;
-      const uint32_t add = ALL_VALID ? inc : (((uint32_t)(wi * 3 + k) < nd) ? inc : 0u);
-      atomicAdd(&tw[f * (RS_REPS / 4) + wsel], add);
-    }
-  }
-}
-
-__device__ __forceinline__ void fill_tile_full(const ResampleArgs &a, const uint32_t *counts, uint32_t rid0,
-                                               uint32_t *tw, int64_t rep0, int64_t t, int lane) {
-#pragma unroll 1
-  for (int p = 0; p < RS_REPS / 2; ++p) {
-    const int64_t ra = rep0 + 2 * p, rb = ra + 1;
-    if (ra >= a.nrep) break;  // wave-uniform
-    const uint32_t na = counts[(size_t)ra * a.ntiles + t];
-    const uint32_t nb = rb < a.nrep ? counts[(size_t)rb * a.ntiles + t] : 0u;
-    const uint32_t wsel = (uint32_t)p >> 1;                  // (2p) >> 2 == (2p+1) >> 2
-    const uint32_t inc_a = 1u << (8u * ((2u * p) & 3u)), inc_b = inc_a << 8;
-    // iterations 1 and 2: calls 0..63 of each replicate; when n >= 768 (wave-uniform,
-    // practically always) every field is a real draw and no select is needed
-    if (na >= 768u) tile_calls<true>(tw, a.k0, a.k1, rid0 + (uint32_t)ra, (uint32_t)t, (uint32_t)lane, na, inc_a, wsel);
-    else tile_calls<false>(tw, a.k0, a.k1, rid0 + (uint32_t)ra, (uint32_t)t, (uint32_t)lane, na, inc_a, wsel);
-    if (nb >= 768u) tile_calls<true>(tw, a.k0, a.k1, rid0 + (uint32_t)rb, (uint32_t)t, (uint32_t)lane, nb, inc_b, wsel);
-    else tile_calls<false>(tw, a.k0, a.k1, rid0 + (uint32_t)rb, (uint32_t)t, (uint32_t)lane, nb, inc_b, wsel);
-    // iteration 3: calls 64..95 of both, 32 lanes each
-    const bool hb = lane >= 32;
-    tile_calls<false>(tw, a.k0, a.k1, rid0 + (uint32_t)(hb ? rb : ra), (uint32_t)t, 64u + ((uint32_t)lane & 31u),
-                      hb ? nb : na, hb ? inc_b : inc_a, wsel);
-    // calls >= 96 (n > 1152, a > 4 sigma event): plain loop
-    const uint32_t nmax = na > nb ? na : nb;
-    for (uint32_t c0 = 96u; c0 * 12u < nmax; c0 += 64u) {
-      tile_calls<false>(tw, a.k0, a.k1, rid0 + (uint32_t)ra, (uint32_t)t, c0 + (uint32_t)lane, na, inc_a, wsel);
-      tile_calls<false>(tw, a.k0, a.k1, rid0 + (uint32_t)rb, (uint32_t)t, c0 + (uint32_t)lane, nb, inc_b, wsel);
-    }
-  }
-}
-
-//
-// Tiles are always contracted over a full 1024-sample window.  The last
-// (partial) tile slides its window back to [N - 1024, N) and gives the samples
-// that belong to the previous tile a zero count, so the hot loop has no
-// bounds handling at all.  Only data sets shorter than one tile (SMALLN) use
-// clamped addresses, in a separate instantiation.
-// MODE: RS_PLAIN = one state point, contiguous chunk of tiles; RS_LISTED = the runs of the fallback list;
-// RS_BATCHED = state blockIdx.z of a batch.  Compile-time so that the plain kernel carries none of the other modes'
-// loop state (scalar registers are what this kernel runs out of first: spilled SGPRs cost vector instructions,
-// and every vector instruction here costs FP64-MFMA time).
-constexpr int RS_PLAIN = 0, RS_LISTED = 1, RS_BATCHED = 2;
-//
-// PACK (1, 2 or 4; NBLK == 1): with C <= 16 / PACK value columns the 16 B-operand columns carry PACK powers of du
-// per column, B[k][jp * CPK + c] = dx_c * du^jp, and the A operands step by du^PACK: ceil(K / PACK) MFMAs per
-// k-step instead of K, so a narrow state does not pay for 16 columns it does not have.
-template <int K, int NBLK, bool WEIGHTED, bool EXPLICIT, bool SMALLN, int MODE = RS_PLAIN, int PACK = 1>
-__global__ __launch_bounds__(RS_BLOCK, 2) void resample_kernel(const ResampleArgs a) {
-  static_assert(PACK == 1 || (NBLK == 1 && (PACK == 2 || PACK == 4)), "power packing needs a single column block");
-  constexpr int CPK = 16 / PACK;            // value columns per power slot
-  constexpr int KJ = (K + PACK - 1) / PACK;  // accumulator tiles (MFMAs per k-step and column block)
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  // readfirstlane: tell the compiler the wave index is wave-uniform, so everything
-  // derived from it (replicate base, LDS tile base, loop bounds) lives in SGPRs
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  const int row = lane & 15;   // A: replicate within block;  B: column within block
-  const int kk = lane >> 4;    // which quarter of the tile this lane group walks
-  const int crow = PACK == 1 ? row : row % CPK;  // B: value column within the block
-  const int jp = PACK == 1 ? 0 : row / CPK;      // B: power of du folded into this lane's column
-
-  // XCD-aware task map: workgroups that share a sample chunk sit on one XCD
-  // (blocks b and b+8 share an XCD) and are dispatched back to back, so the
-  // chunk is streamed from HBM once and re-read from that XCD's L2.
-  const int b = blockIdx.x;
-  const int xcd = b & 7, q = b >> 3;
-  const int chunk = (q / a.n_rbg) * 8 + xcd;
-  const int rbg = q % a.n_rbg;
-  const int colgrp = blockIdx.y;
-  const int64_t rep0 = ((int64_t)rbg * RS_WAVES + wave) * RS_REPS;
-  const int64_t col0 = (int64_t)colgrp * (NBLK * 16);
-
-  const int64_t t_begin = (int64_t)chunk * a.tiles_per_chunk;
-  int64_t t_end = t_begin + a.tiles_per_chunk;
-  if (t_end > a.ntiles) t_end = a.ntiles;
-  // operands of this launch's state (batched mode: state blockIdx.z)
-  const double *X = a.x, *U = a.u, *W = a.w, *PIV = a.pivot;
-  const uint32_t *CNT = a.counts;
-  const int64_t *FREQ = a.freq;
-  double *PX = a.part_x, *PU = a.part_u;
-  uint32_t rid0 = a.rep_base;
-  if constexpr (MODE == RS_BATCHED) {
-    const int64_t sidx = blockIdx.z;
-    const txm_state_ptrs bs = a.batch[sidx];
-    X = bs.x;
-    U = bs.u;
-    W = bs.w;
-    PIV += sidx * (1 + a.C);
-    if (CNT) CNT += (size_t)sidx * a.nrep * a.ntiles;
-    if (FREQ) FREQ += (size_t)sidx * a.nrep * a.N;
-    PX += (size_t)sidx * a.n_chunks * a.nrep_pad * a.C_pad * K;
-    PU += (size_t)sidx * a.n_chunks * a.nrep_pad * K;
-    rid0 += (uint32_t)(sidx * a.nrep);
-  }
-  constexpr bool listed = MODE == RS_LISTED;
-  int64_t nruns = 1;
-  const uint32_t *LIST = a.list, *NLIST = a.n_list;
-  if constexpr (listed) {
-    if (a.i8states != nullptr) {  // batched int8 call: state blockIdx.z
-      const I8State e = a.i8states[blockIdx.z];
-      X = e.x + a.col_off;  // (a.x of a listed launch is x + the column group's offset)
-      U = e.u;
-      W = e.w;
-      PIV = e.pivot;
-      CNT = e.counts;
-      PX = e.fb_x;
-      PU = e.fb_u;
-      rid0 = e.rep_base;
-      LIST = e.list;
-      NLIST = e.n_list;
-    }
-    nruns = (int64_t)*NLIST;
-    if (nruns == 0) return;  // nothing flagged: the finalize kernel does not read this launch's partial sums
-  }
-
-  const double pu = PIV[0];
-  // Columns beyond C (padding of the last 16-column block) re-read column 0:
-  // their sums are finite garbage that the finalize kernel never looks at, which
-  // is cheaper than a mask multiply on the FP64 pipe the MFMAs need.
-  double px[NBLK];
-  int64_t ccol[NBLK];
-#pragma unroll
-  for (int bl = 0; bl < NBLK; ++bl) {
-    const int64_t c = col0 + bl * 16 + crow;
-    ccol[bl] = c < a.C ? c : 0;
-    px[bl] = PIV[1 + a.col_off + ccol[bl]];
-  }
-
-  v4f64 acc[KJ][NBLK];
-  double usum[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) usum[j] = 0.0;
-#pragma unroll
-  for (int j = 0; j < KJ; ++j)
-#pragma unroll
-    for (int bl = 0; bl < NBLK; ++bl) acc[j][bl] = (v4f64){0.0, 0.0, 0.0, 0.0};
-
-  unsigned char *tile = lds_raw + (size_t)wave * RS_TILE_BYTES;
-  const int64_t my_rep = rep0 + row;
-  const bool rep_ok = my_rep < a.nrep;
-  const int64_t last = a.N - 1;
-
-  // register double buffer for one group of RS_GROUP steps
-  constexpr int RS_GROUP = SMALLN ? 2 : rs_group(K, NBLK, WEIGHTED, EXPLICIT, PACK);
-  struct Grp {
-    double u[RS_GROUP];
-    double w[RS_GROUP];
-    double x[RS_GROUP][NBLK];
-    uint32_t fb[RS_GROUP];    // scale mode: u8 counts straight from LDS, one per step
-    int64_t fi[EXPLICIT ? RS_GROUP : 1];  // parity mode: raw int64 counts
-  };
-
-  uint32_t *pg = nullptr;
-  uint32_t tiles_done = 0;
-  const int pslot = (rbg * RS_WAVES + wave) & 63;
-  if constexpr (MODE == RS_PLAIN && !SMALLN)
-    if (a.progress != nullptr) pg = a.progress + ((size_t)(colgrp * a.n_chunks + chunk)) * 64;
-  double cnt = 0.0;  // lanes kk == 0, unweighted: the replicate's draws in the contracted tiles (exact integers)
-  for (int64_t run = listed ? chunk : 0; run < nruns; run += listed ? a.n_chunks : 1) {
-  int64_t tb = t_begin, te = t_end;
-  if constexpr (listed) {
-    tb = (int64_t)LIST[run];
-    te = tb + a.sub_tiles;
-    if (te > a.ntiles) te = a.ntiles;
-  }
-  for (int64_t t = tb; t < te; ++t) {
-    const int64_t i_tile = t * SM_T;
-    if constexpr (!WEIGHTED && !EXPLICIT)
-      if (kk == 0 && rep_ok) cnt += (double)CNT[(size_t)my_rep * a.ntiles + t];
-    const uint32_t tsize = (t == a.ntiles - 1) ? a.last_tile_size : (uint32_t)SM_T;
-    // window of 1024 samples that is contracted for this tile
-    int64_t wbase = i_tile;
-    if constexpr (!SMALLN)
-      if (wbase > a.N - SM_T) wbase = a.N - SM_T;
-    const uint32_t shift = (uint32_t)(i_tile - wbase);  // window slots owned by the previous tile
-
-    if constexpr (!EXPLICIT) {
-      // ---- stage 3 of the sampler: fill this wave's private f tile ---------
-      // (wave-private LDS: DS ops of one wave execute in order, so only the
-      // compiler needs fencing -- no s_barrier, waves of a workgroup drift
-      // apart and their VALU/LDS phases overlap other waves' MFMA phases)
-      uint4 *z = reinterpret_cast<uint4 *>(tile);
-#pragma unroll
-      for (int e = 0; e < RS_TILE_BYTES / 16 / 64; ++e) z[e * 64 + lane] = make_uint4(0, 0, 0, 0);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      uint32_t *tw = reinterpret_cast<uint32_t *>(tile);
-      if (tsize == (uint32_t)SM_T) {
-        fill_tile_full(a, CNT, rid0, tw, rep0, t, lane);
-      } else {
-        for (int rr = 0; rr < RS_REPS; ++rr) {
-          const int64_t r = rep0 + rr;
-          if (r >= a.nrep) break;  // wave-uniform
-          const uint32_t n = CNT[(size_t)r * a.ntiles + t];
-          sampler_fine_tile(a.k0, a.k1, rid0 + (uint32_t)r, (uint32_t)t, n, tsize, lane, [&](uint32_t off0) {
-            const uint32_t off = off0 + shift;
-            atomicAdd(&tw[off * (RS_REPS / 4) + ((uint32_t)rr >> 2)], 1u << (8u * ((uint32_t)rr & 3u)));
-          });
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-    }
-
-    const unsigned char *frow = tile + (kk * RS_QUARTER) * RS_REPS + row;  // + s * 16 per step
-    const int64_t ibase = wbase + (int64_t)kk * RS_QUARTER;
-    const uint32_t lbase = (uint32_t)kk * RS_QUARTER;  // window slot of this lane's step 0
-    // unsigned 32-bit BYTE offsets: base (SGPR pair) + zext(VGPR) is the saddr form of global_load
-    const uint32_t lane_uoff = (uint32_t)(kk * RS_QUARTER) * 8u;
-    uint32_t lane_xoff[NBLK];
-#pragma unroll
-    for (int bl = 0; bl < NBLK; ++bl) lane_xoff[bl] = (uint32_t)((kk * RS_QUARTER * a.ldx_s + ccol[bl]) * 8);
-    auto ld = [](const void *base, uint32_t byteoff) {
-      return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + byteoff);
-    };
-
-    // One-step operand lookahead: the A operands (f * w * du^j) and B operands
-    // (x - px) of step e+1 are computed into a second register set BEFORE the
-    // K*NBLK MFMAs of step e are issued, so the MFMAs of a step go out back to back
-    // and no VALU write targets a register an in-flight MFMA still reads.
-    struct Ops {
-      double a[KJ];
-      double b[NBLK];
-    };
-    auto prep_step = [&](const Grp &G, int e, Ops &o) {
-      double av;
-      if constexpr (EXPLICIT) av = (double)G.fi[e];
-      else av = (double)G.fb[e];
-      if constexpr (WEIGHTED) av *= G.w[e];
-      const double du = G.u[e] - pu;
-#pragma unroll
-      for (int bl = 0; bl < NBLK; ++bl) o.b[bl] = G.x[e][bl] - px[bl];
-      if constexpr (PACK > 1) {
-        double f = (jp & 1) ? du : 1.0;
-        if constexpr (PACK == 4) f *= (jp & 2) ? du * du : 1.0;
-        o.b[0] *= f;
-      }
-#pragma unroll
-      for (int j = 0; j < K; ++j) {
-        if (j % PACK == 0) o.a[j / PACK] = av;
-        // S0[0] = sum of counts: accumulated only when weights make it non-trivial
-        // (unweighted it is the replicate's draw count, summed from `counts` below)
-        if (j > 0 || WEIGHTED || EXPLICIT) usum[j] += av;
-        av *= du;
-      }
-    };
-    auto mfma_step = [&](const Ops &o) {
-#pragma unroll
-      for (int j = 0; j < KJ; ++j)
-#pragma unroll
-        for (int bl = 0; bl < NBLK; ++bl)
-          acc[j][bl] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[j], o.b[bl], acc[j][bl], 0, 0, 0);
-    };
-    auto compute_group = [&](const Grp &G) {
-      Ops P, Q;
-      prep_step(G, 0, P);
-#pragma unroll
-      for (int e = 0; e < RS_GROUP; e += 2) {
-        if (e + 1 < RS_GROUP) prep_step(G, e + 1, Q);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_step(P);
-        __builtin_amdgcn_sched_barrier(0);
-        if (e + 1 < RS_GROUP) {
-          if (e + 2 < RS_GROUP) prep_step(G, e + 2, P);
-          __builtin_amdgcn_sched_barrier(0);
-          mfma_step(Q);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    };
-
-    // Branch-free on purpose: a conditional around the prefetch loads makes the
-    // compiler's s_waitcnt insertion fall back to vmcnt(0) at the join, which
-    // serialises loads and MFMAs.
-    auto load_group = [&](int g, Grp &G) {
-      const int s0 = g * RS_GROUP;
-      if constexpr (!SMALLN) {
-        // wave-uniform row base (SGPRs, scalar ALU) + a loop-invariant 32-bit lane
-        // offset: the loads need no per-step vector address arithmetic
-        const double *ur = U + (wbase + s0);
-#pragma unroll
-        for (int e = 0; e < RS_GROUP; ++e) G.u[e] = ld(ur + e, lane_uoff);
-        if constexpr (WEIGHTED) {
-          const double *wr = W + (wbase + s0);
-#pragma unroll
-          for (int e = 0; e < RS_GROUP; ++e) G.w[e] = ld(wr + e, lane_uoff);
-        }
-#pragma unroll
-        for (int e = 0; e < RS_GROUP; ++e) {
-          const double *xr = X + (wbase + s0 + e) * a.ldx_s;
-#pragma unroll
-          for (int bl = 0; bl < NBLK; ++bl) G.x[e][bl] = ld(xr, lane_xoff[bl]);
-        }
-        if constexpr (EXPLICIT) {
-          const int64_t *fp = FREQ + (size_t)(rep_ok ? my_rep : 0) * a.N + ibase + s0;
-#pragma unroll
-          for (int e = 0; e < RS_GROUP; ++e)
-            G.fi[e] = (rep_ok && lbase + (uint32_t)(s0 + e) >= shift) ? fp[e] : 0;
-        }
-      } else {
-        // N < 1024: a single short tile; clamp addresses, zero the missing samples
-#pragma unroll
-        for (int e = 0; e < RS_GROUP; ++e) {
-          const int64_t ii = ibase + s0 + e;
-          const int64_t ic = ii <= last ? ii : last;
-          G.u[e] = U[ic];
-          if constexpr (WEIGHTED) G.w[e] = W[ic];
-#pragma unroll
-          for (int bl = 0; bl < NBLK; ++bl) G.x[e][bl] = X[ic * a.ldx_s + ccol[bl]];
-          if constexpr (EXPLICIT)
-            G.fi[e] = (rep_ok && ii <= last) ? FREQ[(size_t)(rep_ok ? my_rep : 0) * a.N + ic] : 0;
-        }
-      }
-      if constexpr (!EXPLICIT) {
-#pragma unroll
-        for (int e = 0; e < RS_GROUP; ++e) G.fb[e] = frow[(s0 + e) * RS_REPS];
-      }
-    };
-    // groups per lane quarter (even); SMALLN: only those that hold samples
-    int ngroups = RS_QUARTER / RS_GROUP;
-    if constexpr (SMALLN) {
-      const uint32_t q0 = tsize < (uint32_t)RS_QUARTER ? tsize : (uint32_t)RS_QUARTER;
-      ngroups = (int)((q0 + RS_GROUP - 1) / RS_GROUP);
-      ngroups = (ngroups + 1) & ~1;
-    }
-    {
-      Grp A, B;
-      load_group(0, A);
-      // sched_barrier: keep "issue the next group's loads, then run this group's
-      // MFMAs" in program order (the machine scheduler otherwise sinks the loads
-      // next to their uses to save registers and exposes their latency).
-      for (int g = 0; g < ngroups; g += 2) {
-        load_group(g + 1, B);  // g + 1 < ngroups (even count)
-        __builtin_amdgcn_sched_barrier(0);
-        compute_group(A);
-        __builtin_amdgcn_sched_barrier(0);
-        const int g2 = (g + 2 < ngroups) ? g + 2 : g + 1;  // tail: harmless re-load
-        load_group(g2, A);
-        __builtin_amdgcn_sched_barrier(0);
-        compute_group(B);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-
-    if constexpr (!EXPLICIT) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-    }
-    if (pg != nullptr) {  // kernel argument: uniform
-      ++tiles_done;
-      if (lane == 0) __hip_atomic_store(&pg[pslot], tiles_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll 1
-      for (int spin = 0; spin < RS_THROTTLE_SPINS; ++spin) {
-        uint32_t v = __hip_atomic_load(&pg[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v == 0u) v = 0xffffffffu;  // slot unused or its wave not started yet: not a wave to wait for
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const uint32_t w2 = (uint32_t)__shfl_xor((int)v, o);
-          v = w2 < v ? w2 : v;
-        }
-        if (tiles_done <= v + RS_LEAD) break;
-        __builtin_amdgcn_s_sleep(32);
-      }
-    }
-  }
-  }
-  if (pg != nullptr && lane == 0)  // finished: never hold the others back
-    __hip_atomic_store(&pg[pslot], 0xfffffff0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-
-  // ---- write partial sums ---------------------------------------------------
-  // D layout of v_mfma_f64_16x16x4_f64: col = lane & 15, row = (lane >> 4) + 4 * reg
-  double *px_out = PX + ((size_t)chunk * a.nrep_pad + rep0) * a.C_pad * K;
-#pragma unroll
-  for (int jj = 0; jj < KJ; ++jj)
-#pragma unroll
-    for (int bl = 0; bl < NBLK; ++bl)
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int rrow = kk + 4 * rg;
-        const int64_t c = col0 + bl * 16 + crow;
-        const int j = jj * PACK + jp;
-        if (PACK == 1 || j < K) px_out[((size_t)rrow * a.C_pad + c) * K + j] = acc[jj][bl][rg];
-      }
-  if (colgrp == 0) {
-    if constexpr (!WEIGHTED && !EXPLICIT) usum[0] = cnt;  // other lane groups contribute 0
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      double v = usum[j];
-      v += __shfl_xor(v, 16);
-      v += __shfl_xor(v, 32);
-      if (kk == 0) PU[((size_t)chunk * a.nrep_pad + rep0 + row) * K + j] = v;
-    }
-  }
-}
-
-// finalize: thread per (rep, col): fixed-order sum over chunks, shift to the
-// cmomy state, out[rep][c][2][K].
-template <int K>
-__global__ __launch_bounds__(256) void resample_finalize_kernel(
-    const double *__restrict__ part_x, const double *__restrict__ part_u, int n_chunks,
-    int64_t nrep_pad, int64_t C_pad, int64_t nrep, int64_t C, const double *__restrict__ pivot,
-    double *__restrict__ out, int64_t c_off = 0, int64_t C_total = 0) {
-  // C columns of this launch are the columns c_off .. c_off + C - 1 of the C_total output columns.
-  // Thread = (output e of the block's 32, chunk segment seg of 8): segment seg adds the chunks seg, seg + 8, ... in
-  // ascending order, then the eight segments are added in order -- a fixed tree (one thread per output walking all
-  // chunks was a chain of dependent-latency loads: 0.3 ms for 400 outputs x 1024 chunks).
-  constexpr int NSEG = 8, NOUT = 256 / NSEG;
-  __shared__ double sh[NSEG][NOUT][2 * K];
-  const int eo = threadIdx.x % NOUT, seg = threadIdx.x / NOUT;
-  const int64_t e = (int64_t)blockIdx.x * NOUT + eo;
-  const bool live = e < nrep * C;
-  const int64_t r = live ? e / C : 0, c = live ? e % C : 0;
-  if (C_total == 0) C_total = C;
-  // batched mode: blockIdx.y = state; every per-state array follows the previous state's
-  const int64_t sidx = blockIdx.y;
-  part_x += (size_t)sidx * n_chunks * nrep_pad * C_pad * K;
-  part_u += (size_t)sidx * n_chunks * nrep_pad * K;
-  pivot += sidx * (1 + C);
-  out += (size_t)sidx * nrep * C_total * 2 * K;
-  double S0[K], S1[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) S0[j] = S1[j] = 0.0;
-  if (live)
-    for (int ch = seg; ch < n_chunks; ch += NSEG) {
-      const double *pu_ = part_u + ((size_t)ch * nrep_pad + r) * K;
-      const double *px_ = part_x + (((size_t)ch * nrep_pad + r) * C_pad + c) * K;
-#pragma unroll
-      for (int j = 0; j < K; ++j) {
-        S0[j] += pu_[j];
-        S1[j] += px_[j];
-      }
-    }
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    sh[seg][eo][j] = S0[j];
-    sh[seg][eo][K + j] = S1[j];
-  }
-  __syncthreads();
-  if (seg != 0 || !live) return;
-  for (int g = 1; g < NSEG; ++g)
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      S0[j] += sh[g][eo][j];
-      S1[j] += sh[g][eo][K + j];
-    }
-  double st[2 * K];
-  pivot_sums_to_state_or_empty<K>(S0, S1, pivot[0], pivot[1 + c_off + c], st);  // weight sum exactly 0: the empty state
-  double *o = out + (r * C_total + c_off + c) * 2 * K;
-#pragma unroll
-  for (int q = 0; q < 2 * K; ++q) o[q] = st[q];
-}
-
-// finalize of the int8 path: one slot of partial sums per scaling window, [window][replicate][power][8 digit slots]
-// [column] (u-row: [window][replicate][power][8]); windows in ascending order, digits in ascending order -- a fixed order
-// that does not depend on the launch geometry.  Windows the precision guard flagged hold nothing: they were contracted
-// by the FP64 kernel, whose sums are added behind (same pivot).
-template <int K, int CPAD>
-__global__ __launch_bounds__(256) void resample_finalize_i8_kernel(
-    const double *__restrict__ part_x, const double *__restrict__ part_u, int64_t nwin,
-    const uint32_t *__restrict__ wflag, int64_t nrep_pad, int64_t nrep, int64_t C,
-    const double *__restrict__ pivot, double *__restrict__ out, int64_t c_off, int64_t C_total,
-    const double *__restrict__ fb_x, const double *__restrict__ fb_u, int fb_chunks, int64_t fb_cpad,
-    const uint32_t *__restrict__ n_list, const I8State *__restrict__ states = nullptr, const int summed = 0) {
-  // summed != 0: the x slots hold the digit sums already -- [window][replicate][power][column] -- written by the narrow kernels and
-  // resample_i8g_kernel with the expression below; summed == 1: the u slots too ([window][replicate][power])
-  if (states != nullptr) {  // batched int8 call: state blockIdx.y
-    const I8State e = states[blockIdx.y];
-    part_x = e.part_x; part_u = e.part_u; wflag = e.wflag; pivot = e.pivot; out = e.out;
-    fb_x = e.fb_x; fb_u = e.fb_u; n_list = e.n_list;
-  }
-  // CPAD = columns of a row of part_x (32; 4, 8 or 16 where the narrow-state kernel wrote it)
-  constexpr int cpad = CPAD;
-  // one workgroup per replicate: thread = (column c < cpad, window segment seg of 256 / cpad).  Segment seg adds the
-  // windows seg, seg + nseg, ... in ascending order, then the segments are added in order: a fixed tree that depends on
-  // the number of windows (i.e. on N) and on the state's width only, not on the launch geometry.  (One thread per output
-  // walking all windows was latency-bound on short series with few outputs: 1600 threads x 611 windows at BASELINE
-  // config 2; so were 8 segments for an 8-column state.)
-  __shared__ double sh[256][2 * K];
-  constexpr int nseg = 256 / cpad;
-  const int64_t r = blockIdx.x;
-  const int c = threadIdx.x % cpad, seg = threadIdx.x / cpad;
-  double S0[K], S1[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) S0[j] = S1[j] = 0.0;
-  if (c < C) {
-    for (int64_t w = seg; w < nwin; w += nseg) {
-      if (wflag[w] != 0u) continue;
-      if (summed) {  // (uniform) 1: x and u slots digit-summed; 2: x summed, u per digit (resample_i8g_kernel: its u-row digits ride
-        // in other waves' columns)
-        const double *px_ = part_x + ((size_t)w * nrep_pad + r) * K * cpad + c;
-        if (summed == 1) {
-          const double *pu_ = part_u + ((size_t)w * nrep_pad + r) * K;
-#pragma unroll
-          for (int j = 0; j < K; ++j) {
-            S0[j] += pu_[j];
-            S1[j] += px_[j * cpad];
-          }
-        } else {
-          const double *pu_ = part_u + ((size_t)w * nrep_pad + r) * K * 8;
-#pragma unroll
-          for (int j = 0; j < K; ++j) {
-            const double4 ua = *reinterpret_cast<const double4 *>(pu_ + j * 8), ub = *reinterpret_cast<const double4 *>(pu_ + j * 8 + 4);
-            S0[j] += ((((((ua.x + ua.y) + ua.z) + ua.w) + ub.x) + ub.y) + ub.z);  // digit slots 0..6, ascending
-            S1[j] += px_[j * cpad];
-          }
-        }
-        continue;
-      }
-      const double *pu_ = part_u + ((size_t)w * nrep_pad + r) * K * 8;
-      const double *px_ = part_x + ((size_t)w * nrep_pad + r) * K * 8 * cpad + c;
-#pragma unroll
-      for (int j = 0; j < K; ++j) {
-        const double4 ua = *reinterpret_cast<const double4 *>(pu_ + j * 8), ub = *reinterpret_cast<const double4 *>(pu_ + j * 8 + 4);
-        const double *q = px_ + (size_t)j * 8 * cpad;
-        S0[j] += ((((((ua.x + ua.y) + ua.z) + ua.w) + ub.x) + ub.y) + ub.z);  // digit slots 0..6, ascending
-        S1[j] += ((((((q[0] + q[cpad]) + q[2 * cpad]) + q[3 * cpad]) + q[4 * cpad]) + q[5 * cpad]) + q[6 * cpad]);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    sh[threadIdx.x][j] = S0[j];
-    sh[threadIdx.x][K + j] = S1[j];
-  }
-  __syncthreads();
-  if (seg != 0 || c >= C) return;
-  for (int g = 1; g < nseg; ++g)
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      S0[j] += sh[g * cpad + c][j];
-      S1[j] += sh[g * cpad + c][K + j];
-    }
-  // windows the precision guard handed to the FP64 kernel (same pivot: the sums simply add)
-  if (n_list[0] != 0u)
-    for (int ch = 0; ch < fb_chunks; ++ch) {
-      const double *pu_ = fb_u + ((size_t)ch * nrep_pad + r) * K;
-      const double *px_ = fb_x + (((size_t)ch * nrep_pad + r) * fb_cpad + c) * K;
-#pragma unroll
-      for (int j = 0; j < K; ++j) {
-        S0[j] += pu_[j];
-        S1[j] += px_[j];
-      }
-    }
-  double st[2 * K];
-  pivot_sums_to_state_or_empty<K>(S0, S1, pivot[0], pivot[1 + c_off + c], st);  // weight sum exactly 0: the empty state
-  double *o = out + (r * C_total + c_off + c) * 2 * K;
-#pragma unroll
-  for (int q = 0; q < 2 * K; ++q) o[q] = st[q];
-  (void)nrep;
-}
-
-// the second sample matrix: per-replicate weighted means  out_y[r][c] = py[c] + S1y / S0  from the per-window slots
-// written by the y row set (same fixed tree as above), the sum of weights S0 from the u-row slots (power 0)
-__global__ __launch_bounds__(256) void resample_finalize_y_kernel(
-    const double *__restrict__ part_y, const double *__restrict__ part_u, int K, int64_t nwin,
-    const uint32_t *__restrict__ wflag, int64_t nrep_pad, int64_t C, const double *__restrict__ ypivot,
-    double *__restrict__ out_y, int64_t c_off, int64_t C_total, const double *__restrict__ fb_y,
-    const double *__restrict__ fb_u, int fb_chunks, int64_t fb_cpad, const uint32_t *__restrict__ n_list) {
-  constexpr int NSEG = 8;
-  __shared__ double sh[NSEG][32][2];
-  const int64_t r = blockIdx.x;
-  const int c = threadIdx.x & 31, seg = threadIdx.x >> 5;
-  double S0 = 0.0, S1 = 0.0;
-  if (c < C) {
-    for (int64_t w = seg; w < nwin; w += NSEG) {
-      if (wflag[w] != 0u) continue;
-      const double *pu_ = part_u + ((size_t)w * nrep_pad + r) * K * 8;
-      const double *q = part_y + ((size_t)w * nrep_pad + r) * 8 * I8_CPAD + c;
-      const double4 ua = *reinterpret_cast<const double4 *>(pu_), ub = *reinterpret_cast<const double4 *>(pu_ + 4);
-      S0 += ((((((ua.x + ua.y) + ua.z) + ua.w) + ub.x) + ub.y) + ub.z);
-      S1 += ((((((q[0] + q[I8_CPAD]) + q[2 * I8_CPAD]) + q[3 * I8_CPAD]) + q[4 * I8_CPAD]) + q[5 * I8_CPAD]) + q[6 * I8_CPAD]);
-    }
-  }
-  sh[seg][c][0] = S0;
-  sh[seg][c][1] = S1;
-  __syncthreads();
-  if (seg != 0 || c >= C) return;
-  S0 = sh[0][c][0];
-  S1 = sh[0][c][1];
-  for (int g = 1; g < NSEG; ++g) {
-    S0 += sh[g][c][0];
-    S1 += sh[g][c][1];
-  }
-  if (n_list[0] != 0u)
-    for (int ch = 0; ch < fb_chunks; ++ch) {
-      S0 += fb_u[((size_t)ch * nrep_pad + r) * K];
-      S1 += fb_y[((size_t)ch * nrep_pad + r) * fb_cpad + c];
-    }
-  // as pivot_sums_to_state forms a mean; a replicate of weight sum exactly 0 has no mean: 0, as in the empty state
-  out_y[r * C_total + c_off + c] = S0 == 0.0 ? 0.0 : ypivot[1 + c_off + c] + S1 * (1.0 / S0);
-}
-
-struct ResamplePlan {
-  int nblk, colgroups, n_rbg, n_chunks;
-  int64_t tiles_per_chunk, nrep_pad, C_pad, ntiles;
-  size_t off_pivot, off_px, off_pu, off_prog, prog_bytes, total;
-};
 
 // tiles per sample chunk: ntiles / div chunks, at least 8 and at most 1024 of them (rounded to octets by the callers)
 static int64_t resample_chunk_tiles(int64_t ntiles, int64_t div) {
@@ -768,15 +47,23 @@ static ResamplePlan plan_resample(int64_t N, int64_t C, int64_t nrep, int K) {
   return p;
 }
 
+// What one state point of the int8 path owns, as offsets: its four pre-pass tables (p_*, inside a pre-pass block: the
+// workspace's or the caller's) and its scratch block (s_*, inside the workspace).  A single call has one such pair per
+// call (its column groups share the scratch and have a set of tables each), a batched call one per state.
+struct I8StateLayout {
+  size_t stride, s_px, s_pu, s_fbx, s_fbu, s_stats;     // a state's scratch block in the workspace
+  size_t p_stride, p_wt, p_flag, p_list, p_nlist;       // a state's pre-pass block (workspace, or the caller's prep buffer)
+};
+
 // int8-sliced path (txm_resample_i8.hip): 64 replicates x all columns per workgroup,
 // chunks of whole scaling windows, one workgroup per CU.
 struct I8Plan {
   int n_rbg, n_chunks, ngroups;
   int64_t tiles_per_chunk, nrep_pad, ntiles, nwin, win_tiles;
-  size_t off_px, off_pu, total;
+  size_t total;
   // precision-guard fallback: the FP64 kernel's plan / partial sums for one column group
   int sub_tiles;
-  size_t off_fbx, off_fbu, off_prog, prog_bytes, off_stats, off_prep;
+  size_t off_prog, prog_bytes, off_prep;
   // the per-sample count table of the call's replicates (txm_count_table.hip; wide states: the contraction kernel without a
   // sampler inside, txm_resample_i8g.hip) -- 0 bytes for shapes that never take that kernel
   size_t off_table, table_bytes, off_gprog, total_table;  // (+ sixteen progress words per window: the L2-sharing hint of that kernel)
@@ -785,9 +72,31 @@ struct I8Plan {
   size_t off_py, off_fby, prep_ypiv, prep_ywt, prep_yflag;
   // the pre-pass block ("prep": what depends on the data and the shape, not on the sampler):
   //   [pivot (1 + C)] then per 32-column group [window table | guard flags | fallback run list | n_list (256 B)]
-  size_t prep_wt, prep_flag, prep_list, prep_nlist, prep_group0, prep_group_stride, prep_total;
+  size_t prep_group0, prep_group_stride, prep_total;
+  I8StateLayout L;  // the tables of one group (p_*) and the call's scratch (s_*, rows of I8_CPAD columns) at the head of the workspace
   ResamplePlan fb;
 };
+
+// window table | guard flags | fallback run list | n_list (256 B); p_stride = their end
+static void i8_layout_tables(const I8Plan &p, I8StateLayout &L) {
+  L.p_wt = 0;
+  L.p_flag = L.p_wt + align_up((size_t)p.nwin * I8_WT_STRIDE * sizeof(double) + 2048, 256);  // + timing slots of debug builds
+  L.p_list = L.p_flag + align_up((size_t)p.nwin * sizeof(uint32_t), 256);
+  L.p_nlist = L.p_list + align_up((size_t)p.nwin * (size_t)(p.win_tiles / p.sub_tiles) * sizeof(uint32_t), 256);
+  L.p_stride = L.p_nlist + 256;
+}
+// per-window slots of x (rows of cpad columns) and of the u row | the FP64 fallback's sums | prog_bytes of progress words
+// (single call; their offset is returned) | the pre-pass statistics; stride = their end.  Needs p.fb.
+static size_t i8_layout_scratch(const I8Plan &p, int K, int cpad, size_t prog_bytes, I8StateLayout &L) {
+  L.s_px = 0;
+  L.s_pu = L.s_px + align_up((size_t)p.nwin * p.nrep_pad * K * 8 * cpad * sizeof(double), 256);
+  L.s_fbx = L.s_pu + align_up((size_t)p.nwin * p.nrep_pad * K * 8 * sizeof(double), 256);
+  L.s_fbu = L.s_fbx + align_up((size_t)p.fb.n_chunks * p.fb.nrep_pad * p.fb.C_pad * K * sizeof(double), 256);
+  const size_t prog = L.s_fbu + align_up((size_t)p.fb.n_chunks * p.fb.nrep_pad * (K + 1) * sizeof(double), 256);  // + the y run's
+  L.s_stats = prog + align_up(prog_bytes, 256);
+  L.stride = L.s_stats + align_up((size_t)cdiv(p.ntiles, p.win_tiles < 16 ? p.win_tiles : 16) * 100 * sizeof(double), 256);
+  return prog;
+}
 
 static I8Plan plan_i8(int64_t N, int64_t C, int64_t nrep, int K) {
   I8Plan p;
@@ -810,27 +119,19 @@ static I8Plan plan_i8(int64_t N, int64_t C, int64_t nrep, int K) {
   p.tiles_per_chunk = cdiv(p.nwin, nc) * p.win_tiles;
   p.n_chunks = (int)(cdiv(cdiv(p.ntiles, p.tiles_per_chunk), 8) * 8);
   p.sub_tiles = p.win_tiles < I8_SUB_TILES ? (int)p.win_tiles : I8_SUB_TILES;
+  p.fb = plan_resample(N, C < I8_CPAD ? C : I8_CPAD, nrep, K);
+  p.prog_bytes = (size_t)p.n_chunks * 64 * sizeof(uint32_t);
   // prep block
-  p.prep_wt = 0;
-  p.prep_flag = p.prep_wt + align_up((size_t)p.nwin * I8_WT_STRIDE * sizeof(double) + 2048, 256);  // + timing slots of debug builds
-  p.prep_list = p.prep_flag + align_up((size_t)p.nwin * sizeof(uint32_t), 256);
-  p.prep_nlist = p.prep_list + align_up((size_t)p.nwin * (size_t)(p.win_tiles / p.sub_tiles) * sizeof(uint32_t), 256);
-  p.prep_ywt = p.prep_nlist + 256;
+  i8_layout_tables(p, p.L);
+  p.prep_ywt = p.L.p_stride;
   p.prep_yflag = p.prep_ywt + align_up((size_t)p.nwin * I8_WT_STRIDE * sizeof(double), 256);
   p.prep_group_stride = p.prep_yflag + align_up((size_t)p.nwin * sizeof(uint32_t), 256);
   p.prep_ypiv = align_up((size_t)(1 + C) * sizeof(double), 256);
   p.prep_group0 = 2 * p.prep_ypiv;
   p.prep_total = p.prep_group0 + (size_t)p.ngroups * p.prep_group_stride;
   // workspace
-  p.off_px = 0;
-  p.off_pu = p.off_px + align_up((size_t)p.nwin * p.nrep_pad * K * I8_CPAD * 8 * sizeof(double), 256);
-  p.fb = plan_resample(N, C < I8_CPAD ? C : I8_CPAD, nrep, K);
-  p.off_fbx = p.off_pu + align_up((size_t)p.nwin * p.nrep_pad * K * 8 * sizeof(double), 256);
-  p.off_fbu = p.off_fbx + align_up((size_t)p.fb.n_chunks * p.fb.nrep_pad * p.fb.C_pad * K * sizeof(double), 256);
-  p.off_prog = p.off_fbu + align_up((size_t)p.fb.n_chunks * p.fb.nrep_pad * (K + 1) * sizeof(double), 256);  // + the y run's
-  p.prog_bytes = (size_t)p.n_chunks * 64 * sizeof(uint32_t);
-  p.off_stats = p.off_prog + align_up(p.prog_bytes, 256);
-  p.off_py = p.off_stats + align_up((size_t)cdiv(p.ntiles, p.win_tiles < 16 ? p.win_tiles : 16) * 100 * sizeof(double), 256);
+  p.off_prog = i8_layout_scratch(p, K, I8_CPAD, p.prog_bytes, p.L);
+  p.off_py = p.L.stride;
   p.off_fby = p.off_py + align_up((size_t)p.nwin * p.nrep_pad * 8 * I8_CPAD * sizeof(double), 256);
   p.off_prep = p.off_fby + align_up((size_t)p.fb.n_chunks * p.fb.nrep_pad * p.fb.C_pad * sizeof(double), 256);
   // the count table sits LAST: `total` is the size without it, `total_table` with it -- a call runs the table kernel when
@@ -850,6 +151,16 @@ static I8Plan plan_i8(int64_t N, int64_t C, int64_t nrep, int K) {
 // txm_resample_opts.path does not look at this word either.
 static int g_path_override = -1;
 static int path_override() { return g_path_override; }
+// the path of a call that passes `call_path` (idempotent: an effective path maps to itself)
+static int effective_path(int call_path) { return call_path != TXM_PATH_AUTO ? call_path : path_override(); }
+// a path word other than TXM_PATH_AUTO
+static bool is_path(int path) {
+  return path == TXM_PATH_FP64 || path == TXM_PATH_INT8 || path == TXM_PATH_INT8_FUSED || path == TXM_PATH_INT8_TABLE;
+}
+// what every size and path query answers 0 / TXM_PATH_FP64 on, and every call refuses
+static bool shape_ok(int64_t N, int64_t C, int64_t nrep, int order) {
+  return N >= 1 && C >= 1 && nrep >= 1 && order >= 0 && order <= TXM_MAX_ORDER;
+}
 
 // Wide states on the int8 path: which of its two contraction kernels.  They agree bit for bit (the same int32 sums, the same
 // flush), so this is a rule on speed alone -- measured on MI355X, pre-pass block kept, ms per call fused / table
@@ -910,6 +221,12 @@ static bool table_call_rule(size_t table_bytes, int eff, int64_t N, int64_t C, i
   if (eff == TXM_PATH_INT8_TABLE) return true;
   return C > 16 ? table_kernel_pays(nrep, K, has_y) : narrow_table_pays(N, C, nrep, K);
 }
+// ... and of "does that kernel carry the second matrix": the wide table kernel always, the fused one where it has the row set
+struct I8KernelChoice { bool table_call, with_y; };
+static I8KernelChoice i8_kernel_choice(const I8Plan &q, int eff, int64_t N, int64_t C, int64_t nrep, int K, bool has_y, bool applicable) {
+  const bool table = table_call_rule(q.table_bytes, eff, N, C, nrep, K, has_y, applicable);
+  return {table, has_y && ((table && C > 16) || i8t_carries_y(C, K))};
+}
 // what the table-fed kernels ask of the operands (16-byte LDS-DMA pieces): wide states txm_resample_i8g.hip, narrow ones
 // txm_resample_i8gn.hip (a second matrix never rides a narrow call: it is bootstrapped on its own)
 static bool table_operands_ok(const double *x, int64_t ldx_s, int64_t C, int K, const double *y, int64_t ldy_s) {
@@ -918,7 +235,7 @@ static bool table_operands_ok(const double *x, int64_t ldx_s, int64_t C, int K, 
 
 static bool use_i8(int64_t N, int64_t C, int64_t nrep, int K, int call_path = TXM_PATH_AUTO) {
   if (!i8_supported(N, C, nrep, K)) return false;
-  const int ov = call_path != TXM_PATH_AUTO ? call_path : path_override();
+  const int ov = effective_path(call_path);
   if (ov == TXM_PATH_FP64) return false;
   if (ov == TXM_PATH_INT8 || ov == TXM_PATH_INT8_FUSED || ov == TXM_PATH_INT8_TABLE) return true;
   // measured on MI355X (tools/i8_sweep.py, N = 1e7; tools/ab_order.py, N = 1e8): C <= 16 runs one 16-column FP64
@@ -950,7 +267,7 @@ static bool use_i8(int64_t N, int64_t C, int64_t nrep, int K, int call_path = TX
 using namespace txm;
 
 extern "C" int txm_set_resample_path(int path) {
-  TXM_REQUIRE(path == -1 || path == TXM_PATH_FP64 || path == TXM_PATH_INT8 || path == TXM_PATH_INT8_FUSED || path == TXM_PATH_INT8_TABLE, "set_resample_path: %d is not a path", path);
+  TXM_REQUIRE(path == -1 || is_path(path), "set_resample_path: %d is not a path", path);
   g_path_override = path;
   return TXM_OK;
 }
@@ -981,7 +298,7 @@ using namespace txm;
 extern "C" int txm_resample_vals_info(const void *ws, int64_t N, int64_t C, int64_t nrep, int order,
                                       int64_t *info_host, txm_stream stream) {
   TXM_REQUIRE(ws && info_host, "resample_vals_info: null pointer");
-  TXM_REQUIRE(N >= 1 && C >= 1 && nrep >= 1 && order >= 0 && order <= TXM_MAX_ORDER, "resample_vals_info: bad shape");
+  TXM_REQUIRE(shape_ok(N, C, nrep, order), "resample_vals_info: bad shape");
   info_host[0] = TXM_PATH_FP64;
   info_host[1] = info_host[2] = 0;
   if (!use_i8(N, C, nrep, order + 1)) return TXM_OK;
@@ -990,7 +307,7 @@ extern "C" int txm_resample_vals_info(const void *ws, int64_t N, int64_t C, int6
   int64_t flagged = 0;
   for (int g = 0; g < q.ngroups; ++g) {
     uint32_t nl[2] = {0, 0};
-    TXM_HIP(hipMemcpyAsync(nl, (const char *)ws + q.off_prep + q.prep_group0 + (size_t)g * q.prep_group_stride + q.prep_nlist,
+    TXM_HIP(hipMemcpyAsync(nl, (const char *)ws + q.off_prep + q.prep_group0 + (size_t)g * q.prep_group_stride + q.L.p_nlist,
                            sizeof(nl), hipMemcpyDeviceToHost, (hipStream_t)stream));
     TXM_HIP(hipStreamSynchronize((hipStream_t)stream));
     flagged += nl[1];
@@ -1002,7 +319,7 @@ extern "C" int txm_resample_vals_info(const void *ws, int64_t N, int64_t C, int6
 }
 
 extern "C" int txm_resample_path(int64_t N, int64_t C, int64_t nrep, int order) {
-  if (N < 1 || C < 1 || nrep < 1 || order < 0 || order > TXM_MAX_ORDER) return TXM_PATH_FP64;
+  if (!shape_ok(N, C, nrep, order)) return TXM_PATH_FP64;
   return use_i8(N, C, nrep, order + 1) ? TXM_PATH_INT8 : TXM_PATH_FP64;
 }
 
@@ -1012,14 +329,12 @@ extern "C" int txm_resample_path(int64_t N, int64_t C, int64_t nrep, int order) 
 // `aligned`: x (and y) 16-byte aligned with an even row pitch >= C rounded up to 4 -- what the table kernel's DMA needs.
 // A kept pre-pass block serves exactly the calls that return the same word here (and the same N, C, order, tensors).
 extern "C" int txm_resample_kernel(int64_t N, int64_t C, int64_t nrep, int order, int path, int has_y, int aligned) {
-  if (N < 1 || C < 1 || nrep < 1 || order < 0 || order > TXM_MAX_ORDER) return TXM_PATH_FP64;
+  if (!shape_ok(N, C, nrep, order)) return TXM_PATH_FP64;
   const int K = order + 1;
   if (!use_i8(N, C, nrep, K, path)) return TXM_PATH_FP64;
   const I8Plan q = plan_i8(N, C, nrep, K);
-  const int eff = path != TXM_PATH_AUTO ? path : path_override();
-  const bool table = table_call_rule(q.table_bytes, eff, N, C, nrep, K, has_y != 0, aligned != 0);
-  const bool with_y = has_y != 0 && ((table && C > 16) || i8t_carries_y(C, K));
-  return (table ? TXM_PATH_INT8_TABLE : TXM_PATH_INT8_FUSED) | (with_y ? TXM_KERNEL_WITH_Y : 0);
+  const I8KernelChoice k = i8_kernel_choice(q, effective_path(path), N, C, nrep, K, has_y != 0, aligned != 0);
+  return (k.table_call ? TXM_PATH_INT8_TABLE : TXM_PATH_INT8_FUSED) | (k.with_y ? TXM_KERNEL_WITH_Y : 0);
 }
 
 // the `aligned` argument of txm_resample_kernel for a given pair of operands (y may be NULL): what the count-table kernel's
@@ -1034,24 +349,9 @@ extern "C" int txm_resample_operands_aligned(const double *x, int64_t ldx_s, int
 extern "C" void txm_i8g_quarter_split(int Q, int *n6, int *n4) { g_quarter_split(Q, n6, n4); }
 
 extern "C" size_t txm_resample_prep_bytes(int64_t N, int64_t C, int64_t nrep, int order) {
-  if (N < 1 || C < 1 || nrep < 1 || order < 0 || order > TXM_MAX_ORDER) return 0;
+  if (!shape_ok(N, C, nrep, order)) return 0;
   if (!i8_supported(N, C, nrep, order + 1)) return 256;
   return plan_i8(N, C, nrep, order + 1).prep_total;
-}
-
-// the second sample matrix of txm_resample_opts (y -> per-replicate means) runs as an order-0 bootstrap of its own
-// behind the main call unless the kernel of the main call carries it: its states [nrep][C][2][1] and its own
-// workspace sit behind the main plan's
-static size_t y_main_bytes(int64_t N, int64_t C, int64_t nrep) {
-  size_t n = plan_resample(N, C, nrep, 1).total;
-  if (i8_supported(N, C, nrep, 1)) {
-    const size_t m = plan_i8(N, C, nrep, 1).total;
-    if (m > n) n = m;
-  }
-  return align_up(n, 256);
-}
-static size_t y_extra_bytes(int64_t N, int64_t C, int64_t nrep) {
-  return align_up((size_t)nrep * C * 2 * sizeof(double), 256) + y_main_bytes(N, C, nrep);
 }
 
 // path / has_y: what the call will pass in txm_resample_opts -- they decide whether the int8 path's count table (one byte
@@ -1059,12 +359,11 @@ static size_t y_extra_bytes(int64_t N, int64_t C, int64_t nrep) {
 // library's rule (table_kernel_pays), TXM_PATH_INT8_TABLE always asks for it, TXM_PATH_FP64 / _INT8_FUSED never.  A call
 // handed less than this runs the kernel without the table.
 extern "C" size_t txm_resample_vals_ws_bytes_opts(int64_t N, int64_t C, int64_t nrep, int order, int path, int has_y) {
-  if (N < 1 || C < 1 || nrep < 1 || order < 0 || order > TXM_MAX_ORDER) return 0;
+  if (!shape_ok(N, C, nrep, order)) return 0;
   size_t n = plan_resample(N, C, nrep, order + 1).total;
   if (i8_supported(N, C, nrep, order + 1)) {
     const I8Plan q = plan_i8(N, C, nrep, order + 1);
-    const int eff = path != TXM_PATH_AUTO ? path : path_override();
-    const bool table = table_call_rule(q.table_bytes, eff, N, C, nrep, order + 1, has_y != 0, true);
+    const bool table = table_call_rule(q.table_bytes, effective_path(path), N, C, nrep, order + 1, has_y != 0, true);
     const size_t m = table ? q.total_table : q.total;
     if (m > n) n = m;
   }
@@ -1073,6 +372,15 @@ extern "C" size_t txm_resample_vals_ws_bytes_opts(int64_t N, int64_t C, int64_t 
 
 extern "C" size_t txm_resample_vals_ws_bytes(int64_t N, int64_t C, int64_t nrep, int order) {
   return txm_resample_vals_ws_bytes_opts(N, C, nrep, order, TXM_PATH_AUTO, 0);
+}
+
+// the second sample matrix of txm_resample_opts (y -> per-replicate means) runs as an order-0 bootstrap of its own
+// behind the main call unless the kernel of the main call carries it: its states [nrep][C][2][1] and its own
+// workspace sit behind the main plan's
+// (the order-0 pass: the larger of the two paths' plans, never the count table)
+static size_t y_main_bytes(int64_t N, int64_t C, int64_t nrep) { return txm_resample_vals_ws_bytes_opts(N, C, nrep, 0, TXM_PATH_INT8_FUSED, 0); }
+static size_t y_extra_bytes(int64_t N, int64_t C, int64_t nrep) {
+  return align_up((size_t)nrep * C * 2 * sizeof(double), 256) + y_main_bytes(N, C, nrep);
 }
 
 // ... and the scratch a call with opts.y needs BEHIND those bytes when the kernel of the main call does not carry the
@@ -1085,105 +393,9 @@ extern "C" size_t txm_resample_y_ws_bytes(int64_t N, int64_t C, int64_t nrep) {
 
 // whether the int8 kernel can take the shape at all (TXM_PATH_INT8 on a shape it cannot take runs the FP64 kernel)
 extern "C" int txm_resample_i8_supported(int64_t N, int64_t C, int64_t nrep, int order) {
-  if (N < 1 || C < 1 || nrep < 1 || order < 0 || order > TXM_MAX_ORDER) return 0;
+  if (!shape_ok(N, C, nrep, order)) return 0;
   return i8_supported(N, C, nrep, order + 1) ? 1 : 0;
 }
-
-#define TXM_K_SWITCH(K_, CALL)                          \
-  switch (K_) {                                         \
-    case 1: { constexpr int KK = 1; CALL; } break;      \
-    case 2: { constexpr int KK = 2; CALL; } break;      \
-    case 3: { constexpr int KK = 3; CALL; } break;      \
-    case 4: { constexpr int KK = 4; CALL; } break;      \
-    case 5: { constexpr int KK = 5; CALL; } break;      \
-    case 6: { constexpr int KK = 6; CALL; } break;      \
-    case 7: { constexpr int KK = 7; CALL; } break;      \
-    case 8: { constexpr int KK = 8; CALL; } break;      \
-    case 9: { constexpr int KK = 9; CALL; } break;      \
-    default: set_error("order out of range"); return TXM_ERR_INVALID; \
-  }
-
-namespace txm {
-template <int K>
-static int run_resample(ResampleArgs a, const ResamplePlan &p, bool weighted, bool explicit_,
-                        double *out, hipStream_t st, int64_t S = 1) {
-  dim3 grid((unsigned)(p.n_chunks * p.n_rbg), (unsigned)p.colgroups, (unsigned)S), block(RS_BLOCK);
-  const size_t lds = explicit_ ? 0 : (size_t)RS_WAVES * RS_TILE_BYTES;
-#define TXM_RS_LAUNCH(NB, WT, EX)                                                                       \
-  do {                                                                                                 \
-    if (S > 1 || a.batch != nullptr) {                                                                 \
-      if (a.N < SM_T)                                                                                  \
-        hipLaunchKernelGGL((resample_kernel<K, NB, WT, EX, true, RS_BATCHED>), grid, block, lds, st, a);  \
-      else                                                                                             \
-        hipLaunchKernelGGL((resample_kernel<K, NB, WT, EX, false, RS_BATCHED>), grid, block, lds, st, a); \
-    } else if (a.N < SM_T)                                                                             \
-      hipLaunchKernelGGL((resample_kernel<K, NB, WT, EX, true>), grid, block, lds, st, a);             \
-    else                                                                                               \
-      hipLaunchKernelGGL((resample_kernel<K, NB, WT, EX, false>), grid, block, lds, st, a);            \
-  } while (0)
-  // narrow states (C <= 8, device sampler, full tiles): PACK powers per B column -> ceil(K / PACK) MFMAs per k-step
-  bool packed = false;
-  if constexpr (K >= 2 && K <= 6) {
-    if (p.nblk == 1 && p.colgroups == 1 && !explicit_ && a.N >= SM_T && a.C <= 8) {
-      packed = true;
-      const bool bat = S > 1 || a.batch != nullptr;
-#define TXM_RS_PACKED(PK)                                                                                      \
-  do {                                                                                                         \
-    if (bat) {                                                                                                 \
-      if (weighted) hipLaunchKernelGGL((resample_kernel<K, 1, true, false, false, RS_BATCHED, PK>), grid, block, lds, st, a); \
-      else hipLaunchKernelGGL((resample_kernel<K, 1, false, false, false, RS_BATCHED, PK>), grid, block, lds, st, a);         \
-    } else {                                                                                                   \
-      if (weighted) hipLaunchKernelGGL((resample_kernel<K, 1, true, false, false, RS_PLAIN, PK>), grid, block, lds, st, a);   \
-      else hipLaunchKernelGGL((resample_kernel<K, 1, false, false, false, RS_PLAIN, PK>), grid, block, lds, st, a);           \
-    }                                                                                                          \
-  } while (0)
-      if (a.C <= 4 && K >= 3) TXM_RS_PACKED(4);
-      else TXM_RS_PACKED(2);
-#undef TXM_RS_PACKED
-    }
-  }
-  if (packed) {
-  } else if (p.nblk == 1) {
-    if (weighted) { if (explicit_) TXM_RS_LAUNCH(1, true, true); else TXM_RS_LAUNCH(1, true, false); }
-    else          { if (explicit_) TXM_RS_LAUNCH(1, false, true); else TXM_RS_LAUNCH(1, false, false); }
-  } else {
-    if (weighted) { if (explicit_) TXM_RS_LAUNCH(2, true, true); else TXM_RS_LAUNCH(2, true, false); }
-    else          { if (explicit_) TXM_RS_LAUNCH(2, false, true); else TXM_RS_LAUNCH(2, false, false); }
-  }
-#undef TXM_RS_LAUNCH
-  TXM_LAUNCH_CHECK();
-  const int64_t ne = a.nrep * a.C;
-  hipLaunchKernelGGL((resample_finalize_kernel<K>), dim3((unsigned)cdiv(ne, 32), (unsigned)S), dim3(256), 0, st,
-                     a.part_x, a.part_u, p.n_chunks, p.nrep_pad, p.C_pad, a.nrep, a.C, a.pivot, out);
-  TXM_LAUNCH_CHECK();
-  return TXM_OK;
-}
-
-// the bootstrap kernel alone, in listed mode (device sampler, N >= one tile), partial sums left for the caller's finalize
-template <int K>
-static int run_listed_k(const ResampleArgs &a, const ResamplePlan &p, bool weighted, hipStream_t st, int64_t S = 1) {
-  dim3 grid((unsigned)(p.n_chunks * p.n_rbg), (unsigned)p.colgroups, (unsigned)S), block(RS_BLOCK);
-  const size_t lds = (size_t)RS_WAVES * RS_TILE_BYTES;
-  if (p.nblk == 1) {
-    if (weighted) hipLaunchKernelGGL((resample_kernel<K, 1, true, false, false, RS_LISTED>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((resample_kernel<K, 1, false, false, false, RS_LISTED>), grid, block, lds, st, a);
-  } else {
-    if (weighted) hipLaunchKernelGGL((resample_kernel<K, 2, true, false, false, RS_LISTED>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((resample_kernel<K, 2, false, false, false, RS_LISTED>), grid, block, lds, st, a);
-  }
-  TXM_LAUNCH_CHECK();
-  return TXM_OK;
-}
-
-static int run_listed(const ResampleArgs &a, const ResamplePlan &p0, int K, bool weighted, hipStream_t st, int64_t S = 1) {
-  // the plan was made for a full 32-column group; a narrower last group uses one 16-column block
-  ResamplePlan p = p0;
-  if (a.C <= 16) p.nblk = 1;
-  p.colgroups = 1;
-  TXM_K_SWITCH(K, return run_listed_k<KK>(a, p, weighted, st, S));
-  return TXM_OK;
-}
-}  // namespace txm
 
 namespace txm {
 // y[N][C] -> the mean column of its order-0 replicate states
@@ -1192,241 +404,277 @@ __global__ void y_means_kernel(const double *__restrict__ st /*[n][2]*/, int64_t
   if (e < n) out[e] = st[2 * e + 1];
 }
 
-static int resample_vals_impl(const double *x, int64_t ldx_s, const double *u, const double *w, int64_t N, int64_t C,
-                              int order, int64_t nrep, const int64_t *freq, const txm_sampler_spec *spec,
-                              const uint32_t *counts, const double *pivot, double *out, int path, void *prep,
-                              size_t prep_bytes, bool prep_valid, int64_t *info, void *ws, size_t ws_bytes,
-                              hipStream_t st, const double *y = nullptr, int64_t ldy_s = 0, double *out_y = nullptr,
-                              bool *y_done = nullptr) {
-  // y / out_y: the second sample matrix of txm_resample_opts.  Carried by this call when the int8 kernel can take it
-  // as a row set of its last pass (*y_done = true); otherwise left to the caller (a separate order-0 bootstrap).
-  const bool explicit_ = freq != nullptr;
-  const int K = order + 1;
-  if (y_done) *y_done = false;
-  if (!explicit_ && use_i8(N, C, nrep, K, path)) {
-    const I8Plan q = plan_i8(N, C, nrep, K);
-    // wide states: the per-sample counts of the call's replicates as a table in HBM (built once, shared by the column groups
-    // and the passes) and the contraction kernel without a sampler inside (txm_resample_i8g.hip).  Misaligned operands and
-    // TXM_PATH_INT8_FUSED keep the kernel that draws in place; narrow states and narrow tail groups always run it.
-    const int eff_path = path != TXM_PATH_AUTO ? path : path_override();
-    const bool table_call = ws_bytes >= q.total_table &&
-                            table_call_rule(q.table_bytes, eff_path, N, C, nrep, K, y != nullptr, table_operands_ok(x, ldx_s, C, K, y, ldy_s));
-    const bool with_y = y != nullptr && ((table_call && C > 16) || i8t_carries_y(C, K));
-    if (ws_bytes < q.total) {
-      set_error("resample_vals: workspace too small (%zu < %zu)", ws_bytes, q.total);
-      return TXM_ERR_WORKSPACE;
-    }
-    TXM_REQUIRE(spec->ndat == N && spec->nrep == nrep, "resample_vals: sampler spec does not match N/nrep");
-    TXM_REQUIRE(spec->rep0 >= 0 && spec->rep0 + nrep <= ((int64_t)1 << 32), "resample_vals: sampler rep0 out of range");
-    // the pre-pass block: the caller's persistent buffer (tables reused when prep_valid) or scratch in ws
-    unsigned char *pb = (unsigned char *)ws + q.off_prep;
-    bool have_tables = false;
-    if (prep != nullptr) {
-      if (prep_bytes < q.prep_total) {
-        set_error("resample_vals: prep buffer too small (%zu < %zu)", prep_bytes, q.prep_total);
-        return TXM_ERR_WORKSPACE;
-      }
-      pb = (unsigned char *)prep;
-      have_tables = prep_valid;
-    }
-    double *piv = (double *)pb;
-    double *ypiv = (double *)(pb + q.prep_ypiv);
-    if (!have_tables) {
-      if (pivot) {
-        TXM_HIP(hipMemcpyAsync(piv, pivot, sizeof(double) * (size_t)(1 + C), hipMemcpyDeviceToDevice, st));
-      } else {
-        hipLaunchKernelGGL(pivot_kernel, dim3((unsigned)(1 + C)), dim3(256), 0, st, x, ldx_s, (int64_t)1,
-                           u, (int64_t)1, N, piv);
-        TXM_LAUNCH_CHECK();
-      }
-      if (with_y) {
-        hipLaunchKernelGGL(pivot_kernel, dim3((unsigned)(1 + C)), dim3(256), 0, st, y, ldy_s, (int64_t)1, u, (int64_t)1,
-                           N, ypiv);
-        TXM_LAUNCH_CHECK();
-        // one u pivot for the call (the monomial scales of both matrices are built on it)
-        TXM_HIP(hipMemcpyAsync(ypiv, piv, sizeof(double), hipMemcpyDeviceToDevice, st));
-      }
-    }
-    I8Args b;
-    b.x = x; b.ldx_s = ldx_s; b.u = u; b.w = w; b.N = N; b.nrep = nrep; b.C_call = C;
-    b.cpad = i8_cpad(C, K);
-    b.counts = counts;
-    b.k0 = (uint32_t)spec->seed;
-    b.k1 = (uint32_t)(spec->seed >> 32);
-    b.rep_base = (uint32_t)spec->rep0;
-    b.ntiles = q.ntiles;
-    b.last_tile_size = (uint32_t)(N - (q.ntiles - 1) * SM_T);
-    b.pivot = piv;
-    b.stats = (double *)((char *)ws + q.off_stats);
-    b.nwin = q.nwin;
-    b.part_x = (double *)((char *)ws + q.off_px);
-    b.part_u = (double *)((char *)ws + q.off_pu);
-    b.n_chunks = q.n_chunks; b.n_rbg = q.n_rbg; b.tiles_per_chunk = q.tiles_per_chunk;
-    b.nrep_pad = q.nrep_pad;
-    b.win_tiles = q.win_tiles;
-    b.sub_tiles = q.sub_tiles;
-    b.y = with_y ? y : nullptr;
-    b.ldy_s = ldy_s;
-    b.ypivot = ypiv;
-    b.part_y = (double *)((char *)ws + q.off_py);
-    b.part_summed = i8t_wide_summed(with_y) ? 1 : 0;  // (what the wide fused kernel's instances of this call store: the finalize's mode below)
-    b.progress = q.n_rbg > 1 ? (uint32_t *)((char *)ws + q.off_prog) : nullptr;
-    // the FP64 kernel in listed mode: contracts the windows the precision guard flags (none on ordinary data)
-    ResampleArgs f;
-    f.ldx_s = ldx_s; f.u = u; f.w = w; f.N = N; f.nrep = nrep;
-    f.freq = nullptr; f.counts = counts;
-    f.k0 = b.k0; f.k1 = b.k1; f.rep_base = b.rep_base;
-    f.ntiles = q.ntiles; f.last_tile_size = b.last_tile_size;
-    f.pivot = piv;
-    f.part_x = (double *)((char *)ws + q.off_fbx);
-    f.part_u = (double *)((char *)ws + q.off_fbu);
-    f.n_chunks = q.fb.n_chunks; f.n_rbg = q.fb.n_rbg; f.tiles_per_chunk = q.fb.tiles_per_chunk;
-    f.nrep_pad = q.fb.nrep_pad; f.C_pad = q.fb.C_pad;
-    f.sub_tiles = q.sub_tiles; f.batch = nullptr; f.progress = nullptr;
-    TXM_REQUIRE(q.fb.nrep_pad == q.nrep_pad, "resample_vals: replicate padding of the two kernels differs");
-    // one launch (or two, orders 5-7) per group of 32 columns; the groups reuse the partial buffers
-    int g = 0;
-    bool have_table = false;
-    for (int64_t col0 = 0; col0 < C; col0 += I8_CPAD, ++g) {
-      unsigned char *pg = pb + q.prep_group0 + (size_t)g * q.prep_group_stride;
-      b.wtab = (double *)(pg + q.prep_wt);
-      b.wflag = (uint32_t *)(pg + q.prep_flag);
-      b.list = (uint32_t *)(pg + q.prep_list);
-      b.n_list = (uint32_t *)(pg + q.prep_nlist);
-      b.ywtab = (double *)(pg + q.prep_ywt);
-      b.yflag = (uint32_t *)(pg + q.prep_yflag);
-      f.list = b.list; f.n_list = b.n_list;
-      b.col0 = col0;
-      b.C = C - col0 < I8_CPAD ? C - col0 : I8_CPAD;
-      // a tail group of <= 16 columns behind full groups runs the narrow-state variant (its own partial-sum row width) --
-      // unless a second matrix rides on the pass, which only the wide variant carries
-      const bool narrow_tail = C > I8_CPAD && b.C <= 16 && K >= 2 && !with_y;
-      b.C_call = narrow_tail ? b.C : C;
-      b.cpad = i8_cpad(b.C_call, K);
-      if (!have_tables) {
-        const int rc0 = launch_i8_prepass(b, K, st);
-        if (rc0 != TXM_OK) return rc0;
-      }
-      const bool table_kernel = table_call && !narrow_tail;
-      int rc;
-      if (table_kernel) {
-        unsigned char *table = (unsigned char *)ws + q.off_table;
-        if (!have_table) {
-          rc = launch_count_table(counts, nrep, N, b.k0, b.k1, b.rep_base, 0, cdiv(nrep, G_REPS), table, st);
-          if (rc != TXM_OK) return rc;
-          have_table = true;
-        }
-        I8Args bg = b;
-        bg.progress = nrep > G_REPS ? (uint32_t *)((char *)ws + q.off_gprog) : nullptr;
-        rc = C > 16 ? launch_resample_i8g(bg, K, w != nullptr, table, 0, (int)cdiv(nrep, G_REPS), st)
-                    : launch_resample_i8gn(bg, K, w != nullptr, table, 0, (int)cdiv(nrep, G_REPS), 0, st);
-      } else {
-        rc = launch_resample_i8(b, K, w != nullptr, q.prog_bytes, st);
-      }
-      if (rc != TXM_OK) return rc;
-      f.x = x + col0; f.C = b.C; f.col_off = col0;
-      {
-        const int rc2 = run_listed(f, q.fb, K, w != nullptr, st);
-        if (rc2 != TXM_OK) return rc2;
-      }
-      // (the slots' layout: digit sums where the fused narrow kernel with chunk groups wrote them, per-digit slots otherwise)
-      // (table-fed kernels: always -- txm_resample_i8gn.hip both x and u, txm_resample_i8g.hip x only; the fused kernel: its chunk-group instances)
-      // the fused kernel: narrow instances always, the wide one unless a second matrix rides the call (its finalize reads per-digit u slots)
-      const int fin_summed = table_kernel ? (C <= 16 ? 1 : 2)
-                                          : (i8t_narrow_nq(b.C_call, K) != 0 ? (i8t_partials_summed(b.C_call, K) ? 1 : 0) : b.part_summed);
-#define TXM_I8_FIN2(KK, CP)                                                                            \
-  hipLaunchKernelGGL((resample_finalize_i8_kernel<KK, CP>), dim3((unsigned)nrep), dim3(256), 0, st,      \
-                     b.part_x, b.part_u, q.nwin, b.wflag, q.nrep_pad, nrep, b.C, piv, out, col0, C,        \
-                     f.part_x, f.part_u, q.fb.n_chunks, q.fb.C_pad, b.n_list, (const I8State *)nullptr, fin_summed)
-#define TXM_I8_FIN(KK)                                                                                 \
-  do {                                                                                                 \
-    if (b.cpad == 32) TXM_I8_FIN2(KK, 32);                                                             \
-    else if (b.cpad == 16) TXM_I8_FIN2(KK, 16);                                                        \
-    else if (b.cpad == 8) TXM_I8_FIN2(KK, 8);                                                          \
-    else TXM_I8_FIN2(KK, 4);                                                                           \
-  } while (0)
-      switch (K) {
-        case 1: TXM_I8_FIN(1); break;
-        case 2: TXM_I8_FIN(2); break;
-        case 3: TXM_I8_FIN(3); break;
-        case 4: TXM_I8_FIN(4); break;
-        case 5: TXM_I8_FIN(5); break;
-        case 6: TXM_I8_FIN(6); break;
-        case 7: TXM_I8_FIN(7); break;
-        default: TXM_I8_FIN(8); break;
-      }
-#undef TXM_I8_FIN
-      TXM_LAUNCH_CHECK();
-      if (with_y) {
-        // the windows the guard flagged (for either matrix): the FP64 kernel in listed mode on y, order 0
-        ResampleArgs fy = f;
-        fy.x = y + col0; fy.ldx_s = ldy_s; fy.pivot = ypiv;
-        fy.part_x = (double *)((char *)ws + q.off_fby);
-        fy.part_u = f.part_u + (size_t)q.fb.n_chunks * q.fb.nrep_pad * K;  // scratch behind x's u-row sums (unused by the finalize)
-        const int rc3 = run_listed(fy, q.fb, 1, w != nullptr, st);
-        if (rc3 != TXM_OK) return rc3;
-        hipLaunchKernelGGL(resample_finalize_y_kernel, dim3((unsigned)nrep), dim3(256), 0, st, b.part_y, b.part_u, K, q.nwin,
-                           b.wflag, q.nrep_pad, b.C, ypiv, out_y, col0, C, fy.part_x, f.part_u, q.fb.n_chunks, q.fb.C_pad,
-                           b.n_list);
-        TXM_LAUNCH_CHECK();
-      }
-    }
-    if (with_y && y_done) *y_done = true;
-    // a reused prep block keeps its n_list words; a fresh one inside ws is what txm_resample_vals_info reads back
-    if (prep != nullptr)
-      TXM_HIP(hipMemcpyAsync((char *)ws + q.off_prep, pb, q.prep_total, hipMemcpyDeviceToDevice, st));
-    if (info != nullptr) {
-      hipLaunchKernelGGL(i8_info_kernel, dim3(1), dim3(64), 0, st, pb + q.prep_group0, q.prep_group_stride, q.prep_nlist,
-                         q.ngroups, q.nwin, (have_tables ? 1 : 0) | (have_table ? 2 : 0), info);
-      TXM_LAUNCH_CHECK();
-    }
-    return TXM_OK;
-  }
-  if (info != nullptr) {
-    hipLaunchKernelGGL(fp64_info_kernel, dim3(1), dim3(64), 0, st, info);
-    TXM_LAUNCH_CHECK();
-  }
-  const ResamplePlan p = plan_resample(N, C, nrep, K);
-  if (ws_bytes < p.total) {
-    set_error("resample_vals: workspace too small (%zu < %zu)", ws_bytes, p.total);
+// ---- one description of a call and the steps every call is made of -----------------------------------------------------
+// What txm_resample_vals / txm_resample_vals_batched_opts resolve from their arguments, once.
+struct ResampleCall {
+  const char *fn = "resample_vals";                   // the entry point's name in error texts
+  const double *x = nullptr, *u = nullptr, *w = nullptr;  // operands of a single call ...
+  const txm_state_ptrs *states_host = nullptr;        // ... or the S states of a batched one
+  int64_t S = 1, ldx_s = 0, N = 0, C = 0, nrep = 0;   // nrep: replicates per state
+  int K = 1;
+  bool weighted = false;
+  const int64_t *freq = nullptr;                      // explicit table, or the sampler's spec and tile counts
+  const txm_sampler_spec *spec = nullptr;
+  const uint32_t *counts = nullptr;
+  const double *pivot = nullptr;                      // the caller's, nullptr: computed
+  double *out = nullptr;
+  int path = TXM_PATH_AUTO;                           // the options, resolved (take_opts): the EFFECTIVE path, ...
+  void *prep = nullptr;
+  size_t prep_bytes = 0, ws_bytes = 0;
+  bool prep_valid = false;
+  int64_t *info = nullptr, ldy_s = 0;
+  const double *y = nullptr;
+  double *out_y = nullptr;
+  void *ws = nullptr;
+  hipStream_t st = nullptr;
+  bool explicit_() const { return freq != nullptr; }
+  bool batched() const { return states_host != nullptr; }
+};
+
+static int check_pitch(const char *fn, const char *operand, int64_t ld, int64_t C) {
+  if (TXM_RESAMPLE_PITCH_OK(ld, C)) return TXM_OK;  // else the kernels' 32-bit lane offsets would wrap
+  set_error("%s: row pitch %sld%s_s = %lld with C = %lld columns exceeds the limit 768 * ld%s_s + C <= 2^29 = 536870912 (32-bit byte offsets inside a sampler tile); copy %s to a tighter array",
+            fn, operand[0] == 'y' ? "opts." : "", operand, (long long)ld, (long long)C, operand, operand);
+  return TXM_ERR_UNSUPPORTED;
+}
+// the options of a call (NULL: the defaults): the path word is checked, then resolved
+static int take_opts(ResampleCall &c, const txm_resample_opts *opts) {
+  const int path = opts ? (int)opts->path : TXM_PATH_AUTO;
+  TXM_REQUIRE(path == TXM_PATH_AUTO || is_path(path), "%s: opts.path %d is not a path", c.fn, path);
+  c.path = effective_path(path);
+  if (opts == nullptr) return TXM_OK;
+  c.prep = opts->prep; c.prep_bytes = opts->prep_bytes; c.prep_valid = opts->prep_valid != 0; c.info = opts->info;
+  c.y = opts->y; c.ldy_s = opts->ldy_s; c.out_y = opts->out_y;
+  return TXM_OK;
+}
+static int check_workspace(const char *fn, size_t have, size_t need) {
+  if (have >= need) return TXM_OK;
+  set_error("%s: workspace too small (%zu < %zu)", fn, have, need);
+  return TXM_ERR_WORKSPACE;
+}
+// the sampler of a call spans its S * nrep replicates of N samples (the two entry points word it differently)
+static int check_sampler(const ResampleCall &c) {
+  const int64_t nrep = c.S * c.nrep;
+  TXM_REQUIRE(c.spec->ndat == c.N && c.spec->nrep == nrep, "%s", c.batched() ? "resample_vals_batched: the sampler must span S * nrep replicates of N samples"
+                                                                           : "resample_vals: sampler spec does not match N/nrep");
+  TXM_REQUIRE(c.spec->rep0 >= 0 && c.spec->rep0 + nrep <= ((int64_t)1 << 32), "%s", c.batched() ? "resample_vals_batched: sampler replicates outside [0, 2^32)"
+                                                                                             : "resample_vals: sampler rep0 out of range");
+  return TXM_OK;
+}
+// the pre-pass block: the caller's persistent buffer (tables reused when prep_valid) or scratch in ws
+static int bind_prep(const ResampleCall &c, size_t need, unsigned char *&pb, bool &have_tables) {
+  have_tables = false;
+  if (c.prep == nullptr) return TXM_OK;
+  if (c.prep_bytes < need) {
+    set_error("%s: prep buffer too small (%zu < %zu)", c.fn, c.prep_bytes, need);
     return TXM_ERR_WORKSPACE;
   }
-  TXM_REQUIRE((int64_t)p.n_chunks * p.n_rbg < ((int64_t)1 << 31), "resample_vals: grid too large");
-  double *piv = (double *)((char *)ws + p.off_pivot);
-  if (pivot) {
-    TXM_HIP(hipMemcpyAsync(piv, pivot, sizeof(double) * (size_t)(1 + C), hipMemcpyDeviceToDevice, st));
+  pb = (unsigned char *)c.prep;
+  have_tables = c.prep_valid;
+  return TXM_OK;
+}
+// piv[1 + C] = the caller's pivot, or the one pivot_kernel computes from (x, u)
+static int fill_pivot(const double *given, const double *x, int64_t ldx_s, const ResampleCall &c, double *piv) {
+  if (given) {
+    TXM_HIP(hipMemcpyAsync(piv, given, sizeof(double) * (size_t)(1 + c.C), hipMemcpyDeviceToDevice, c.st));
   } else {
-    hipLaunchKernelGGL(pivot_kernel, dim3((unsigned)(1 + C)), dim3(256), 0, st, x, ldx_s, (int64_t)1,
-                       u, (int64_t)1, N, piv);
+    hipLaunchKernelGGL(pivot_kernel, dim3((unsigned)(1 + c.C)), dim3(256), 0, c.st, x, ldx_s, (int64_t)1, c.u, (int64_t)1, c.N, piv);
     TXM_LAUNCH_CHECK();
   }
+  return TXM_OK;
+}
+// the sampler words of the kernels' arguments (an explicit table: zeros)
+struct SamplerWords { uint32_t k0 = 0, k1 = 0, rep_base = 0; };
+static SamplerWords sampler_words(const ResampleCall &c) {
+  if (c.explicit_()) return {};
+  return {(uint32_t)c.spec->seed, (uint32_t)(c.spec->seed >> 32), (uint32_t)c.spec->rep0};
+}
+static uint32_t last_tile_size(int64_t N, int64_t ntiles) { return (uint32_t)(N - (ntiles - 1) * SM_T); }
+
+// THE fill of the FP64 kernel's arguments: plan, operands, sampler, partial-sum pointers.  Whatever a launch mode adds
+// (progress words, fallback lists, a state table) the caller sets on top; the rest stays null / zero.
+static ResampleArgs fp64_args(const ResampleCall &c, const ResamplePlan &p, const double *piv, double *part_x, double *part_u) {
+  const SamplerWords s = sampler_words(c);
   ResampleArgs a;
-  a.x = x; a.ldx_s = ldx_s; a.u = u; a.w = w; a.N = N; a.C = C; a.nrep = nrep;
-  a.freq = freq; a.counts = counts;
-  a.k0 = a.k1 = 0;
-  a.rep_base = 0;
+  a.x = c.x; a.ldx_s = c.ldx_s; a.u = c.u; a.w = c.w; a.N = c.N; a.C = c.C; a.nrep = c.nrep;
+  a.freq = c.freq; a.counts = c.counts;
+  a.k0 = s.k0; a.k1 = s.k1; a.rep_base = s.rep_base;
   a.ntiles = p.ntiles;
-  a.last_tile_size = (uint32_t)(N - (p.ntiles - 1) * SM_T);
-  if (!explicit_) {
-    TXM_REQUIRE(spec->ndat == N && spec->nrep == nrep, "resample_vals: sampler spec does not match N/nrep");
-    TXM_REQUIRE(spec->rep0 >= 0 && spec->rep0 + nrep <= ((int64_t)1 << 32), "resample_vals: sampler rep0 out of range");
-    a.k0 = (uint32_t)spec->seed;
-    a.k1 = (uint32_t)(spec->seed >> 32);
-    a.rep_base = (uint32_t)spec->rep0;
-  }
+  a.last_tile_size = last_tile_size(c.N, p.ntiles);
   a.pivot = piv;
-  a.part_x = (double *)((char *)ws + p.off_px);
-  a.part_u = (double *)((char *)ws + p.off_pu);
+  a.part_x = part_x;
+  a.part_u = part_u;
   a.n_chunks = p.n_chunks; a.n_rbg = p.n_rbg; a.tiles_per_chunk = p.tiles_per_chunk;
   a.nrep_pad = p.nrep_pad; a.C_pad = p.C_pad;
-  a.list = nullptr; a.n_list = nullptr; a.sub_tiles = 0; a.col_off = 0; a.batch = nullptr;
-  a.progress = nullptr;
+  return a;
+}
+// ... and of what the int8 kernels' arguments take from the call and the state's plan
+static I8Args i8_args(const ResampleCall &c, const I8Plan &q, const double *piv) {
+  const SamplerWords s = sampler_words(c);
+  I8Args b;
+  b.x = c.x; b.ldx_s = c.ldx_s; b.u = c.u; b.w = c.w; b.N = c.N; b.nrep = c.nrep; b.C_call = c.C;
+  b.counts = c.counts;
+  b.k0 = s.k0; b.k1 = s.k1; b.rep_base = s.rep_base;
+  b.ntiles = q.ntiles;
+  b.last_tile_size = last_tile_size(c.N, q.ntiles);
+  b.pivot = piv;
+  b.nwin = q.nwin;
+  b.n_rbg = q.n_rbg;
+  b.nrep_pad = q.nrep_pad;
+  b.win_tiles = q.win_tiles;
+  b.sub_tiles = q.sub_tiles;
+  return b;
+}
+
+// ---- the int8 call ------------------------------------------------------------------------------------------------------
+// What the column groups of a call share.
+struct I8CallState {
+  I8KernelChoice kernel;
+  unsigned char *pb;       // the pre-pass block
+  bool have_tables;        // ... holds the tables already
+  bool have_table = false; // the count table of the call's replicates has been generated
+};
+
+// One group of 32 columns (they reuse the partial buffers): pre-pass, contraction kernel (one launch, or two at orders 5-7),
+// the FP64 kernel in listed mode on the windows the precision guard flags (none on ordinary data), finalize -- then the
+// last two for the second matrix where the group's last pass carried it.  b, f: the call's arguments, completed here.
+static int resample_i8_group(const ResampleCall &c, const I8Plan &q, I8CallState &cs, int g, I8Args b, ResampleArgs f) {
+  const int K = c.K;
+  const int64_t C = c.C, nrep = c.nrep, col0 = (int64_t)g * I8_CPAD;
+  hipStream_t st = c.st;
+  unsigned char *pg = cs.pb + q.prep_group0 + (size_t)g * q.prep_group_stride;
+  b.wtab = (double *)(pg + q.L.p_wt);
+  b.wflag = (uint32_t *)(pg + q.L.p_flag);
+  b.list = (uint32_t *)(pg + q.L.p_list);
+  b.n_list = (uint32_t *)(pg + q.L.p_nlist);
+  b.ywtab = (double *)(pg + q.prep_ywt);
+  b.yflag = (uint32_t *)(pg + q.prep_yflag);
+  f.list = b.list; f.n_list = b.n_list;
+  b.col0 = col0;
+  b.C = C - col0 < I8_CPAD ? C - col0 : I8_CPAD;
+  // a tail group of <= 16 columns behind full groups runs the narrow-state variant (its own partial-sum row width) --
+  // unless a second matrix rides on the pass, which only the wide variant carries
+  const bool narrow_tail = C > I8_CPAD && b.C <= 16 && K >= 2 && !cs.kernel.with_y;
+  b.C_call = narrow_tail ? b.C : C;
+  b.cpad = i8_cpad(b.C_call, K);
+  if (!cs.have_tables)
+    if (const int rc = launch_i8_prepass(b, K, st)) return rc;
+  const bool table_kernel = cs.kernel.table_call && !narrow_tail;
+  if (table_kernel) {
+    unsigned char *table = (unsigned char *)c.ws + q.off_table;
+    if (!cs.have_table) {
+      if (const int rc = launch_count_table(c.counts, nrep, c.N, b.k0, b.k1, b.rep_base, 0, cdiv(nrep, G_REPS), table, st)) return rc;
+      cs.have_table = true;
+    }
+    I8Args bg = b;
+    bg.progress = nrep > G_REPS ? (uint32_t *)((char *)c.ws + q.off_gprog) : nullptr;
+    if (const int rc = C > 16 ? launch_resample_i8g(bg, K, c.weighted, table, 0, (int)cdiv(nrep, G_REPS), st)
+                              : launch_resample_i8gn(bg, K, c.weighted, table, 0, (int)cdiv(nrep, G_REPS), 0, st))
+      return rc;
+  } else {
+    if (const int rc = launch_resample_i8(b, K, c.weighted, q.prog_bytes, st)) return rc;
+  }
+  f.x = c.x + col0; f.C = b.C; f.col_off = col0;
+  if (const int rc = run_listed(f, q.fb, K, c.weighted, st)) return rc;
+  // (the slots' layout: digit sums where the fused narrow kernel with chunk groups wrote them, per-digit slots otherwise)
+  // (table-fed kernels: always -- txm_resample_i8gn.hip both x and u, txm_resample_i8g.hip x only; the fused kernel: its chunk-group instances)
+  // the fused kernel: narrow instances always, the wide one unless a second matrix rides the call (its finalize reads per-digit u slots)
+  const int fin_summed = table_kernel ? (C <= 16 ? 1 : 2)
+                                      : (i8t_narrow_nq(b.C_call, K) != 0 ? (i8t_partials_summed(b.C_call, K) ? 1 : 0) : b.part_summed);
+  if (const int rc = launch_finalize_i8(b, f, K, fin_summed, c.out, C, st)) return rc;
+  if (!cs.kernel.with_y) return TXM_OK;
+  // the windows the guard flagged (for either matrix): the FP64 kernel in listed mode on y, order 0
+  ResampleArgs fy = f;
+  fy.x = c.y + col0; fy.ldx_s = c.ldy_s; fy.pivot = b.ypivot;
+  fy.part_x = (double *)((char *)c.ws + q.off_fby);
+  fy.part_u = f.part_u + (size_t)q.fb.n_chunks * q.fb.nrep_pad * K;  // scratch behind x's u-row sums (unused by the finalize)
+  if (const int rc = run_listed(fy, q.fb, 1, c.weighted, st)) return rc;
+  return launch_finalize_y(b, fy, f.part_u, K, c.out_y, C, st);
+}
+
+// y / out_y: the second sample matrix of txm_resample_opts.  Carried by this call when the int8 kernel can take it
+// as a row set of its last pass (*y_done = true); otherwise left to the caller (a separate order-0 bootstrap).
+static int resample_i8_call(const ResampleCall &c, bool *y_done) {
+  const int K = c.K;
+  const int64_t C = c.C;
+  hipStream_t st = c.st;
+  const I8Plan q = plan_i8(c.N, C, c.nrep, K);
+  // wide states: the per-sample counts of the call's replicates as a table in HBM (built once, shared by the column groups
+  // and the passes) and the contraction kernel without a sampler inside (txm_resample_i8g.hip).  Misaligned operands and
+  // TXM_PATH_INT8_FUSED keep the kernel that draws in place; narrow states and narrow tail groups always run it.
+  I8CallState cs;
+  cs.kernel = i8_kernel_choice(q, c.path, c.N, C, c.nrep, K, c.y != nullptr,
+                               c.ws_bytes >= q.total_table && table_operands_ok(c.x, c.ldx_s, C, K, c.y, c.ldy_s));
+  const bool with_y = cs.kernel.with_y;
+  if (const int rc = check_workspace(c.fn, c.ws_bytes, q.total)) return rc;
+  if (const int rc = check_sampler(c)) return rc;
+  cs.pb = (unsigned char *)c.ws + q.off_prep;
+  if (const int rc = bind_prep(c, q.prep_total, cs.pb, cs.have_tables)) return rc;
+  double *piv = (double *)cs.pb;
+  double *ypiv = (double *)(cs.pb + q.prep_ypiv);
+  if (!cs.have_tables) {
+    if (const int rc = fill_pivot(c.pivot, c.x, c.ldx_s, c, piv)) return rc;
+    if (with_y) {
+      if (const int rc = fill_pivot(nullptr, c.y, c.ldy_s, c, ypiv)) return rc;
+      // one u pivot for the call (the monomial scales of both matrices are built on it)
+      TXM_HIP(hipMemcpyAsync(ypiv, piv, sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+  }
+  I8Args b = i8_args(c, q, piv);
+  b.stats = (double *)((char *)c.ws + q.L.s_stats);
+  b.part_x = (double *)((char *)c.ws + q.L.s_px);
+  b.part_u = (double *)((char *)c.ws + q.L.s_pu);
+  b.n_chunks = q.n_chunks; b.tiles_per_chunk = q.tiles_per_chunk;
+  b.y = with_y ? c.y : nullptr;
+  b.ldy_s = c.ldy_s;
+  b.ypivot = ypiv;
+  b.part_y = (double *)((char *)c.ws + q.off_py);
+  b.part_summed = i8t_wide_summed(with_y) ? 1 : 0;  // (what the wide fused kernel's instances of this call store: the finalize's mode)
+  b.progress = q.n_rbg > 1 ? (uint32_t *)((char *)c.ws + q.off_prog) : nullptr;
+  ResampleArgs f = fp64_args(c, q.fb, piv, (double *)((char *)c.ws + q.L.s_fbx), (double *)((char *)c.ws + q.L.s_fbu));
+  f.sub_tiles = q.sub_tiles;
+  TXM_REQUIRE(q.fb.nrep_pad == q.nrep_pad, "resample_vals: replicate padding of the two kernels differs");
+  for (int g = 0; g < q.ngroups; ++g)
+    if (const int rc = resample_i8_group(c, q, cs, g, b, f)) return rc;
+  if (with_y) *y_done = true;
+  // a reused prep block keeps its n_list words; a fresh one inside ws is what txm_resample_vals_info reads back
+  if (c.prep != nullptr)
+    TXM_HIP(hipMemcpyAsync((char *)c.ws + q.off_prep, cs.pb, q.prep_total, hipMemcpyDeviceToDevice, st));
+  if (c.info != nullptr) {
+    hipLaunchKernelGGL(i8_info_kernel, dim3(1), dim3(64), 0, st, cs.pb + q.prep_group0, q.prep_group_stride, q.L.p_nlist,
+                       q.ngroups, q.nwin, (cs.have_tables ? 1 : 0) | (cs.have_table ? 2 : 0), c.info);
+    TXM_LAUNCH_CHECK();
+  }
+  return TXM_OK;
+}
+
+// ---- the FP64 call ------------------------------------------------------------------------------------------------------
+static int resample_fp64_call(const ResampleCall &c) {
+  hipStream_t st = c.st;
+  if (c.info != nullptr) {
+    hipLaunchKernelGGL(fp64_info_kernel, dim3(1), dim3(64), 0, st, c.info);
+    TXM_LAUNCH_CHECK();
+  }
+  const ResamplePlan p = plan_resample(c.N, c.C, c.nrep, c.K);
+  if (const int rc = check_workspace(c.fn, c.ws_bytes, p.total)) return rc;
+  TXM_REQUIRE((int64_t)p.n_chunks * p.n_rbg < ((int64_t)1 << 31), "resample_vals: grid too large");
+  double *piv = (double *)((char *)c.ws + p.off_pivot);
+  if (const int rc = fill_pivot(c.pivot, c.x, c.ldx_s, c, piv)) return rc;
+  if (!c.explicit_())
+    if (const int rc = check_sampler(c)) return rc;
+  ResampleArgs a = fp64_args(c, p, piv, (double *)((char *)c.ws + p.off_px), (double *)((char *)c.ws + p.off_pu));
   if (p.n_rbg > 1 && a.N >= SM_T) {
-    a.progress = (uint32_t *)((char *)ws + p.off_prog);
+    a.progress = (uint32_t *)((char *)c.ws + p.off_prog);
     TXM_HIP(hipMemsetAsync(a.progress, 0, p.prog_bytes, st));
   }
-  TXM_K_SWITCH(K, return run_resample<KK>(a, p, w != nullptr, explicit_, out, st));
-  return TXM_OK;
+  return run_resample(a, p, c.K, c.weighted, c.explicit_(), c.out, st);
+}
+
+// the place that chooses between the int8 and the FP64 call
+static int resample_vals_impl(const ResampleCall &c, bool *y_done) {
+  *y_done = false;
+  if (!c.explicit_() && use_i8(c.N, c.C, c.nrep, c.K, c.path)) return resample_i8_call(c, y_done);
+  return resample_fp64_call(c);
 }
 }  // namespace txm
 
@@ -1440,45 +688,38 @@ extern "C" int txm_resample_vals(const double *x, int64_t ldx_s, int64_t ldx_c, 
   TXM_REQUIRE(order >= 0 && order <= TXM_MAX_ORDER, "resample_vals: order %d outside [0, %d]", order,
               TXM_MAX_ORDER);
   TXM_REQUIRE(ldx_c == 1 && ldx_s >= C, "resample_vals: x must be (rec, val) row-major (ldx_c == 1)");
-  if (!TXM_RESAMPLE_PITCH_OK(ldx_s, C)) {  // before anything is enqueued: the kernels' 32-bit lane offsets would wrap
-    set_error("resample_vals: row pitch ldx_s = %lld with C = %lld columns exceeds the limit 768 * ldx_s + C <= 2^29 = 536870912 (32-bit byte offsets inside a sampler tile); copy x to a tighter array",
-              (long long)ldx_s, (long long)C);
-    return TXM_ERR_UNSUPPORTED;
-  }
-  const bool explicit_ = freq != nullptr;
-  TXM_REQUIRE(explicit_ != (spec != nullptr && counts != nullptr),
+  if (const int rc = check_pitch("resample_vals", "x", ldx_s, C)) return rc;  // before anything is enqueued
+  TXM_REQUIRE((freq != nullptr) != (spec != nullptr && counts != nullptr),
               "resample_vals: give either freq or (spec, counts)");
-  txm_resample_opts o;
-  o.path = TXM_PATH_AUTO; o.prep_valid = 0; o.prep = nullptr; o.prep_bytes = 0; o.info = nullptr;
-  o.y = nullptr; o.ldy_s = 0; o.out_y = nullptr;
-  if (opts) o = *opts;
-  TXM_REQUIRE(o.path == TXM_PATH_AUTO || o.path == TXM_PATH_FP64 || o.path == TXM_PATH_INT8 || o.path == TXM_PATH_INT8_FUSED || o.path == TXM_PATH_INT8_TABLE,
-              "resample_vals: opts.path %d is not a path", (int)o.path);
-  TXM_REQUIRE((o.y == nullptr) == (o.out_y == nullptr), "resample_vals: opts.y and opts.out_y go together");
-  TXM_REQUIRE(o.y == nullptr || o.ldy_s >= C, "resample_vals: opts.ldy_s < C");
-  if (o.y != nullptr && !TXM_RESAMPLE_PITCH_OK(o.ldy_s, C)) {
-    set_error("resample_vals: row pitch opts.ldy_s = %lld with C = %lld columns exceeds the limit 768 * ldy_s + C <= 2^29 = 536870912 (32-bit byte offsets inside a sampler tile); copy y to a tighter array",
-              (long long)o.ldy_s, (long long)C);
-    return TXM_ERR_UNSUPPORTED;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const size_t main_bytes = txm_resample_vals_ws_bytes_opts(N, C, nrep, order, o.path, o.y != nullptr);
-  const size_t avail = ws_bytes < main_bytes ? ws_bytes : main_bytes;
+  ResampleCall c;
+  c.x = x; c.ldx_s = ldx_s; c.u = u; c.w = w; c.weighted = w != nullptr;
+  c.N = N; c.C = C; c.nrep = nrep; c.K = order + 1;
+  c.freq = freq; c.spec = spec; c.counts = counts; c.pivot = pivot; c.out = out;
+  if (const int rc = take_opts(c, opts)) return rc;
+  TXM_REQUIRE((c.y == nullptr) == (c.out_y == nullptr), "resample_vals: opts.y and opts.out_y go together");
+  TXM_REQUIRE(c.y == nullptr || c.ldy_s >= C, "resample_vals: opts.ldy_s < C");
+  if (c.y != nullptr)
+    if (const int rc = check_pitch("resample_vals", "y", c.ldy_s, C)) return rc;
+  const size_t main_bytes = txm_resample_vals_ws_bytes_opts(N, C, nrep, order, c.path, c.y != nullptr);
+  c.ws = ws; c.ws_bytes = ws_bytes < main_bytes ? ws_bytes : main_bytes; c.st = (hipStream_t)stream;
   bool y_done = false;
-  int rc = resample_vals_impl(x, ldx_s, u, w, N, C, order, nrep, freq, spec, counts, pivot, out, o.path, o.prep,
-                              o.prep_bytes, o.prep_valid != 0, o.info, ws, avail, st, o.y, o.ldy_s, o.out_y, &y_done);
-  if (rc != TXM_OK || o.y == nullptr || y_done) return rc;
+  int rc = resample_vals_impl(c, &y_done);
+  if (rc != TXM_OK || c.y == nullptr || y_done) return rc;
   // second sample matrix: an order-0 bootstrap on the same sampler draw, then its mean column
   if (ws_bytes < main_bytes + y_extra_bytes(N, C, nrep)) {
     set_error("resample_vals: workspace too small for opts.y (%zu < %zu)", ws_bytes, main_bytes + y_extra_bytes(N, C, nrep));
     return TXM_ERR_WORKSPACE;
   }
   double *ystates = (double *)((char *)ws + main_bytes);
-  void *yws = (char *)ws + main_bytes + align_up((size_t)nrep * C * 2 * sizeof(double), 256);
-  rc = resample_vals_impl(o.y, o.ldy_s, u, w, N, C, 0, nrep, freq, spec, counts, nullptr, ystates, o.path, nullptr, 0,
-                          false, nullptr, yws, y_main_bytes(N, C, nrep), st);
+  ResampleCall cy;  // (its own pivot, no pre-pass block, no info, no second matrix)
+  cy.x = c.y; cy.ldx_s = c.ldy_s; cy.u = u; cy.w = w; cy.weighted = c.weighted;
+  cy.N = N; cy.C = C; cy.nrep = nrep;
+  cy.freq = freq; cy.spec = spec; cy.counts = counts; cy.out = ystates; cy.path = c.path;
+  cy.ws = (char *)ws + main_bytes + align_up((size_t)nrep * C * 2 * sizeof(double), 256);
+  cy.ws_bytes = y_main_bytes(N, C, nrep); cy.st = c.st;
+  rc = resample_vals_impl(cy, &y_done);
   if (rc != TXM_OK) return rc;
-  hipLaunchKernelGGL(y_means_kernel, dim3((unsigned)cdiv(nrep * C, 256)), dim3(256), 0, st, ystates, nrep * C, o.out_y);
+  hipLaunchKernelGGL(y_means_kernel, dim3((unsigned)cdiv(nrep * C, 256)), dim3(256), 0, c.st, ystates, nrep * C, c.out_y);
   TXM_LAUNCH_CHECK();
   return TXM_OK;
 }
@@ -1513,10 +754,6 @@ static BatchPlan plan_batched(int64_t S, int64_t N, int64_t C, int64_t nrep, int
 // finalize) takes the state from a grid axis and its operands from an I8State table, so the batch is the same arithmetic
 // on the same per-window slots as S single calls: the same bits (tests/test_batched_gpu.py).
 namespace txm {
-struct I8StateLayout {
-  size_t stride, s_px, s_pu, s_fbx, s_fbu, s_stats;     // a state's scratch block in the workspace
-  size_t p_stride, p_wt, p_flag, p_list, p_nlist;       // a state's pre-pass block (workspace, or the caller's prep buffer)
-};
 struct BatchI8Plan {
   I8Plan q;                  // one state's plan: windows, replicate groups, the fallback's chunking
   int cpad, n_chunks;
@@ -1536,18 +773,10 @@ static BatchI8Plan plan_batched_i8(int64_t S, int64_t N, int64_t C, int64_t nrep
   if (nc > q.nwin) nc = cdiv(q.nwin, 8) * 8;
   b.tiles_per_chunk = cdiv(q.nwin, nc) * q.win_tiles;
   b.n_chunks = (int)(cdiv(cdiv(q.ntiles, b.tiles_per_chunk), 8) * 8);
+  // a state's tables as one column group's of the single call; its scratch with rows of cpad columns and no progress words
   I8StateLayout &L = b.L;
-  L.s_px = 0;
-  L.s_pu = L.s_px + align_up((size_t)q.nwin * q.nrep_pad * K * 8 * b.cpad * sizeof(double), 256);
-  L.s_fbx = L.s_pu + align_up((size_t)q.nwin * q.nrep_pad * K * 8 * sizeof(double), 256);
-  L.s_fbu = L.s_fbx + align_up((size_t)q.fb.n_chunks * q.fb.nrep_pad * q.fb.C_pad * K * sizeof(double), 256);
-  L.s_stats = L.s_fbu + align_up((size_t)q.fb.n_chunks * q.fb.nrep_pad * (K + 1) * sizeof(double), 256);
-  L.stride = L.s_stats + align_up((size_t)cdiv(q.ntiles, q.win_tiles < 16 ? q.win_tiles : 16) * 100 * sizeof(double), 256);
-  L.p_wt = 0;
-  L.p_flag = L.p_wt + align_up((size_t)q.nwin * I8_WT_STRIDE * sizeof(double) + 2048, 256);
-  L.p_list = L.p_flag + align_up((size_t)q.nwin * sizeof(uint32_t), 256);
-  L.p_nlist = L.p_list + align_up((size_t)q.nwin * (size_t)(q.win_tiles / q.sub_tiles) * sizeof(uint32_t), 256);
-  L.p_stride = L.p_nlist + 256;
+  L = q.L;
+  i8_layout_scratch(q, K, b.cpad, 0, L);
   b.prep_piv = 0;
   b.prep_state0 = align_up((size_t)S * (1 + C) * sizeof(double), 256);
   b.prep_total = b.prep_state0 + (size_t)S * L.p_stride;
@@ -1566,7 +795,7 @@ static BatchI8Plan plan_batched_i8(int64_t S, int64_t N, int64_t C, int64_t nrep
 // against 11.5 ms on the power-packed FP64 kernel (gpurun_out/r4_c5_probe.log).
 static bool use_i8_batched(int64_t S, int64_t N, int64_t C, int64_t nrep, int K, int call_path = TXM_PATH_AUTO) {
   if (!i8_supported(N, C, nrep, K) || i8t_narrow_nq(C, K) == 0) return false;
-  const int ov = call_path != TXM_PATH_AUTO ? call_path : path_override();
+  const int ov = effective_path(call_path);
   if (ov == TXM_PATH_FP64) return false;
   if (ov == TXM_PATH_INT8 || ov == TXM_PATH_INT8_FUSED || ov == TXM_PATH_INT8_TABLE) return true;
   // A rule on the STATE's shape only -- never on how many states share the launch: the states of a collection must take the
@@ -1612,121 +841,88 @@ __global__ void i8_batch_args_kernel(const I8Args base, int64_t S, I8Args *__res
   r.part_x = e.part_x; r.part_u = e.part_u; r.counts = e.counts; r.rep_base = e.rep_base;
   out[s] = r;
 }
-
-static int resample_batched_i8(const txm_state_ptrs *states_host, int64_t S, int64_t ldx_s, int64_t N, int64_t C, int K,
-                               int64_t nrep, bool weighted, const txm_sampler_spec *spec, const uint32_t *counts, double *out,
-                               void *prep, size_t prep_bytes, bool prep_valid, int64_t *info, void *ws, size_t ws_bytes,
-                               hipStream_t st) {
-  const BatchI8Plan b = plan_batched_i8(S, N, C, nrep, K);
+static int resample_batched_i8(const ResampleCall &c) {
+  const int64_t S = c.S, C = c.C;
+  const int K = c.K;
+  hipStream_t st = c.st;
+  const BatchI8Plan b = plan_batched_i8(S, c.N, C, c.nrep, K);
   const I8Plan &q = b.q;
-  if (ws_bytes < b.total) {
-    set_error("resample_vals_batched: workspace too small (%zu < %zu)", ws_bytes, b.total);
-    return TXM_ERR_WORKSPACE;
-  }
-  TXM_REQUIRE(spec->ndat == N && spec->nrep == S * nrep, "resample_vals_batched: the sampler must span S * nrep replicates of N samples");
-  TXM_REQUIRE(spec->rep0 >= 0 && spec->rep0 + spec->nrep <= ((int64_t)1 << 32), "resample_vals_batched: sampler replicates outside [0, 2^32)");
+  if (const int rc = check_workspace(c.fn, c.ws_bytes, b.total)) return rc;
+  if (const int rc = check_sampler(c)) return rc;
   TXM_REQUIRE((int64_t)b.n_chunks * q.n_rbg < ((int64_t)1 << 31) && S <= 65535, "resample_vals_batched: grid too large");
-  txm_state_ptrs *tab = (txm_state_ptrs *)((char *)ws + b.off_tab);
-  TXM_HIP(hipMemcpyAsync(tab, states_host, (size_t)S * sizeof(txm_state_ptrs), hipMemcpyHostToDevice, st));
-  // the pre-pass block (pivots, window tables, guard flags, fallback lists of the S states): the caller's persistent buffer
-  // (reused when prep_valid) or scratch in ws
-  unsigned char *pb = (unsigned char *)ws + b.off_prep;
-  bool have_tables = false;
-  if (prep != nullptr) {
-    if (prep_bytes < b.prep_total) {
-      set_error("resample_vals_batched: prep buffer too small (%zu < %zu)", prep_bytes, b.prep_total);
-      return TXM_ERR_WORKSPACE;
-    }
-    pb = (unsigned char *)prep;
-    have_tables = prep_valid;
-  }
+  txm_state_ptrs *tab = (txm_state_ptrs *)((char *)c.ws + b.off_tab);
+  TXM_HIP(hipMemcpyAsync(tab, c.states_host, (size_t)c.S * sizeof(txm_state_ptrs), hipMemcpyHostToDevice, st));
+  // the pre-pass block: pivots, window tables, guard flags, fallback lists of the S states
+  unsigned char *pb = (unsigned char *)c.ws + b.off_prep;
+  bool have_tables;
+  if (const int rc = bind_prep(c, b.prep_total, pb, have_tables)) return rc;
   double *piv = (double *)(pb + b.prep_piv);
   if (!have_tables) {
-    hipLaunchKernelGGL(pivot_batch_kernel, dim3((unsigned)(1 + C), (unsigned)S), dim3(256), 0, st, tab, ldx_s, N, C, piv);
+    hipLaunchKernelGGL(pivot_batch_kernel, dim3((unsigned)(1 + C), (unsigned)S), dim3(256), 0, st, tab, c.ldx_s, c.N, C, piv);
     TXM_LAUNCH_CHECK();
   }
-  I8State *states = (I8State *)((char *)ws + b.off_states);
-  hipLaunchKernelGGL(i8_states_kernel, dim3((unsigned)cdiv(S, 64)), dim3(64), 0, st, tab, S, (unsigned char *)ws + b.off_state0,
-                     pb + b.prep_state0, b.L, piv, C, counts, nrep, q.ntiles, out, K, (uint32_t)spec->rep0, states);
+  I8State *states = (I8State *)((char *)c.ws + b.off_states);
+  hipLaunchKernelGGL(i8_states_kernel, dim3((unsigned)cdiv(S, 64)), dim3(64), 0, st, tab, S, (unsigned char *)c.ws + b.off_state0,
+                     pb + b.prep_state0, b.L, piv, C, c.counts, c.nrep, q.ntiles, c.out, K, (uint32_t)c.spec->rep0, states);
   TXM_LAUNCH_CHECK();
-  bool vec_ok = ldx_s % 2 == 0;
-  for (int64_t s = 0; s < S; ++s) vec_ok = vec_ok && (reinterpret_cast<uintptr_t>(states_host[s].x) & 15) == 0;
-  I8Args a;
+  const txm_state_ptrs &h0 = c.states_host[0];  // (the kernels read the state table; the call's own operand words are state 0's)
+  bool vec_ok = c.ldx_s % 2 == 0;
+  for (int64_t s = 0; s < S; ++s) vec_ok = vec_ok && (reinterpret_cast<uintptr_t>(c.states_host[s].x) & 15) == 0;
+  I8Args a = i8_args(c, q, piv);
   a.states = states;
   a.S = S;
-  a.x = vec_ok ? states_host[0].x : reinterpret_cast<const double *>((uintptr_t)8);  // (the pre-pass reads its alignment only)
-  a.ldx_s = ldx_s; a.u = states_host[0].u; a.w = states_host[0].w; a.N = N; a.C = C; a.nrep = nrep;
-  a.col0 = 0; a.C_call = C;
+  a.x = vec_ok ? h0.x : reinterpret_cast<const double *>((uintptr_t)8);  // (the pre-pass reads its alignment only)
+  a.u = h0.u; a.w = h0.w; a.C = C;
   a.part_summed = 1;  // (narrow instances always store digit-summed slots; the field is the wide instance's)
-  a.counts = counts;
-  a.k0 = (uint32_t)spec->seed;
-  a.k1 = (uint32_t)(spec->seed >> 32);
-  a.rep_base = (uint32_t)spec->rep0;
-  a.ntiles = q.ntiles;
-  a.last_tile_size = (uint32_t)(N - (q.ntiles - 1) * SM_T);
-  a.pivot = piv; a.wtab = nullptr; a.stats = nullptr; a.nwin = q.nwin;
-  a.part_x = nullptr; a.cpad = b.cpad; a.part_u = nullptr;
-  a.y = nullptr; a.ldy_s = 0; a.ypivot = nullptr; a.ywtab = nullptr; a.yflag = nullptr; a.part_y = nullptr;
-  a.n_chunks = b.n_chunks; a.n_rbg = q.n_rbg; a.tiles_per_chunk = b.tiles_per_chunk; a.win_tiles = q.win_tiles;
-  a.nrep_pad = q.nrep_pad;
-  a.wflag = nullptr; a.list = nullptr; a.n_list = nullptr; a.sub_tiles = q.sub_tiles;
-  a.progress = nullptr;
-  I8Args *bargs = (I8Args *)((char *)ws + b.off_bargs);
+  a.cpad = b.cpad;
+  a.n_chunks = b.n_chunks; a.tiles_per_chunk = b.tiles_per_chunk;
+  I8Args *bargs = (I8Args *)((char *)c.ws + b.off_bargs);
   hipLaunchKernelGGL(i8_batch_args_kernel, dim3((unsigned)cdiv(S, 64)), dim3(64), 0, st, a, S, bargs);
   TXM_LAUNCH_CHECK();
   a.batch_args = bargs;
-  int rc = have_tables ? TXM_OK : launch_i8_prepass(a, K, st);
-  if (rc != TXM_OK) return rc;
-  rc = launch_resample_i8t(a, K, weighted, 0, st);
-  if (rc != TXM_OK) return rc;
+  if (!have_tables)
+    if (const int rc = launch_i8_prepass(a, K, st)) return rc;
+  if (const int rc = launch_resample_i8t(a, K, c.weighted, 0, st)) return rc;
   // the windows the precision guard flags, state by state on grid axis z (a state with an empty list: its blocks exit)
-  ResampleArgs f;
-  f.x = states_host[0].x; f.ldx_s = ldx_s; f.u = states_host[0].u; f.w = states_host[0].w; f.N = N; f.C = C; f.nrep = nrep;
-  f.freq = nullptr; f.counts = counts;
-  f.k0 = a.k0; f.k1 = a.k1; f.rep_base = a.rep_base;
-  f.ntiles = q.ntiles; f.last_tile_size = a.last_tile_size;
-  f.pivot = piv; f.part_x = nullptr; f.part_u = nullptr;
-  f.n_chunks = q.fb.n_chunks; f.n_rbg = q.fb.n_rbg; f.tiles_per_chunk = q.fb.tiles_per_chunk;
-  f.nrep_pad = q.fb.nrep_pad; f.C_pad = q.fb.C_pad;
-  f.list = nullptr; f.n_list = nullptr; f.sub_tiles = q.sub_tiles; f.col_off = 0; f.batch = nullptr; f.progress = nullptr;
+  ResampleArgs f = fp64_args(c, q.fb, piv, nullptr, nullptr);
+  f.x = h0.x; f.u = h0.u; f.w = h0.w;
+  f.sub_tiles = q.sub_tiles;
   f.i8states = states;
   TXM_REQUIRE(q.fb.nrep_pad == q.nrep_pad, "resample_vals_batched: replicate padding of the two kernels differs");
-  rc = run_listed(f, q.fb, K, weighted, st, S);
-  if (rc != TXM_OK) return rc;
-  const int bfin_summed = i8t_partials_summed(C, K) ? 1 : 0;  // (batched launches always run the fused narrow kernel)
-#define TXM_I8_BFIN2(KK, CP)                                                                                        \
-  hipLaunchKernelGGL((resample_finalize_i8_kernel<KK, CP>), dim3((unsigned)nrep, (unsigned)S), dim3(256), 0, st, nullptr, \
-                     nullptr, q.nwin, nullptr, q.nrep_pad, nrep, C, nullptr, nullptr, (int64_t)0, C, nullptr, nullptr,      \
-                     q.fb.n_chunks, q.fb.C_pad, nullptr, states, bfin_summed)
-#define TXM_I8_BFIN(KK)                                  \
-  do {                                                   \
-    if (b.cpad == 16) TXM_I8_BFIN2(KK, 16);              \
-    else if (b.cpad == 8) TXM_I8_BFIN2(KK, 8);           \
-    else TXM_I8_BFIN2(KK, 4);                            \
-  } while (0)
-  switch (K) {
-    case 2: TXM_I8_BFIN(2); break;
-    case 3: TXM_I8_BFIN(3); break;
-    case 4: TXM_I8_BFIN(4); break;
-    case 5: TXM_I8_BFIN(5); break;
-    case 6: TXM_I8_BFIN(6); break;
-    case 7: TXM_I8_BFIN(7); break;
-    default: TXM_I8_BFIN(8); break;
-  }
-#undef TXM_I8_BFIN
-#undef TXM_I8_BFIN2
-  TXM_LAUNCH_CHECK();
-  if (info != nullptr) {
+  if (const int rc = run_listed(f, q.fb, K, c.weighted, st, S)) return rc;
+  // (batched launches always run the fused narrow kernel)
+  if (const int rc = launch_finalize_i8(a, f, K, i8t_partials_summed(C, K) ? 1 : 0, nullptr, C, st)) return rc;
+  if (c.info != nullptr) {
     hipLaunchKernelGGL(i8_info_kernel, dim3(1), dim3(64), 0, st, pb + b.prep_state0, b.L.p_stride, b.L.p_nlist, (int)S, q.nwin,
-                       have_tables ? 1 : 0, info);
+                       have_tables ? 1 : 0, c.info);
     TXM_LAUNCH_CHECK();
   }
   return TXM_OK;
 }
+
+static int resample_batched_fp64(const ResampleCall &c) {
+  hipStream_t st = c.st;
+  if (c.info != nullptr) {
+    hipLaunchKernelGGL(fp64_info_kernel, dim3(1), dim3(64), 0, st, c.info);
+    TXM_LAUNCH_CHECK();
+  }
+  const BatchPlan b = plan_batched(c.S, c.N, c.C, c.nrep, c.K);
+  if (const int rc = check_workspace(c.fn, c.ws_bytes, b.total)) return rc;
+  txm_state_ptrs *tab = (txm_state_ptrs *)((char *)c.ws + b.off_tab);
+  TXM_HIP(hipMemcpyAsync(tab, c.states_host, (size_t)c.S * sizeof(txm_state_ptrs), hipMemcpyHostToDevice, st));
+  double *piv = (double *)((char *)c.ws + b.off_pivot);
+  hipLaunchKernelGGL(pivot_batch_kernel, dim3((unsigned)(1 + c.C), (unsigned)c.S), dim3(256), 0, st, tab, c.ldx_s, c.N, c.C, piv);
+  TXM_LAUNCH_CHECK();
+  if (!c.explicit_())
+    if (const int rc = check_sampler(c)) return rc;
+  ResampleArgs a = fp64_args(c, b.one, piv, (double *)((char *)c.ws + b.off_px), (double *)((char *)c.ws + b.off_pu));
+  a.batch = tab;
+  return run_resample(a, b.one, c.K, c.weighted, c.explicit_(), c.out, st, c.S);
+}
 }  // namespace txm
 
 extern "C" size_t txm_resample_vals_batched_ws_bytes(int64_t S, int64_t N, int64_t C, int64_t nrep, int order) {
-  if (S < 1 || N < 1 || C < 1 || nrep < 1 || order < 0 || order > TXM_MAX_ORDER) return 0;
+  if (S < 1 || !shape_ok(N, C, nrep, order)) return 0;
   // (the larger of the two paths: which one a call takes may be forced per process, txm_set_resample_path)
   const size_t f = plan_batched(S, N, C, nrep, order + 1).total;
   if (!i8_supported(N, C, nrep, order + 1) || i8t_narrow_nq(C, order + 1) == 0) return f;
@@ -1737,12 +933,12 @@ extern "C" size_t txm_resample_vals_batched_ws_bytes(int64_t S, int64_t N, int64
 // the kernel a TXM_PATH_AUTO batched call takes (the batched counterpart of txm_resample_path): callers that keep a
 // pre-pass block bind it only when the call really runs the int8 path
 extern "C" int txm_resample_batched_path(int64_t S, int64_t N, int64_t C, int64_t nrep, int order) {
-  if (S < 1 || N < 1 || C < 1 || nrep < 1 || order < 0 || order > TXM_MAX_ORDER) return TXM_PATH_FP64;
+  if (S < 1 || !shape_ok(N, C, nrep, order)) return TXM_PATH_FP64;
   return use_i8_batched(S, N, C, nrep, order + 1) ? TXM_PATH_INT8 : TXM_PATH_FP64;
 }
 
 extern "C" size_t txm_resample_batched_prep_bytes(int64_t S, int64_t N, int64_t C, int64_t nrep, int order) {
-  if (S < 1 || N < 1 || C < 1 || nrep < 1 || order < 0 || order > TXM_MAX_ORDER) return 0;
+  if (S < 1 || !shape_ok(N, C, nrep, order)) return 0;
   if (!i8_supported(N, C, nrep, order + 1) || i8t_narrow_nq(C, order + 1) == 0) return 0;
   return plan_batched_i8(S, N, C, nrep, order + 1).prep_total;
 }
@@ -1759,69 +955,25 @@ extern "C" int txm_resample_vals_batched_opts(const txm_state_ptrs *states_host,
                                               int64_t C, int order, int64_t nrep, const int64_t *freq,
                                               const txm_sampler_spec *spec, const uint32_t *counts, double *out,
                                               const txm_resample_opts *opts, void *ws, size_t ws_bytes, txm_stream stream) {
-  const int call_path = opts ? opts->path : TXM_PATH_AUTO;
-  TXM_REQUIRE(call_path == TXM_PATH_AUTO || call_path == TXM_PATH_FP64 || call_path == TXM_PATH_INT8 || call_path == TXM_PATH_INT8_FUSED || call_path == TXM_PATH_INT8_TABLE,
-              "resample_vals_batched: opts.path %d is not a path", call_path);
-  TXM_REQUIRE(!(opts && (opts->y || opts->out_y)), "resample_vals_batched: no second sample matrix on the batched entry");
+  ResampleCall c;
+  c.fn = "resample_vals_batched";
+  if (const int rc = take_opts(c, opts)) return rc;
+  TXM_REQUIRE(!(c.y || c.out_y), "resample_vals_batched: no second sample matrix on the batched entry");
   TXM_REQUIRE(states_host && out && ws, "resample_vals_batched: null pointer");
   TXM_REQUIRE(S >= 1 && S <= 65535 && N >= 1 && C >= 1 && nrep >= 1, "resample_vals_batched: need S, N, C, nrep >= 1");
   TXM_REQUIRE(order >= 0 && order <= TXM_MAX_ORDER, "resample_vals_batched: order %d outside [0, %d]", order, TXM_MAX_ORDER);
   TXM_REQUIRE(ldx_s >= C, "resample_vals_batched: row pitch ldx_s < C");
-  if (!TXM_RESAMPLE_PITCH_OK(ldx_s, C)) {
-    set_error("resample_vals_batched: row pitch ldx_s = %lld with C = %lld columns exceeds the limit 768 * ldx_s + C <= 2^29 = 536870912 (32-bit byte offsets inside a sampler tile); copy x to a tighter array",
-              (long long)ldx_s, (long long)C);
-    return TXM_ERR_UNSUPPORTED;
-  }
-  const bool explicit_ = freq != nullptr;
-  TXM_REQUIRE(explicit_ != (spec != nullptr && counts != nullptr), "resample_vals_batched: give either freq or (spec, counts)");
-  const bool weighted = states_host[0].w != nullptr;
+  if (const int rc = check_pitch(c.fn, "x", ldx_s, C)) return rc;
+  TXM_REQUIRE((freq != nullptr) != (spec != nullptr && counts != nullptr), "resample_vals_batched: give either freq or (spec, counts)");
+  c.weighted = states_host[0].w != nullptr;
   for (int64_t s = 0; s < S; ++s) {
     TXM_REQUIRE(states_host[s].x && states_host[s].u, "resample_vals_batched: state %lld has a null pointer", (long long)s);
-    TXM_REQUIRE((states_host[s].w != nullptr) == weighted, "resample_vals_batched: weights for all states or for none");
+    TXM_REQUIRE((states_host[s].w != nullptr) == c.weighted, "resample_vals_batched: weights for all states or for none");
   }
-  const int K = order + 1;
-  if (!explicit_ && use_i8_batched(S, N, C, nrep, K, call_path))
-    return resample_batched_i8(states_host, S, ldx_s, N, C, K, nrep, weighted, spec, counts, out, opts ? opts->prep : nullptr,
-                               opts ? opts->prep_bytes : 0, opts && opts->prep_valid != 0, opts ? opts->info : nullptr, ws, ws_bytes,
-                               (hipStream_t)stream);
-  if (opts && opts->info != nullptr) {
-    hipLaunchKernelGGL(fp64_info_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, opts->info);
-    TXM_LAUNCH_CHECK();
-  }
-  const BatchPlan b = plan_batched(S, N, C, nrep, K);
-  if (ws_bytes < b.total) {
-    set_error("resample_vals_batched: workspace too small (%zu < %zu)", ws_bytes, b.total);
-    return TXM_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  txm_state_ptrs *tab = (txm_state_ptrs *)((char *)ws + b.off_tab);
-  TXM_HIP(hipMemcpyAsync(tab, states_host, (size_t)S * sizeof(txm_state_ptrs), hipMemcpyHostToDevice, st));
-  double *piv = (double *)((char *)ws + b.off_pivot);
-  hipLaunchKernelGGL(pivot_batch_kernel, dim3((unsigned)(1 + C), (unsigned)S), dim3(256), 0, st, tab, ldx_s, N, C, piv);
-  TXM_LAUNCH_CHECK();
-  const ResamplePlan &p = b.one;
-  ResampleArgs a;
-  a.x = nullptr; a.ldx_s = ldx_s; a.u = nullptr; a.w = nullptr; a.N = N; a.C = C; a.nrep = nrep;
-  a.freq = freq; a.counts = counts;
-  a.k0 = a.k1 = 0;
-  a.rep_base = 0;
-  a.ntiles = p.ntiles;
-  a.last_tile_size = (uint32_t)(N - (p.ntiles - 1) * SM_T);
-  if (!explicit_) {
-    TXM_REQUIRE(spec->ndat == N && spec->nrep == S * nrep, "resample_vals_batched: the sampler must span S * nrep replicates of N samples");
-    TXM_REQUIRE(spec->rep0 >= 0 && spec->rep0 + spec->nrep <= ((int64_t)1 << 32), "resample_vals_batched: sampler replicates outside [0, 2^32)");
-    a.k0 = (uint32_t)spec->seed;
-    a.k1 = (uint32_t)(spec->seed >> 32);
-    a.rep_base = (uint32_t)spec->rep0;
-  }
-  a.pivot = piv;
-  a.part_x = (double *)((char *)ws + b.off_px);
-  a.part_u = (double *)((char *)ws + b.off_pu);
-  a.n_chunks = p.n_chunks; a.n_rbg = p.n_rbg; a.tiles_per_chunk = p.tiles_per_chunk;
-  a.nrep_pad = p.nrep_pad; a.C_pad = p.C_pad;
-  a.list = nullptr; a.n_list = nullptr; a.sub_tiles = 0; a.col_off = 0;
-  a.batch = tab;
-  a.progress = nullptr;
-  TXM_K_SWITCH(K, return run_resample<KK>(a, p, weighted, explicit_, out, st, S));
-  return TXM_OK;
+  c.states_host = states_host; c.S = S; c.ldx_s = ldx_s;
+  c.N = N; c.C = C; c.nrep = nrep; c.K = order + 1;
+  c.freq = freq; c.spec = spec; c.counts = counts; c.out = out;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
+  if (!c.explicit_() && use_i8_batched(S, N, C, nrep, c.K, c.path)) return resample_batched_i8(c);
+  return resample_batched_fp64(c);
 }

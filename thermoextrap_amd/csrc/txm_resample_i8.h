@@ -49,50 +49,50 @@ struct I8Args {
   const I8State *states = nullptr;  // batched launch: state blockIdx.y (narrow-state kernels only); nullptr: one state
   const I8Args *batch_args = nullptr;  // ... and the bootstrap kernel's own arguments per state (device array [S], built per call)
   int64_t S = 1;
-  const double *x;
-  int64_t ldx_s;
-  const double *u;
-  const double *w;
-  int64_t N, C, nrep;      // C <= 32: the columns col0 .. col0 + C - 1 of x (one column group per launch)
-  int64_t col0;
-  int64_t C_call;          // all columns of the call (decides the kernel family: i8t_applicable)
-  const uint32_t *counts;  // [nrep][ntiles]
-  uint32_t k0, k1;
-  uint32_t rep_base;       // replicate r of the call draws stream replicate rep_base + r (txm_sampler_spec.rep0)
-  int64_t ntiles;
-  uint32_t last_tile_size;
-  const double *pivot;     // [1 + all columns]: {pivot_u, pivot_x[...]}, indexed with col0
-  double *wtab;            // [nwin][I8_WT_STRIDE]
-  double *stats;           // [ceil(ntiles / min(16, win_tiles))][100] per-sub-block statistics of the pre-pass
-  int64_t nwin;
+  const double *x = nullptr;
+  int64_t ldx_s = 0;
+  const double *u = nullptr;
+  const double *w = nullptr;
+  int64_t N = 0, C = 0, nrep = 0;   // C <= 32: the columns col0 .. col0 + C - 1 of x (one column group per launch)
+  int64_t col0 = 0;
+  int64_t C_call = 0;               // all columns of the call (decides the kernel family: i8t_applicable)
+  const uint32_t *counts = nullptr;  // [nrep][ntiles]
+  uint32_t k0 = 0, k1 = 0;
+  uint32_t rep_base = 0;            // replicate r of the call draws stream replicate rep_base + r (txm_sampler_spec.rep0)
+  int64_t ntiles = 0;
+  uint32_t last_tile_size = 0;
+  const double *pivot = nullptr;    // [1 + all columns]: {pivot_u, pivot_x[...]}, indexed with col0
+  double *wtab = nullptr;           // [nwin][I8_WT_STRIDE]
+  double *stats = nullptr;          // [ceil(ntiles / min(16, win_tiles))][100] per-sub-block statistics of the pre-pass
+  int64_t nwin = 0;
   // partial sums: ONE SLOT PER SCALING WINDOW, written once (no read-modify-write, no zeroing; the finalize kernel
   // skips the windows the guard flagged and adds the rest in window order, so a replicate's sums do not depend on the
   // launch geometry)
-  double *part_x;          // [nwin][nrep_pad][K][8 digit slots][cpad columns], or digit-summed [nwin][nrep_pad][K][cpad] (part_summed)
-  int cpad;                // columns of a row of part_x: 32, or 4 / 8 where the narrow-state kernel runs (i8_cpad)
-  double *part_u;          // [nwin][nrep_pad][K][8 digit slots]
-  int part_summed;         // wide fused kernel: 1 = store digit-summed slots [nwin][nrep_pad][K][cpad] / [nwin][nrep_pad][K] (the narrow
-                           // kernels always do, the wide table-fed kernel for x only: see resample_finalize_i8_kernel's `summed`)
+  double *part_x = nullptr;         // [nwin][nrep_pad][K][8 digit slots][cpad columns], or digit-summed [nwin][nrep_pad][K][cpad] (part_summed)
+  int cpad = 0;                     // columns of a row of part_x: 32, or 4 / 8 where the narrow-state kernel runs (i8_cpad)
+  double *part_u = nullptr;         // [nwin][nrep_pad][K][8 digit slots]
+  int part_summed = 0;              // wide fused kernel: 1 = store digit-summed slots [nwin][nrep_pad][K][cpad] / [nwin][nrep_pad][K] (the narrow
+                                    // kernels always do, the wide table-fed kernel for x only: see resample_finalize_i8_kernel's `summed`)
   // optional second sample matrix (txm_resample_opts.y): order-0 sums sum_i f w (y_c - py_c) of its 32 columns, carried
   // as one more row set of the LAST pass of the transposing-read kernel (nullptr: none)
-  const double *y;
-  int64_t ldy_s;
-  const double *ypivot;    // [1 + all columns]: {pivot_u, pivot_y[...]}
-  double *ywtab;           // [nwin][I8_WT_STRIDE]: the window table of y (column scales of y)
-  uint32_t *yflag;         // [nwin] guard flags of y, OR-ed into wflag by the pre-pass
-  double *part_y;          // [nwin][nrep_pad][8 digit slots][32 columns]
-  int n_chunks, n_rbg;
-  int64_t tiles_per_chunk; // multiple of win_tiles
-  int64_t win_tiles;       // sampler tiles per scaling window: 256, 64, 16 or 4
-  int64_t nrep_pad;
+  const double *y = nullptr;
+  int64_t ldy_s = 0;
+  const double *ypivot = nullptr;   // [1 + all columns]: {pivot_u, pivot_y[...]}
+  double *ywtab = nullptr;          // [nwin][I8_WT_STRIDE]: the window table of y (column scales of y)
+  uint32_t *yflag = nullptr;        // [nwin] guard flags of y, OR-ed into wflag by the pre-pass
+  double *part_y = nullptr;         // [nwin][nrep_pad][8 digit slots][32 columns]
+  int n_chunks = 0, n_rbg = 0;
+  int64_t tiles_per_chunk = 0;      // multiple of win_tiles
+  int64_t win_tiles = 0;            // sampler tiles per scaling window: 256, 64, 16 or 4
+  int64_t nrep_pad = 0;
   // precision guard: flag[w] != 0 -> window w is left to the FP64 kernel (run list built by i8_list_kernel)
-  uint32_t *wflag;         // [nwin]
-  uint32_t *list;          // [nwin * (win_tiles / sub_tiles)] first tile of every run; n_list[0] = runs, n_list[1] = flagged windows
-  uint32_t *n_list;
-  int sub_tiles;           // tiles per run: min(I8_SUB_TILES, win_tiles)
-  // L2-sharing hint (see ResampleArgs::progress in txm_resample.hip): the replicate groups of a chunk publish the
+  uint32_t *wflag = nullptr;        // [nwin]
+  uint32_t *list = nullptr;         // [nwin * (win_tiles / sub_tiles)] first tile of every run; n_list[0] = runs, n_list[1] = flagged windows
+  uint32_t *n_list = nullptr;
+  int sub_tiles = 0;                // tiles per run: min(I8_SUB_TILES, win_tiles)
+  // L2-sharing hint (see ResampleArgs::progress in txm_resample_fp64.h): the replicate groups of a chunk publish the
   // tiles they have finished and stay within I8_LEAD tiles of each other, so that the chunk is streamed from HBM once
-  uint32_t *progress;      // [n_chunks][64], zeroed by the launcher; nullptr: off
+  uint32_t *progress = nullptr;     // [n_chunks][64], zeroed by the launcher; nullptr: off
 };
 constexpr uint32_t I8_LEAD = 2;
 constexpr int I8_THROTTLE_SPINS = 48;

@@ -16,7 +16,7 @@
 //   flushed per window into the window's own FP64 slot per digit (x 256^i x the window descale).
 //   Rounding: one rint per monomial at 2^-51 of the WINDOW maximum (unbiased) -- which is only harmless while the
 //   window's typical monomial is not dwarfed by its maximum: the guard below checks exactly that, per window and column,
-//   and hands the windows that fail to the FP64 kernel (txm_resample.hip, listed mode) inside the same call.
+//   and hands the windows that fail to the FP64 kernel (txm_resample_fp64.hip, listed mode) inside the same call.
 #include "txm_resample_i8.h"
 
 #include <stdlib.h>
