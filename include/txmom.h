@@ -177,7 +177,7 @@ typedef struct txm_sampler_spec {
 /* Per-(replicate, tile) draw counts, tile = 1024 consecutive samples.
  * counts: [nrep][txm_sampler_ntiles(ndat)] uint32.  ndat <= 2^30, nrep <= 2^24; the workspace
  * is no longer used (the tile tree lives in LDS) but the query still returns a
- * valid size and the arguments are accepted. */
+ * valid size and ws_bytes is held to it like everywhere else (TXM_ERR_WORKSPACE). */
 int64_t txm_sampler_ntiles(int64_t ndat);
 size_t txm_sampler_counts_ws_bytes(const txm_sampler_spec *spec_host);
 int txm_sampler_tile_counts(const txm_sampler_spec *spec_host, uint32_t *counts, void *ws,
@@ -322,7 +322,8 @@ size_t txm_resample_vals_ws_bytes(int64_t N, int64_t C, int64_t nrep, int order)
 /* the same for a call that will pass txm_resample_opts.path = `path` and a second matrix iff has_y: the int8 path's count-table
  * kernel (wide states; txm_resample_vals_ws_bytes = path TXM_PATH_AUTO, has_y 0) keeps one byte per (replicate padded to 128,
  * sample) in the workspace -- 12.8 GB per 128 replicates at N = 1e8.  A call given less workspace than this, but at least
- * what TXM_PATH_INT8_FUSED needs, runs the kernel that draws the counts in place: same bits, other speed.  Callers bound the
+ * what TXM_PATH_INT8_FUSED needs, runs the kernel that draws the counts in place: same bits, other speed; less than that is
+ * refused (TXM_ERR_WORKSPACE) before anything is enqueued, whichever kernel the call would have taken.  Callers bound the
  * workspace by bootstrapping replicate slabs (spec.rep0): rows [a, b) of a call equal the (b - a)-replicate call at rep0 = a. */
 size_t txm_resample_vals_ws_bytes_opts(int64_t N, int64_t C, int64_t nrep, int order, int path, int has_y);
 /* extra workspace, BEHIND txm_resample_vals_ws_bytes(), that a call with opts.y needs (ws_bytes >= the sum); a call

@@ -594,6 +594,17 @@ static int resample_i8_group(const ResampleCall &c, const I8Plan &q, I8CallState
 
 // y / out_y: the second sample matrix of txm_resample_opts.  Carried by this call when the int8 kernel can take it
 // as a row set of its last pass (*y_done = true); otherwise left to the caller (a separate order-0 bootstrap).
+// THE kernel choice of an int8 call from what it was handed (plan, path, operands, workspace): the count-table kernel only
+// when the workspace holds the table and the operands suit its DMA; with_y: the kernel carries opts.y as a row set
+static I8KernelChoice i8_call_kernel(const ResampleCall &c, const I8Plan &q) {
+  return i8_kernel_choice(q, c.path, c.N, c.C, c.nrep, c.K, c.y != nullptr,
+                          c.ws_bytes >= q.total_table && table_operands_ok(c.x, c.ldx_s, c.C, c.K, c.y, c.ldy_s));
+}
+// does this call bootstrap opts.y inside its own kernel (no separate order-0 pass, no extra workspace behind the main plan)?
+static bool call_carries_y(const ResampleCall &c) {
+  if (c.y == nullptr || c.explicit_() || !use_i8(c.N, c.C, c.nrep, c.K, c.path)) return false;
+  return i8_call_kernel(c, plan_i8(c.N, c.C, c.nrep, c.K)).with_y;
+}
 static int resample_i8_call(const ResampleCall &c, bool *y_done) {
   const int K = c.K;
   const int64_t C = c.C;
@@ -603,8 +614,7 @@ static int resample_i8_call(const ResampleCall &c, bool *y_done) {
   // and the passes) and the contraction kernel without a sampler inside (txm_resample_i8g.hip).  Misaligned operands and
   // TXM_PATH_INT8_FUSED keep the kernel that draws in place; narrow states and narrow tail groups always run it.
   I8CallState cs;
-  cs.kernel = i8_kernel_choice(q, c.path, c.N, C, c.nrep, K, c.y != nullptr,
-                               c.ws_bytes >= q.total_table && table_operands_ok(c.x, c.ldx_s, C, K, c.y, c.ldy_s));
+  cs.kernel = i8_call_kernel(c, q);
   const bool with_y = cs.kernel.with_y;
   if (const int rc = check_workspace(c.fn, c.ws_bytes, q.total)) return rc;
   if (const int rc = check_sampler(c)) return rc;
@@ -702,14 +712,18 @@ extern "C" int txm_resample_vals(const double *x, int64_t ldx_s, int64_t ldx_c, 
     if (const int rc = check_pitch("resample_vals", "y", c.ldy_s, C)) return rc;
   const size_t main_bytes = txm_resample_vals_ws_bytes_opts(N, C, nrep, order, c.path, c.y != nullptr);
   c.ws = ws; c.ws_bytes = ws_bytes < main_bytes ? ws_bytes : main_bytes; c.st = (hipStream_t)stream;
+  // The queries are the larger of the two paths' plans rounded up to 256 bytes, so a path's own check cannot hold a call to
+  // them: refuse here, before anything is enqueued, whatever is less than the query WITHOUT the count table (a workspace
+  // between that and the query with it is the documented way onto the kernel that draws in place) ...
+  if (const int rc = check_workspace(c.fn, ws_bytes, txm_resample_vals_ws_bytes_opts(N, C, nrep, order, TXM_PATH_INT8_FUSED, c.y != nullptr)))
+    return rc;
+  // ... and a second matrix's extra workspace, unless the call's kernel carries y
+  if (c.y != nullptr && !call_carries_y(c))
+    if (const int rc = check_workspace(c.fn, ws_bytes, main_bytes + y_extra_bytes(N, C, nrep))) return rc;
   bool y_done = false;
   int rc = resample_vals_impl(c, &y_done);
   if (rc != TXM_OK || c.y == nullptr || y_done) return rc;
-  // second sample matrix: an order-0 bootstrap on the same sampler draw, then its mean column
-  if (ws_bytes < main_bytes + y_extra_bytes(N, C, nrep)) {
-    set_error("resample_vals: workspace too small for opts.y (%zu < %zu)", ws_bytes, main_bytes + y_extra_bytes(N, C, nrep));
-    return TXM_ERR_WORKSPACE;
-  }
+  // second sample matrix: an order-0 bootstrap on the same sampler draw, then its mean column (behind the main plan: checked above)
   double *ystates = (double *)((char *)ws + main_bytes);
   ResampleCall cy;  // (its own pivot, no pre-pass block, no info, no second matrix)
   cy.x = c.y; cy.ldx_s = c.ldy_s; cy.u = u; cy.w = w; cy.weighted = c.weighted;
@@ -850,12 +864,13 @@ static int resample_batched_i8(const ResampleCall &c) {
   if (const int rc = check_workspace(c.fn, c.ws_bytes, b.total)) return rc;
   if (const int rc = check_sampler(c)) return rc;
   TXM_REQUIRE((int64_t)b.n_chunks * q.n_rbg < ((int64_t)1 << 31) && S <= 65535, "resample_vals_batched: grid too large");
-  txm_state_ptrs *tab = (txm_state_ptrs *)((char *)c.ws + b.off_tab);
-  TXM_HIP(hipMemcpyAsync(tab, c.states_host, (size_t)c.S * sizeof(txm_state_ptrs), hipMemcpyHostToDevice, st));
-  // the pre-pass block: pivots, window tables, guard flags, fallback lists of the S states
+  // the pre-pass block: pivots, window tables, guard flags, fallback lists of the S states (a short caller-held block is
+  // refused here, before the state table goes into the workspace: a refused call writes nothing)
   unsigned char *pb = (unsigned char *)c.ws + b.off_prep;
   bool have_tables;
   if (const int rc = bind_prep(c, b.prep_total, pb, have_tables)) return rc;
+  txm_state_ptrs *tab = (txm_state_ptrs *)((char *)c.ws + b.off_tab);
+  TXM_HIP(hipMemcpyAsync(tab, c.states_host, (size_t)c.S * sizeof(txm_state_ptrs), hipMemcpyHostToDevice, st));
   double *piv = (double *)(pb + b.prep_piv);
   if (!have_tables) {
     hipLaunchKernelGGL(pivot_batch_kernel, dim3((unsigned)(1 + C), (unsigned)S), dim3(256), 0, st, tab, c.ldx_s, c.N, C, piv);
@@ -974,6 +989,8 @@ extern "C" int txm_resample_vals_batched_opts(const txm_state_ptrs *states_host,
   c.N = N; c.C = C; c.nrep = nrep; c.K = order + 1;
   c.freq = freq; c.spec = spec; c.counts = counts; c.out = out;
   c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
+  // the query is the larger of the two paths' plans: hold every call to it, before anything is enqueued
+  if (const int rc = check_workspace(c.fn, ws_bytes, txm_resample_vals_batched_ws_bytes(S, N, C, nrep, order))) return rc;
   if (!c.explicit_() && use_i8_batched(S, N, C, nrep, c.K, c.path)) return resample_batched_i8(c);
   return resample_batched_fp64(c);
 }

@@ -447,8 +447,12 @@ extern "C" int txm_sampler_tile_counts(const txm_sampler_spec *sp, uint32_t *cou
   int rc = check_spec(sp, &g, &nsamp);
   if (rc != TXM_OK) return rc;
   TXM_REQUIRE(counts, "sampler: null counts");
+  // nothing is kept in ws (the tile tree lives in LDS), but the size contract of every entry point holds here too
   (void)ws;
-  (void)ws_bytes;
+  if (ws_bytes < txm_sampler_counts_ws_bytes(sp)) {
+    set_error("sampler: workspace too small (%zu < %zu)", ws_bytes, txm_sampler_counts_ws_bytes(sp));
+    return TXM_ERR_WORKSPACE;
+  }
   hipStream_t st = (hipStream_t)stream;
   const uint32_t k0 = (uint32_t)sp->seed, k1 = (uint32_t)(sp->seed >> 32);
   // few replicates: more lanes a replicate, and 2^M workgroups a replicate (each the subtree under a node of level M) until the
