@@ -534,6 +534,29 @@ int txm_mbar_cov(const txm_mbar_state *states_host, int32_t K, int64_t C, double
                  const double *g_host, const double *logD, const double *alpha_host, int32_t n_alpha,
                  const double *mean, double *out, double *lnw, void *ws, size_t ws_bytes, txm_stream stream);
 
+/* The Gram matrix behind MBAR's covariance ACROSS columns and targets (MBARModel.predict_with_covariance): with
+ * y_n,(a,c) = W_na d_nac, d_nac = x[n][c] - mean[a][c], the covariance of two averages is
+ *   sum_n y_n,(a,c) y_n,(a',c') + (sqrt(N) b_ac)^T (I_K - sqrt(N) G_s sqrt(N))^+ (sqrt(N) b_a'c')
+ * (b of txm_mbar_cov, G_s the Gram matrix of the sampled states); this call gives the first term:
+ *   cross_alpha = 0: out (device, [n_alpha][C][C])         = sum_n W_na^2 d_nac d_nac'
+ *   cross_alpha = 1: out (device, [n_alpha C][n_alpha C])  = sum_n W_na W_na' d_nac d_na'c'   (index a C + c)
+ * It FOLLOWS the txm_mbar_cov call for the same targets: upiv, logD, alpha_host and mean are that call's, lnw (device
+ * [n_alpha]) is its output, so that W_na = e^{-alpha[a] ut_n - logD[n] - lnw[a]} is one exponential; ws is that call's
+ * workspace (txm_mbar_cov_ws_bytes(K, C, n_alpha) always suffices; there is no size query of its own).  The launch is
+ * planned from ws_bytes: more bytes, more sample workgroups, up to one per 256 samples of the longest state and about
+ * eight workgroups per CU in all.  1 <= C <= 255, 1 <= n_alpha <= 8, 1 <= K <= 64; bad arguments TXM_ERR_INVALID, fewer
+ * bytes than the smallest plan (one sample workgroup) TXM_ERR_WORKSPACE, both before anything is enqueued.
+ * The contraction runs on the FP64 matrix pipe; partials are combined in a fixed order: bitwise reproducible, and out is
+ * exactly symmetric.
+ * txm_mbar_cross_cov_plan: the plan the call would run under (host logic, n_max the longest state): plan_host [4] =
+ * column tiles T a side, tile pairs T (T + 1) / 2, sample workgroups, bytes of ws used (when refused: the smallest
+ * workspace the call takes). */
+int txm_mbar_cross_cov_plan(int32_t K, int64_t C, int32_t n_alpha, int32_t cross_alpha, int64_t n_max,
+                            size_t ws_bytes, int64_t *plan_host);
+int txm_mbar_cross_cov(const txm_mbar_state *states_host, int32_t K, int64_t C, double upiv, const double *logD,
+                       const double *alpha_host, int32_t n_alpha, const double *mean, const double *lnw,
+                       int32_t cross_alpha, double *out, void *ws, size_t ws_bytes, txm_stream stream);
+
 /* ---- (f-6) MBARModel.bootstrap: nrep weighted MBAR problems over the same pooled samples ----------- */
 /* Extends (f-5) where the reference stops (models.py:1109-1111: MBARModel.resample raises): replicate r
  * gives sample n of state s the integer count c[r][n] of row r of that state's multinomial sampler

@@ -244,6 +244,19 @@ def mbar_mean_variance(Gs, N, yy, b, *, pinv=None) -> np.ndarray:
     return np.asarray(yy, dtype=np.float64) + np.einsum("...j,jk,...k->...", rb, P, rb)
 
 
+def mbar_mean_covariance(Gs, N, gram, b, *, pinv=None) -> np.ndarray:
+    """cov of MBAR averages from the K x K block alone: Theta is bilinear in the unsampled columns, so two of them,
+    y_i and y_j, have Theta_ij = gram_ij + (sqrt(N) b_i)^T (I_K - sqrt(N) G_s sqrt(N))^+ (sqrt(N) b_j) with
+    gram_ij = sum_n y_ni y_nj and b_ik = sum_n W_nk y_ni.  ``gram`` (..., M, M) and ``b`` (..., M, K): the leading axes
+    broadcast; the diagonal is ``mbar_mean_variance``.  The second term is averaged with its transpose, so a symmetric
+    ``gram`` gives an exactly symmetric result.  ``pinv``: ``mbar_reduced_pinv(Gs, N)`` if the caller keeps it."""
+    rn = np.sqrt(np.asarray(N, dtype=np.float64).reshape(-1))
+    P = mbar_reduced_pinv(Gs, N) if pinv is None else pinv
+    rb = np.asarray(b, dtype=np.float64) * rn
+    q = np.einsum("...ik,kl,...jl->...ij", rb, P, rb)
+    return np.asarray(gram, dtype=np.float64) + 0.5 * (q + np.swapaxes(q, -1, -2))
+
+
 def mbar_overlap(Gs, N):
     """The overlap matrix O = G_s diag(N) of the sampled states (rows sum to 1), its eigenvalues in descending order --
     those of the symmetric sqrt(N) G_s sqrt(N), which is similar to O -- and the scalar 1 - the second largest

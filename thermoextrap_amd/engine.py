@@ -17,8 +17,8 @@ import torch
 
 from . import _lib
 from ._lib import ResampleOpts, SamplerSpec, check
-from ._mbar_host import (_MBAR_MAX_STEP, _MBAR_PINV_CUT, _sym_pinv, mbar_mean_variance, mbar_newton,  # noqa: F401
-                         mbar_newton_batched, mbar_overlap, mbar_reduced_pinv, mbar_solution_g, mbar_theta)
+from ._mbar_host import (_MBAR_MAX_STEP, _MBAR_PINV_CUT, _sym_pinv, mbar_mean_covariance, mbar_mean_variance,  # noqa: F401
+                         mbar_newton, mbar_newton_batched, mbar_overlap, mbar_reduced_pinv, mbar_solution_g, mbar_theta)
 from ._operands import either_layout, resample_pitch_ok, rowmajor_layout  # noqa: F401
 
 F64 = torch.float64
@@ -1340,6 +1340,57 @@ def mbar_cov_sums(xs, us, alpha0, sol: MbarSolution, alphas, means, *, with_lnw:
         return Q, B, yy, b
     # the kernel's exponents are -alpha (u - upiv) - (logD + c): sum_n e^{-alpha u_n - logD_n} = e^{-alpha upiv + c} x its sum
     return Q, B, yy, b, torch.cat(lnws).cpu().numpy() - al * sol.upiv + c
+
+
+def mbar_cross_cov_sums(xs, us, alpha0, sol: MbarSolution, alphas, means, *, cross_alpha: bool = False):
+    """The sums of the asymptotic covariance ACROSS columns (txm_mbar_cross_cov), on the host: the Gram matrix
+    sum_n W_na W_na' d_nac d_na'c' (d_nac = x_nc - mean_ac) and ``mbar_cov_sums``' b (n_alpha, C, K).  The Gram is
+    (n_alpha, C, C), a' = a, or with ``cross_alpha`` (n_alpha, C, n_alpha, C), at most 8 targets.  Per 8 targets a
+    txm_mbar_cov pass, then the Gram pass in the same workspace on the same stream, fed the first's ln sum_n w_an on the
+    device: nothing waits on the host between them.  At most 255 columns."""
+    L = _L()
+    tab, keep, ns, C = _mbar_table(us, xs)
+    K = len(us)
+    a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(-1))
+    if a0.shape != (K,):
+        raise ValueError("need one alpha0 per state")
+    g, _ = mbar_solution_g(ns, a0, sol)
+    g = np.ascontiguousarray(g)
+    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
+    if C > 255:
+        raise ValueError(f"the covariance across columns takes at most 255 columns, got {C}")
+    if cross_alpha and len(al) > 8:
+        raise ValueError(f"the covariance across targets takes at most 8 targets, got {len(al)}")
+    _check_f64_cuda(means, "means")
+    if means.shape != (len(al), C):
+        raise ValueError(f"means must be ({len(al)}, {C}), got {tuple(means.shape)}")
+    if sol.logD.shape != (int(ns.sum()),):
+        raise ValueError("sol.logD must hold one value per pooled sample")
+    dp = ct.POINTER(ct.c_double)
+    width = 1 + K + C * (1 + K)
+    outs, grams = [], []
+    for i0, chunk in _eight_per_pass(al):
+        na = len(chunk)
+        mean = means[i0:i0 + na].contiguous()
+        out = torch.empty((na, width), dtype=F64, device="cuda")
+        lnw = torch.empty(na, dtype=F64, device="cuda")
+        gram = torch.empty((na * C, na * C) if cross_alpha else (na, C, C), dtype=F64, device="cuda")
+        nbytes = L.txm_mbar_cov_ws_bytes(K, C, na)
+        ws = workspace(nbytes, tag="mbar_cov")
+        check(L.txm_mbar_cov(tab, K, C, float(sol.upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp), _ptr(sol.logD),
+                             chunk.ctypes.data_as(dp), na, _ptr(mean), _ptr(out), _ptr(lnw), _ptr(ws), nbytes,
+                             _stream()), "txm_mbar_cov")
+        # (the query's bytes, not the cached buffer's: the plan, and with it the bits, depend on nothing else)
+        check(L.txm_mbar_cross_cov(tab, K, C, float(sol.upiv), _ptr(sol.logD), chunk.ctypes.data_as(dp), na, _ptr(mean),
+                                   _ptr(lnw), int(bool(cross_alpha)), _ptr(gram), _ptr(ws), nbytes, _stream()),
+              "txm_mbar_cross_cov")
+        outs.append(out)
+        grams.append(gram)
+    v = torch.cat(outs, dim=0).cpu().numpy()
+    G = torch.cat(grams, dim=0).cpu().numpy()
+    del keep
+    b = v[:, 1 + K:].reshape(len(al), C, 1 + K)[:, :, 1:].copy()
+    return (G.reshape(len(al), C, len(al), C) if cross_alpha else G), b
 
 
 # ---------------------------------------------------------------------------

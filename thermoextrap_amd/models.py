@@ -1809,6 +1809,44 @@ class MBARModel(StateCollection):
         err = DataArray(np.sqrt(np.clip(var, 0.0, None)).reshape(len(avals), *cshape), dims, coords=coords)
         return mean, err
 
+    def predict_with_covariance(self, alpha, alpha_name=None, cross_alpha=False):
+        """(mean, cov): ``predict(alpha)`` bit for bit and the asymptotic covariance of the averages across the
+        observable columns -- what the error bar of a sum, an integral over bins or a ratio of columns needs.  ``cov`` has
+        dims (alpha, *val_dims, *[d + "_2" for d in val_dims]); its diagonal is ``predict_with_error``'s err squared.
+        With ``cross_alpha=True`` the covariance also runs across the targets (at most 8): dims (alpha, *val_dims,
+        alpha + "_2", *[d + "_2" ...]), which the error bar of a difference between two targets needs.  At most 255
+        columns.  The assumptions are ``predict_with_error``'s: independent samples (``timeseries.decorrelate`` first),
+        first order in the fluctuations.  Two more passes over the samples per 8 targets; no re-solve."""
+        from types import SimpleNamespace
+
+        avals, alpha_name = self._alpha_values(alpha, alpha_name)
+        us, xs, others, cshape = self._samples()
+        C = int(np.prod(cshape, dtype=np.int64))
+        if C > 255:
+            raise ValueError(f"predict_with_covariance takes at most 255 observable columns, got {C}")
+        if cross_alpha and len(avals) > 8:
+            raise ValueError(f"predict_with_covariance(cross_alpha=True) takes at most 8 targets, got {len(avals)}")
+        sol = self._solution()
+        means = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
+        gram, b = engine.mbar_cross_cov_sums(xs, us, self.alpha0, sol, avals, means, cross_alpha=cross_alpha)
+        na = len(avals)
+        if cross_alpha:
+            cov = engine.mbar_mean_covariance(self._gram(), self._counts(), gram.reshape(na * C, na * C),
+                                              b.reshape(na * C, -1), pinv=self._reduced_pinv())
+        else:
+            cov = engine.mbar_mean_covariance(self._gram(), self._counts(), gram, b, pinv=self._reduced_pinv())
+        dims, coords = (alpha_name, *others), {alpha_name: avals}
+        mean = DataArray(means.cpu().numpy().reshape(na, *cshape), dims, coords=coords)
+        xv = self._samples_host()[0][1]
+        src = SimpleNamespace(out_dims=list(others), out_shape=list(cshape), coords=dict(getattr(xv, "_coords", {})))
+        al = DataArray(avals, (alpha_name,), coords=coords)
+        if not cross_alpha:
+            return mean, _delta.label_cov(cov, al, src)
+        out = DataArray(cov.reshape(na, *cshape, na, *cshape),
+                        (alpha_name, *others, alpha_name + "_2", *[d + "_2" for d in others]),
+                        coords={alpha_name: avals, alpha_name + "_2": avals})
+        return mean, _delta.cross_labels(out, src)
+
     def _target_sums(self, avals):
         """(Q, B, ln sum_n w_an) of the targets: the covariance pass over the first observable column only."""
         us, xs, _, _ = self._samples()
