@@ -557,6 +557,33 @@ int txm_mbar_cross_cov(const txm_mbar_state *states_host, int32_t K, int64_t C, 
                        const double *alpha_host, int32_t n_alpha, const double *mean, const double *lnw,
                        int32_t cross_alpha, double *out, void *ws, size_t ws_bytes, txm_stream stream);
 
+/* Reweighted histograms and every sum their asymptotic covariance needs (MBARModel.histogram) for n_alpha <= 8 targets
+ * alpha_host (host).  bin_host: HOST array of K device pointers, bin_host[s][i] the int32 bin index of sample i of state s;
+ * an index outside [0, nbins) means "outside the range": the sample counts in the normalisation and in the class nbins.
+ * With 1_b(n) = (class of sample n == b), b <= nbins, and W_nk, W_na as for txm_mbar_cov (g_host, alpha0_host: the solution
+ * a txm_mbar_eval wrote `logD` at, same upiv):
+ *   out (device, [n_alpha][K + 2][nbins + 1]): rows k < K  T_kab = sum_n W_nk W_na 1_b(n),
+ *                                              row K       H_ab  = sum_n W_na 1_b(n)     (the histogram; sums to 1),
+ *                                              row K + 1   S_ab  = sum_n W_na^2 1_b(n).
+ *   lnw (nullable, device [n_alpha]): as txm_mbar_cov's.
+ * sum_n w_an is taken from row K, as the sum of its nbins + 1 column sums in index order, so Q_a = sum_b S_ab and
+ * B_ak = sum_b T_kab are sums of non-negative entries.  A column no sample fell into is exactly 0.0.
+ * One pass over u, logD and the bin index behind predict's max pass; x of the states is not read (may be NULL); the
+ * contraction runs on the FP64 matrix pipe against the one-hot of the bin index, formed in registers.  No atomics: two
+ * calls under the same plan give the same bits.  `states_host` and `bin_host` are copied into the workspace.
+ * 1 <= K <= 64, 1 <= nbins <= 1023, 1 <= n_alpha <= 8; bad arguments TXM_ERR_INVALID, fewer bytes than the smallest plan
+ * TXM_ERR_WORKSPACE, both before anything is enqueued.
+ * There is no size query: the launch is planned from ws_bytes (more bytes, more sample workgroups, up to one per 256
+ * samples of the longest state and about four workgroups per CU in all).  txm_mbar_hist_plan: the plan the call would
+ * run under (host logic, n_max the longest state): plan_host [4] = bin tiles per workgroup, bin-tile groups, sample
+ * workgroups, bytes of ws used (when refused: the smallest workspace the call takes).  Calling it with
+ * ws_bytes = SIZE_MAX gives the full plan and its bytes. */
+int txm_mbar_hist_plan(int32_t K, int32_t nbins, int32_t n_alpha, int64_t n_max, size_t ws_bytes, int64_t *plan_host);
+int txm_mbar_hist(const txm_mbar_state *states_host, const int32_t *const *bin_host, int32_t K, int32_t nbins,
+                  double upiv, const double *alpha0_host, const double *g_host, const double *logD,
+                  const double *alpha_host, int32_t n_alpha, double *out, double *lnw,
+                  void *ws, size_t ws_bytes, txm_stream stream);
+
 /* ---- (f-6) MBARModel.bootstrap: nrep weighted MBAR problems over the same pooled samples ----------- */
 /* Extends (f-5) where the reference stops (models.py:1109-1111: MBARModel.resample raises): replicate r
  * gives sample n of state s the integer count c[r][n] of row r of that state's multinomial sampler

@@ -21,6 +21,7 @@ _LAZY = {
     "factory_data_values": "data", "xrwrap_uv": "data", "xrwrap_xv": "data", "xrwrap_alpha": "data",
     "Derivatives": "models", "ExtrapModel": "models", "StateCollection": "models", "PerturbModel": "models",
     "ExtrapWeightedModel": "models", "InterpModel": "models", "InterpModelPiecewise": "models", "MBARModel": "models", "MBARBootstrap": "models",
+    "MBARHistogram": "models",
     "DataArray": "xrlite", "Dataset": "xrlite",
     "statistical_inefficiency": "timeseries", "statistical_inefficiencies": "timeseries", "subsample_correlated_data": "timeseries",
     "normalized_fluctuation_correlation_function": "timeseries", "decorrelate": "timeseries",

@@ -16,7 +16,7 @@ CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libtxmom.so"
 SOURCES = ["txm_api.hip", "txm_reduce.hip", "txm_sampler.hip", "txm_small.hip", "txm_resample.hip", "txm_resample_fp64.hip",
            "txm_resample_i8.hip", "txm_resample_i8t.hip", "txm_resample_i8g.hip", "txm_resample_i8gn.hip", "txm_count_table.hip", "txm_perturb.hip",
-           "txm_mbar.hip", "txm_mbar_cov.hip", "txm_mbar_cross_cov.hip", "txm_mbar_boot.hip", "txm_lagsum.hip", "txm_influence.hip",
+           "txm_mbar.hip", "txm_mbar_cov.hip", "txm_mbar_cross_cov.hip", "txm_mbar_hist.hip", "txm_mbar_boot.hip", "txm_lagsum.hip", "txm_influence.hip",
            "txm_influence_block.hip", "txm_influence_cross.hip", "txm_influence_block_cross.hip", "txm_perturb_cov.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-pass-failed"]
 # per-file flags.  txm_resample_i8t.hip: 11 int32 accumulator tiles (176 registers) per wave at two waves per SIMD only

@@ -266,3 +266,73 @@ def mbar_overlap(Gs, N):
     rn = np.sqrt(N)
     ev = np.linalg.eigvalsh(rn[:, None] * (0.5 * (Gs + Gs.T)) * rn[None, :])[::-1].copy()
     return Gs * N[None, :], ev, (float(1.0 - ev[1]) if len(ev) > 1 else 1.0)
+
+
+# ---- reweighted histograms (MBARModel.histogram; include/txmom.h txm_mbar_hist) -----------------------------------------
+# For indicator columns 1_b every sum of the covariance is a weighted histogram over the classes (the nbins bins, then the
+# class of the samples outside the range): H_b = sum_n W_na 1_b, S_b = sum_n W_na^2 1_b, T_kb = sum_n W_nk W_na 1_b.  Every
+# complement below is a sum over the OTHER classes -- additions of non-negative numbers only, never 1 - p or Q - S_b -- so
+# a bin that holds 99.9 % of the weight keeps full relative accuracy.
+
+def _sum_of_others(v: np.ndarray) -> np.ndarray:
+    """out[..., b] = sum_{b'' != b} v[..., b''] by additions alone (the entries before b, then the entries after it)."""
+    v = np.asarray(v, dtype=np.float64)
+    out = np.zeros_like(v)
+    out[..., 1:] += np.cumsum(v, axis=-1)[..., :-1]
+    out[..., :-1] += np.cumsum(v[..., ::-1], axis=-1)[..., ::-1][..., 1:]
+    return out
+
+
+def _sum_without_pairs(v: np.ndarray) -> np.ndarray:
+    """out[b, b'] = sum_{b'' not in (b, b')} v[b''] for b < b' (0 elsewhere) by additions alone: the entries before b, the
+    entries strictly between (a running sum along row b) and the entries after b'."""
+    v = np.asarray(v, dtype=np.float64)
+    m = len(v)
+    before = np.concatenate([[0.0], np.cumsum(v)[:-1]])
+    after = np.concatenate([np.cumsum(v[::-1])[::-1][1:], [0.0]])
+    run = np.cumsum(np.triu(np.broadcast_to(v, (m, m)), 1), axis=1)      # run[b, j] = sum_{b < i <= j} v[i]
+    between = np.zeros((m, m))
+    between[:, 1:] = run[:, :-1]
+    return np.triu(before[:, None] + between + after[None, :], 1)
+
+
+def mbar_hist_terms(H, S, T):
+    """The diagonal of the Gram matrix and the b vectors of the bins from the class sums of one or more targets:
+    ``H``, ``S`` (..., nbins + 1) and ``T`` (..., K, nbins + 1), the last class the samples outside the range.  Returns
+    (yy (..., nbins), b (..., nbins, K)):  yy_b = (1 - p_b)^2 S_b + p_b^2 (Q - S_b),
+    b_k,b = (1 - p_b) T_kb - p_b (B_k - T_kb), every complement a sum over the other classes."""
+    H, S, T = (np.asarray(a, dtype=np.float64) for a in (H, S, T))
+    p, q, rest_s, rest_t = H[..., :-1], _sum_of_others(H)[..., :-1], _sum_of_others(S)[..., :-1], _sum_of_others(T)[..., :-1]
+    yy = q * q * S[..., :-1] + p * p * rest_s
+    b = q[..., None, :] * T[..., :-1] - p[..., None, :] * rest_t
+    return yy, np.swapaxes(b, -1, -2)
+
+
+def mbar_hist_variance(Gs, N, H, S, T, *, pinv=None) -> np.ndarray:
+    """var of every bin of a reweighted histogram, (..., nbins): ``mbar_mean_variance`` of ``mbar_hist_terms``."""
+    yy, b = mbar_hist_terms(H, S, T)
+    return mbar_mean_variance(Gs, N, yy, b, pinv=pinv)
+
+
+def mbar_hist_covariance(Gs, N, H, S, T, *, pinv=None) -> np.ndarray:
+    """The asymptotic covariance between the bins of a reweighted histogram, (n_alpha, nbins, nbins), from the class sums
+    of ``engine.mbar_hist_sums`` (``H``, ``S`` (n_alpha, nbins + 1), ``T`` (n_alpha, K, nbins + 1)) through
+    ``mbar_mean_covariance``.  The Gram matrix of the indicator columns d_b = 1_b - p_b in closed form:
+        gram_bb  = (1 - p_b)^2 S_b + p_b^2 (Q - S_b)
+        gram_bb' = -p_b' (1 - p_b) S_b - p_b (1 - p_b') S_b' + p_b p_b' (Q - S_b - S_b')       (b != b')
+    with 1 - p_b, Q - S_b and Q - S_b - S_b' sums over the other classes; the upper triangle is mirrored, so the result
+    is exactly symmetric."""
+    H, S, T = (np.asarray(a, dtype=np.float64) for a in (H, S, T))
+    if H.ndim != 2 or S.shape != H.shape or T.ndim != 3 or T.shape[0] != H.shape[0] or T.shape[2] != H.shape[1]:
+        raise ValueError("H and S must be (n_alpha, nbins + 1) and T (n_alpha, K, nbins + 1)")
+    na, nb = H.shape[0], H.shape[1] - 1
+    yy, b = mbar_hist_terms(H, S, T)
+    q = _sum_of_others(H)[:, :-1]
+    gram = np.empty((na, nb, nb))
+    for a in range(na):
+        p, s = H[a, :-1], S[a, :-1]
+        rest = _sum_without_pairs(S[a])[:nb, :nb]
+        ps = q[a] * s
+        up = np.triu(-(ps[:, None] * p[None, :]) - (p[:, None] * ps[None, :]) + (p[:, None] * p[None, :]) * rest, 1)
+        gram[a] = up + up.T + np.diag(yy[a])
+    return mbar_mean_covariance(Gs, N, gram, b, pinv=pinv)

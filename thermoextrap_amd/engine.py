@@ -17,8 +17,9 @@ import torch
 
 from . import _lib
 from ._lib import ResampleOpts, SamplerSpec, check
-from ._mbar_host import (_MBAR_MAX_STEP, _MBAR_PINV_CUT, _sym_pinv, mbar_mean_covariance, mbar_mean_variance,  # noqa: F401
-                         mbar_newton, mbar_newton_batched, mbar_overlap, mbar_reduced_pinv, mbar_solution_g, mbar_theta)
+from ._mbar_host import (_MBAR_MAX_STEP, _MBAR_PINV_CUT, _sym_pinv, mbar_hist_covariance, mbar_hist_terms,  # noqa: F401
+                         mbar_hist_variance, mbar_mean_covariance, mbar_mean_variance, mbar_newton, mbar_newton_batched,
+                         mbar_overlap, mbar_reduced_pinv, mbar_solution_g, mbar_theta)
 from ._operands import either_layout, resample_pitch_ok, rowmajor_layout  # noqa: F401
 
 F64 = torch.float64
@@ -1391,6 +1392,80 @@ def mbar_cross_cov_sums(xs, us, alpha0, sol: MbarSolution, alphas, means, *, cro
     del keep
     b = v[:, 1 + K:].reshape(len(al), C, 1 + K)[:, :, 1:].copy()
     return (G.reshape(len(al), C, len(al), C) if cross_alpha else G), b
+
+
+HIST_MAX_BINS = 1023    # txm_mbar_hist: nbins + 1 columns in at most 64 tiles of 16
+_SIZE_MAX = ct.c_size_t(-1).value
+
+
+def bin_index(values, edges) -> torch.Tensor:
+    """The int32 bin index of every value under ``numpy.histogram``'s rule for the increasing ``edges`` (float64,
+    nbins + 1 of them): bin i holds edges[i] <= v < edges[i + 1], the last bin also v == edges[-1]; values below, above
+    and NaN map to -1.  ``torch.bucketize`` on the device ``values`` lives on."""
+    v = values if isinstance(values, torch.Tensor) else torch.as_tensor(np.asarray(values))
+    v = v.to(F64)
+    e = torch.as_tensor(np.ascontiguousarray(edges, dtype=np.float64), device=v.device)
+    if e.dim() != 1 or e.shape[0] < 2 or not bool((e[1:] > e[:-1]).all()):
+        raise ValueError("edges must be 1-D and increasing, at least two of them")
+    nb = e.shape[0] - 1
+    idx = torch.bucketize(v, e, right=True) - 1          # edges[idx] <= v < edges[idx + 1]; nb for v >= edges[-1]
+    idx = torch.where(v == e[-1], torch.full_like(idx, nb - 1), idx)
+    idx = torch.where((idx < 0) | (idx >= nb) | torch.isnan(v), torch.full_like(idx, -1), idx)
+    return idx.to(torch.int32)
+
+
+def mbar_hist_sums(bins, us, alpha0, sol: MbarSolution, alphas, nbins: int):
+    """The class sums of reweighted histograms and of their covariance (txm_mbar_hist), 8 targets per pass over the
+    samples, on the host.  ``bins``: one int32 CUDA tensor per state, the bin index of every sample; an index outside
+    [0, nbins) puts the sample into the class ``nbins`` ("outside the range").  Returns (H, S, T, Q, B, lnw):
+    H (n_alpha, nbins + 1) = sum_n W_na 1_b, S (n_alpha, nbins + 1) = sum_n W_na^2 1_b,
+    T (n_alpha, K, nbins + 1) = sum_n W_nk W_na 1_b, Q (n_alpha,) = sum_b S_ab, B (n_alpha, K) = sum_b T_kab and
+    lnw (n_alpha,) = ln sum_n e^{-alpha u_n - logD_n} as ``mbar_cov_sums`` gives it."""
+    L = _L()
+    tab, keep, ns, _ = _mbar_table(us)
+    K = len(us)
+    nbins = int(nbins)
+    if not 1 <= nbins <= HIST_MAX_BINS:
+        raise ValueError(f"a histogram takes 1 <= nbins <= {HIST_MAX_BINS} bins, got {nbins}")
+    if len(bins) != K:
+        raise ValueError("need one tensor of bin indices per state")
+    b2 = []
+    for s, b in enumerate(bins):
+        if not (isinstance(b, torch.Tensor) and b.is_cuda and b.dtype == torch.int32):
+            raise TypeError("bins must be int32 CUDA tensors")
+        if b.shape != (int(ns[s]),):
+            raise ValueError(f"bins of state {s} must be ({int(ns[s])},), got {tuple(b.shape)}")
+        b2.append(b.contiguous())
+    btab = (ct.c_void_p * K)(*[b.data_ptr() for b in b2])
+    a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(-1))
+    if a0.shape != (K,):
+        raise ValueError("need one alpha0 per state")
+    g, c = mbar_solution_g(ns, a0, sol)
+    g = np.ascontiguousarray(g)
+    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
+    if sol.logD.shape != (int(ns.sum()),):
+        raise ValueError("sol.logD must hold one value per pooled sample")
+    dp = ct.POINTER(ct.c_double)
+    outs, lnws = [], []
+    for _, chunk in _eight_per_pass(al):
+        na = len(chunk)
+        plan = (ct.c_int64 * 4)()
+        check(L.txm_mbar_hist_plan(K, nbins, na, int(ns.max()), _SIZE_MAX, plan), "txm_mbar_hist_plan")
+        nbytes = int(plan[3])
+        out = torch.empty((na, K + 2, nbins + 1), dtype=F64, device="cuda")
+        lnw = torch.empty(na, dtype=F64, device="cuda")
+        ws = workspace(nbytes, tag="mbar_hist")
+        # (the plan's bytes, not the cached buffer's: the plan, and with it the bits, depend on nothing else)
+        check(L.txm_mbar_hist(tab, btab, K, nbins, float(sol.upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp),
+                              _ptr(sol.logD), chunk.ctypes.data_as(dp), na, _ptr(out), _ptr(lnw), _ptr(ws), nbytes,
+                              _stream()), "txm_mbar_hist")
+        outs.append(out)
+        lnws.append(lnw)
+    v = torch.cat(outs, dim=0).cpu().numpy()
+    lnw = torch.cat(lnws).cpu().numpy() - al * sol.upiv + c
+    del keep, b2
+    T, H, S = v[:, :K, :].copy(), v[:, K, :].copy(), v[:, K + 1, :].copy()
+    return H, S, T, S.sum(axis=-1), T.sum(axis=-1), lnw
 
 
 # ---------------------------------------------------------------------------

@@ -1673,6 +1673,59 @@ class MBAROverlap(NamedTuple):
     scalar: float
 
 
+class MBARHistogram:
+    """What ``MBARModel.histogram`` returns.  ``p`` and ``std`` (dims (alpha, "bin")): the reweighted probability of every
+    bin and its asymptotic standard deviation; ``cov`` (dims (alpha, "bin", "bin_2"), or None): the covariance between the
+    bins; ``outside`` (dims (alpha,)): the weight of the samples outside the range; ``edges`` (nbins + 1); ``n_eff``
+    (dims (alpha,)): Kish's effective sample number 1 / sum_n W_na^2.  The "bin" coordinate holds the bin centres."""
+
+    def __init__(self, p, std, cov, outside, edges, n_eff, avals, alpha_name):
+        self.edges = np.asarray(edges, dtype=np.float64)
+        self.alpha_name = alpha_name
+        centres = 0.5 * (self.edges[:-1] + self.edges[1:])
+        coords = {alpha_name: avals, "bin": centres}
+        self.p = DataArray(p, (alpha_name, "bin"), coords=coords)
+        self.std = DataArray(std, (alpha_name, "bin"), coords=coords)
+        self.cov = None if cov is None else DataArray(cov, (alpha_name, "bin", "bin_2"), coords={**coords, "bin_2": centres})
+        self.outside = DataArray(outside, (alpha_name,), coords={alpha_name: avals})
+        self.n_eff = DataArray(n_eff, (alpha_name,), coords={alpha_name: avals})
+
+    def density(self):
+        """(p / width, std / width): the probability density of every bin and its standard deviation."""
+        w = np.diff(self.edges)
+        return self.p / w, self.std / w
+
+    def free_energy(self, reference=None):
+        """(F, dF), dims (alpha, "bin"): the free-energy profile F = -ln p and its first-order standard deviation.
+        ``reference=None``: dF = std / p.  ``reference`` a bin index, or ``"max"`` (every target's most probable bin): F
+        relative to that bin and dF^2 = v_b / p_b^2 + v_r / p_r^2 - 2 c_br / (p_b p_r) from ``cov`` (dF = 0 at the
+        reference).  Empty bins give F = +inf and dF = nan."""
+        p, std = np.asarray(self.p.values, dtype=np.float64), np.asarray(self.std.values, dtype=np.float64)
+        na, nb = p.shape
+        with np.errstate(divide="ignore", invalid="ignore"):
+            F = -np.log(p)
+            if reference is None:
+                dF = np.where(p > 0, std / p, np.nan)
+            else:
+                if self.cov is None:
+                    raise ValueError("free_energy(reference=...) needs the covariance between the bins: histogram(..., cov=True)")
+                if isinstance(reference, str):
+                    if reference != "max":
+                        raise ValueError(f'reference = {reference!r}: a bin index or "max"')
+                    r = np.argmax(p, axis=1)
+                else:
+                    r = np.full(na, range(nb)[int(reference)])
+                rows = np.arange(na)
+                c = np.asarray(self.cov.values, dtype=np.float64)
+                v = np.einsum("abb->ab", c)
+                pr, vr, cbr = p[rows, r][:, None], v[rows, r][:, None], c[rows, :, r]
+                var = v / (p * p) + vr / (pr * pr) - 2.0 * cbr / (p * pr)
+                dF = np.where((p > 0) & (pr > 0), np.sqrt(np.clip(var, 0.0, None)), np.nan)
+                dF[rows, r] = np.where(pr[:, 0] > 0, 0.0, np.nan)
+                F = F - F[rows, r][:, None]
+        return (DataArray(F, self.p.dims, coords=self.p.coords), DataArray(dF, self.p.dims, coords=self.p.coords))
+
+
 class MBARModel(StateCollection):
     """MBAR over the pooled samples of every state (reference models.py:1049-1111, which hands u_kn = alpha0_k u_n to
     pymbar):  <x>(alpha) = sum_n x_n e^{-alpha u_n - logD_n} / sum_n e^{-alpha u_n - logD_n}  with
@@ -1846,6 +1899,82 @@ class MBARModel(StateCollection):
                         (alpha_name, *others, alpha_name + "_2", *[d + "_2" for d in others]),
                         coords={alpha_name: avals, alpha_name + "_2": avals})
         return mean, _delta.cross_labels(out, src)
+
+    def _histogram_values(self, values):
+        """One 1-D CUDA tensor per state for ``histogram``'s ``values``, and whether they are integers."""
+        us, xs, _, cshape = self._samples()
+        if isinstance(values, str):
+            if values != "u":
+                raise ValueError(f'values = {values!r}: the only name is "u", the energy')
+            return list(us), False
+        if isinstance(values, (int, np.integer, tuple)):
+            C = int(np.prod(cshape, dtype=np.int64))
+            col = int(np.ravel_multi_index(tuple(int(i) for i in values), cshape)) if isinstance(values, tuple) else int(values)
+            if not 0 <= col < C:
+                raise IndexError(f"values = {values!r}: the observable has {C} columns")
+            return [x[:, col].contiguous() for x in xs], False
+        if len(values) != len(us):
+            raise ValueError(f"values: need one 1-D array per state ({len(us)}), got {len(values)}")
+        out, integral = [], True
+        for s, v in enumerate(values):
+            t = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(getattr(v, "values", v)))
+            if t.dim() != 1 or t.shape[0] != us[s].shape[0]:
+                raise ValueError(f"values of state {s} must be ({us[s].shape[0]},), got {tuple(t.shape)}")
+            integral = integral and not (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool)
+            out.append(t.to(us[s].device))
+        return out, integral
+
+    def histogram(self, alpha, bins, *, values=0, range=None, alpha_name=None, cov=True) -> "MBARHistogram":
+        """The reweighted distribution of an order parameter at every target alpha, p_b(alpha) = sum_n W_na 1_b(n), with
+        its asymptotic error bars and -- ``cov=True`` -- the covariance between the bins that a free-energy profile
+        relative to a reference bin needs.  Nothing of size samples x bins is formed: one pass over the samples per 8
+        targets gives every sum the covariance takes (engine.mbar_hist_sums); no re-solve.
+
+        ``values``: ``"u"`` (the energy), an int or a tuple indexing the non-record dims of ``xv`` (that column), or a
+        list of one 1-D array per state (any order parameter).  ``bins``: an int -- with ``range=(lo, hi)``, by default
+        the pooled minimum and maximum, as ``numpy.histogram`` -- or a 1-D array of increasing edges; bins are closed on
+        the left, the last one also on the right.  For 2-D or custom bins pass ``values`` as integer arrays with
+        ``bins=int`` and ``range=None``: the values are then the bin indices themselves.  Samples outside the range
+        count in the normalisation (``outside`` holds their weight).  At most 1023 bins.
+
+        The assumptions are ``predict_with_error``'s: independent samples (``timeseries.decorrelate`` first), first order
+        in the fluctuations.  Returns an ``MBARHistogram``."""
+        avals, alpha_name = self._alpha_values(alpha, alpha_name)
+        us, _, _, _ = self._samples()
+        vals, integral = self._histogram_values(values)
+        if np.ndim(bins) == 0:
+            nb = int(bins)
+            if nb < 1:
+                raise ValueError(f"bins = {bins}: need at least one bin")
+            if integral and range is None:
+                edges = None                                       # the values are the bin indices
+            else:
+                if range is None:
+                    lo, hi = min(float(v.min()) for v in vals), max(float(v.max()) for v in vals)
+                else:
+                    lo, hi = (float(r) for r in range)
+                if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
+                    raise ValueError(f"range = ({lo}, {hi}) is not a finite interval")
+                edges = np.histogram_bin_edges(np.empty(0), bins=nb, range=(lo, hi))
+        else:
+            edges = np.asarray(bins, dtype=np.float64)
+            if edges.ndim != 1 or len(edges) < 2 or not np.all(np.diff(edges) > 0):
+                raise ValueError("bins must be an int or a 1-D array of increasing edges")
+            nb = len(edges) - 1
+        if nb > engine.HIST_MAX_BINS:
+            raise ValueError(f"histogram takes at most {engine.HIST_MAX_BINS} bins, got {nb}")
+        if edges is None:
+            idx = [v.to(torch.int64).clamp(-1, nb).to(torch.int32) for v in vals]
+            edges = np.arange(nb + 1, dtype=np.float64)
+        else:
+            idx = [engine.bin_index(v, edges) for v in vals]
+        sol = self._solution()
+        H, S, T, Q, _, _ = engine.mbar_hist_sums(idx, us, self.alpha0, sol, avals, nb)
+        Gs, N, pinv = self._gram(), self._counts(), self._reduced_pinv()
+        var = engine.mbar_hist_variance(Gs, N, H, S, T, pinv=pinv)
+        covar = engine.mbar_hist_covariance(Gs, N, H, S, T, pinv=pinv) if cov else None
+        return MBARHistogram(H[:, :nb].copy(), np.sqrt(np.clip(var, 0.0, None)), covar, H[:, nb].copy(), edges, 1.0 / Q,
+                             avals, alpha_name)
 
     def _target_sums(self, avals):
         """(Q, B, ln sum_n w_an) of the targets: the covariance pass over the first observable column only."""
