@@ -584,6 +584,41 @@ int txm_mbar_hist(const txm_mbar_state *states_host, const int32_t *const *bin_h
                   const double *alpha_host, int32_t n_alpha, double *out, double *lnw,
                   void *ws, size_t ws_bytes, txm_stream stream);
 
+/* Blocked (batch-means) MBAR error bars for CORRELATED series kept whole (MBARModel.predict_with_error /
+ * predict_with_covariance / free_energy / free_energy_covariance (block=...), blocking_curve) for n_alpha <= 8 targets
+ * alpha_host (host).  Every first-order influence of an MBAR estimate is linear in the row
+ *   t_n = (W_n1 .. W_nK, {W_na, y_n,(a,0) .. y_n,(a,C-1)} for each target a),     M = K + n_alpha (C + 1) columns
+ * (column K + a (C + 1): W_na; column K + a (C + 1) + 1 + c: y_n,(a,c) = W_na (x[n][c] - mean[a][c])) with W_nk, W_na as
+ * for txm_mbar_cov (g_host, alpha0_host: the solution a txm_mbar_eval wrote `logD` at, same upiv).  It FOLLOWS the
+ * txm_mbar_cov call for the same targets: mean (device [n_alpha][C]) is txm_mbar_predict's output, lnw (device [n_alpha])
+ * txm_mbar_cov's, so that W_na = e^{-alpha[a] ut_n - logD[n] - lnw[a]} is one exponential.  State s is cut into level-0
+ * blocks of block_host[s] records (HOST array [K], every entry >= 1; a last short block is kept, an entry above n_s means
+ * the whole state; blocks never straddle two states); level l merges the pairs of level l - 1 within each state (a last
+ * unpaired block stays).  With T_beta = sum_{n in beta} t_n and Tc_beta = T_beta - (len_beta / n_s) sum_{beta' in s} T_beta':
+ *   gamma   (device, [n_levels][M][M]) = sum_beta Tc_beta Tc_beta^T over the blocks of level l   (no nb / (nb - 1) factor)
+ *   nblocks (device, int64 [n_levels][K]) = the blocks of every state at every level.
+ * A state that has ONE block at a level contributes exactly 0.0 to that level.  The covariance of two estimates is
+ * l^T gamma l' with l the coefficient vectors of their influences (thermoextrap_amd/_mbar_host.py).
+ * One pass over u, logD and x: every level-0 block is summed in an order fixed by its start, its length and C alone (not by
+ * the launch); the sums are centred per state BEFORE the Gram pass, which runs on the FP64 matrix pipe with the block axis
+ * as the k-axis, upper-triangle tiles only, every entry stored with its mirror.  No atomics: two calls under the same plan
+ * give the same bits and every gamma[l] is exactly symmetric.  `states_host` is copied into the workspace.
+ * 1 <= K <= 64, 1 <= C <= 255, 1 <= n_alpha <= 8, 1 <= n_levels <= 32; bad arguments TXM_ERR_INVALID, fewer bytes than the
+ * smallest plan TXM_ERR_WORKSPACE, both before anything is enqueued.
+ * There is no size query.  txm_mbar_block_cov_plan (host logic; n_host [K] the states' sample counts): plan_host [7] = M,
+ * level-0 blocks of all states, rows of the piece array (blocks above 4096 records are summed in pieces of 4096),
+ * macro-tile pairs of the Gram pass, its block workgroups, bytes of ws used (when refused: the smallest workspace the call
+ * takes), byte offset of the level-0 array in ws (after a call with n_levels = 1 it holds Tc [blocks][M], state after
+ * state: a diagnostic the tests read).  The workspace holds the block sums, 8 M sum_s ceil(n_s / block_s) bytes (half as
+ * much again for n_levels > 1), the pieces, the per-state column sums and the Gram records; more bytes buy more block workgroups of the Gram pass, up to
+ * one per 256 blocks and about four per CU in all.  ws_bytes = SIZE_MAX gives the full plan and its bytes. */
+int txm_mbar_block_cov_plan(const int64_t *n_host, const int64_t *block_host, int32_t K, int64_t C, int32_t n_alpha,
+                            int32_t n_levels, size_t ws_bytes, int64_t *plan_host);
+int txm_mbar_block_cov(const txm_mbar_state *states_host, int32_t K, int64_t C, double upiv, const double *alpha0_host,
+                       const double *g_host, const double *logD, const double *alpha_host, int32_t n_alpha,
+                       const double *mean, const double *lnw, const int64_t *block_host, int32_t n_levels,
+                       double *gamma, int64_t *nblocks, void *ws, size_t ws_bytes, txm_stream stream);
+
 /* ---- (f-6) MBARModel.bootstrap: nrep weighted MBAR problems over the same pooled samples ----------- */
 /* Extends (f-5) where the reference stops (models.py:1109-1111: MBARModel.resample raises): replicate r
  * gives sample n of state s the integer count c[r][n] of row r of that state's multinomial sampler

@@ -16,7 +16,7 @@ CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libtxmom.so"
 SOURCES = ["txm_api.hip", "txm_reduce.hip", "txm_sampler.hip", "txm_small.hip", "txm_resample.hip", "txm_resample_fp64.hip",
            "txm_resample_i8.hip", "txm_resample_i8t.hip", "txm_resample_i8g.hip", "txm_resample_i8gn.hip", "txm_count_table.hip", "txm_perturb.hip",
-           "txm_mbar.hip", "txm_mbar_cov.hip", "txm_mbar_cross_cov.hip", "txm_mbar_hist.hip", "txm_mbar_boot.hip", "txm_lagsum.hip", "txm_influence.hip",
+           "txm_mbar.hip", "txm_mbar_cov.hip", "txm_mbar_cross_cov.hip", "txm_mbar_hist.hip", "txm_mbar_block.hip", "txm_mbar_boot.hip", "txm_lagsum.hip", "txm_influence.hip",
            "txm_influence_block.hip", "txm_influence_cross.hip", "txm_influence_block_cross.hip", "txm_perturb_cov.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-pass-failed"]
 # per-file flags.  txm_resample_i8t.hip: 11 int32 accumulator tiles (176 registers) per wave at two waves per SIMD only
@@ -37,9 +37,10 @@ _I8G = _I8T + ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]
 _CROSS = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # txm_influence_block_cross.hip: 16 FP64 accumulator tiles (128 registers) live across the block loop.  With the AGPR split the
 # Gram kernel holds them in AGPRs but moves operands through 592 v_accvgpr copies (56 VGPRs + 128 AGPRs); in VGPR form there is
-# no copy (184 VGPRs, no AGPRs) -- two waves per SIMD either way, no spills, no scratch
+# no copy (184 VGPRs, no AGPRs) -- two waves per SIMD either way, no spills, no scratch.  txm_mbar_block.hip runs the same Gram
+# body (txm_block_gram.h) and is built the same way
 EXTRA_FLAGS = {"txm_resample_i8t.hip": _I8T, "txm_resample_i8g.hip": _I8G, "txm_resample_i8gn.hip": _I8G, "txm_sampler.hip": ["-ffp-contract=off"],
-               "txm_influence_cross.hip": _CROSS, "txm_influence_block_cross.hip": _CROSS}
+               "txm_influence_cross.hip": _CROSS, "txm_influence_block_cross.hip": _CROSS, "txm_mbar_block.hip": _CROSS}
 
 
 def _hipcc() -> str:

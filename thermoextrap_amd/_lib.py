@@ -168,6 +168,11 @@ SIGNATURES = {
     "txm_mbar_hist": (c_int, [ct.POINTER(MbarState), ct.POINTER(c_void_p), ct.c_int32, ct.c_int32, ct.c_double,
                               ct.POINTER(ct.c_double), ct.POINTER(ct.c_double), c_void_p, ct.POINTER(ct.c_double), ct.c_int32,
                               c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
+    "txm_mbar_block_cov_plan": (c_int, [ct.POINTER(c_i64), ct.POINTER(c_i64), ct.c_int32, c_i64, ct.c_int32, ct.c_int32,
+                                        c_size, ct.POINTER(c_i64)]),
+    "txm_mbar_block_cov": (c_int, [ct.POINTER(MbarState), ct.c_int32, c_i64, ct.c_double, ct.POINTER(ct.c_double),
+                                   ct.POINTER(ct.c_double), c_void_p, ct.POINTER(ct.c_double), ct.c_int32, c_void_p, c_void_p,
+                                   ct.POINTER(c_i64), ct.c_int32, c_void_p, c_void_p, c_void_p, c_size, c_void_p]),
     "txm_mbar_boot_ws_bytes": (c_size, [ct.c_int32, c_i64, ct.c_int32, c_i64, c_i64]),
     "txm_mbar_boot_eval": (c_int, [ct.POINTER(MbarState), ct.POINTER(MbarBootState), ct.c_int32, ct.POINTER(ct.c_double),
                                    c_void_p, c_void_p, c_i64, ct.c_double, c_void_p, c_void_p, c_size, c_void_p]),

@@ -336,3 +336,84 @@ def mbar_hist_covariance(Gs, N, H, S, T, *, pinv=None) -> np.ndarray:
         up = np.triu(-(ps[:, None] * p[None, :]) - (p[:, None] * ps[None, :]) + (p[:, None] * p[None, :]) * rest, 1)
         gram[a] = up + up.T + np.diag(yy[a])
     return mbar_mean_covariance(Gs, N, gram, b, pinv=pinv)
+
+
+# ---- blocked (batch-means) error bars for correlated series kept whole (include/txmom.h txm_mbar_block_cov) -------------
+# Give sample n the mass 1 + eps_n in every sum over samples (N_k in the denominators fixed).  To first order an MBAR
+# estimate moves by sum_n eps_n phi_n, and every influence phi_n is linear in the row
+#   t_n = (W_n1 .. W_nK, {W_na, y_n,(a,0) .. y_n,(a,C-1)} for each target a),      M = K + n_alpha (C + 1) columns:
+#   average            phi_n(a, c)       = y_n,(a,c) + c_ac^T W_n.,   c_ac = sqrt(N) P sqrt(N) b_ac
+#   sampled state      phi_n(f_i - f_0)  = -[R W_n.]_i + [R W_n.]_0,  R = N^{-1/2} P N^{1/2}
+#   target             phi_n(f_a - f_0)  = -W_na - (sqrt(N) P sqrt(N) B_a)^T W_n. + [R W_n.]_0
+# with P = (I_K - sqrt(N) G_s sqrt(N))^+ (mbar_reduced_pinv).  The builders below return the coefficient vectors l as rows
+# of a matrix L over the M columns; with Gamma the Gram matrix of the per-state-centred block sums of t_n (one stationary
+# series per state, independent states) the covariance of the estimates is L Gamma L^T.  No nb / (nb - 1) factor; a state
+# with a single block contributes exactly zero.
+
+def mbar_block_width(K: int, n_alpha: int, C: int) -> int:
+    """Columns of the row t_n: the K sampled states, then per target its weight and its C centred products."""
+    return int(K) + int(n_alpha) * (int(C) + 1)
+
+
+def _block_pinv(Gs, N, pinv):
+    N = np.asarray(N, dtype=np.float64).reshape(-1)
+    return N, np.sqrt(N), (mbar_reduced_pinv(Gs, N) if pinv is None else np.asarray(pinv, dtype=np.float64))
+
+
+def mbar_block_coef_mean(Gs, N, b, *, pinv=None) -> np.ndarray:
+    """L (n_alpha * C, M) of the averages <x_c>(a), row a C + c: 1 at y_(a,c) and c_ac on the K sampled columns.
+    ``b`` (n_alpha, C, K): ``engine.mbar_cov_sums``' b for the targets of the Gamma call, in its order."""
+    N, rn, P = _block_pinv(Gs, N, pinv)
+    b = np.asarray(b, dtype=np.float64)
+    na, C, K = b.shape
+    L = np.zeros((na, C, mbar_block_width(K, na, C)))
+    L[:, :, :K] = ((b * rn) @ P) * rn
+    for a in range(na):
+        L[a, np.arange(C), K + a * (C + 1) + 1 + np.arange(C)] = 1.0
+    return L.reshape(na * C, -1)
+
+
+def mbar_block_coef_sampled(Gs, N, M: int | None = None, *, pinv=None) -> np.ndarray:
+    """L (K, M) of the sampled states' f_i - f_0 (row 0 is zero): -R_i. + R_0. on the K sampled columns."""
+    N, rn, P = _block_pinv(Gs, N, pinv)
+    K = len(N)
+    R = (P * rn[None, :]) / rn[:, None]
+    L = np.zeros((K, K if M is None else int(M)))
+    L[:, :K] = R[0][None, :] - R
+    L[0] = 0.0
+    return L
+
+
+def mbar_block_coef_target(Gs, N, B, C: int, *, pinv=None) -> np.ndarray:
+    """L (n_alpha, M) of the targets' f_a - f_0: -1 at W_na, -(sqrt(N) P sqrt(N) B_a) + R_0. on the K sampled columns.
+    ``B`` (n_alpha, K): ``engine.mbar_cov_sums``' B for the targets of the Gamma call, in its order."""
+    N, rn, P = _block_pinv(Gs, N, pinv)
+    B = np.asarray(B, dtype=np.float64)
+    na, K = B.shape
+    R0 = (P[0] * rn) / rn[0]
+    L = np.zeros((na, mbar_block_width(K, na, C)))
+    L[:, :K] = R0[None, :] - ((B * rn) @ P) * rn
+    L[np.arange(na), K + np.arange(na) * (int(C) + 1)] = -1.0
+    return L
+
+
+def _block_lg(gamma, L):
+    gamma = np.asarray(gamma, dtype=np.float64)
+    L = np.asarray(L, dtype=np.float64)
+    if L.ndim != 2 or gamma.ndim < 2 or gamma.shape[-1] != L.shape[-1] or gamma.shape[-2] != L.shape[-1]:
+        raise ValueError(f"gamma {gamma.shape} does not match L {L.shape}: need (..., M, M) and (R, M)")
+    return np.matmul(L, gamma), L
+
+
+def mbar_block_covariance(gamma, L) -> np.ndarray:
+    """L Gamma L^T for ``gamma`` (..., M, M) and ``L`` (R, M): (..., R, R), symmetrised so that a symmetric Gamma gives
+    an exactly symmetric result."""
+    LG, L = _block_lg(gamma, L)
+    c = np.matmul(LG, L.T)
+    return 0.5 * (c + np.swapaxes(c, -1, -2))
+
+
+def mbar_block_variance(gamma, L) -> np.ndarray:
+    """The diagonal of ``mbar_block_covariance``: l_r^T Gamma l_r for every row of ``L``, (..., R)."""
+    LG, L = _block_lg(gamma, L)
+    return np.einsum("...ri,ri->...r", LG, L)

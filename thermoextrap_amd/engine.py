@@ -17,7 +17,8 @@ import torch
 
 from . import _lib
 from ._lib import ResampleOpts, SamplerSpec, check
-from ._mbar_host import (_MBAR_MAX_STEP, _MBAR_PINV_CUT, _sym_pinv, mbar_hist_covariance, mbar_hist_terms,  # noqa: F401
+from ._mbar_host import (_MBAR_MAX_STEP, _MBAR_PINV_CUT, _sym_pinv, mbar_block_coef_mean, mbar_block_coef_sampled,  # noqa: F401
+                         mbar_block_coef_target, mbar_block_covariance, mbar_block_variance, mbar_block_width, mbar_hist_covariance, mbar_hist_terms,
                          mbar_hist_variance, mbar_mean_covariance, mbar_mean_variance, mbar_newton, mbar_newton_batched,
                          mbar_overlap, mbar_reduced_pinv, mbar_solution_g, mbar_theta)
 from ._operands import either_layout, resample_pitch_ok, rowmajor_layout  # noqa: F401
@@ -1396,6 +1397,115 @@ def mbar_cross_cov_sums(xs, us, alpha0, sol: MbarSolution, alphas, means, *, cro
 
 HIST_MAX_BINS = 1023    # txm_mbar_hist: nbins + 1 columns in at most 64 tiles of 16
 _SIZE_MAX = ct.c_size_t(-1).value
+
+
+class MbarBlockGamma(NamedTuple):
+    """What ``mbar_block_gamma`` returns, on the host.  Targets go 8 per slab; slab i holds the targets 8 i .. 8 i + 7 and
+    has its own Gram matrix (its leading K x K block, the sampled states', is the same in every slab)."""
+
+    gamma: list            # per slab (n_levels, M_i, M_i), M_i = K + n_i (C + 1): Gamma of every level
+    nblocks: np.ndarray    # (n_levels, K) int64: the blocks of every state at every level
+    b: np.ndarray          # (n_alpha, C, K): mbar_cov_sums' b
+    B: np.ndarray          # (n_alpha, K): mbar_cov_sums' B
+    lnw: np.ndarray        # (n_alpha,): mbar_cov_sums' lnw (with_lnw=True)
+
+
+def mbar_block_lengths(block, ns) -> np.ndarray:
+    """``block`` of the blocked MBAR error bars as int64 (K,): an int serves every state, a sequence gives each state its
+    own (what ``timeseries.block_lengths`` returns)."""
+    K = len(ns)
+    if isinstance(block, (str, bytes, bool)) or (np.ndim(block) == 0 and not isinstance(block, (int, np.integer))):
+        raise TypeError(f"block must be an int or one int per state, got {block!r}")
+    vals = [block] * K if np.ndim(block) == 0 else list(block)
+    if len(vals) != K:
+        raise ValueError(f"block must be an int or hold one entry per state: len(block)={len(vals)}, {K} states")
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"block must be an int or one int per state, got {v!r}")
+        if v < 1:
+            raise ValueError(f"block must be >= 1, got {v}")
+    return np.ascontiguousarray(vals, dtype=np.int64)
+
+
+def mbar_block_levels(ns, block) -> tuple[np.ndarray, np.ndarray]:
+    """The levels of a blocking curve of the pooled states: ``(factors, n_blocks)`` with ``factors[l] = 2**l`` (level l
+    cuts state s into blocks of ``block[s] * 2**l`` records) and ``n_blocks[l][s] = ceil(ceil(n_s / block[s]) / 2**l)``,
+    for every level at which some state still has at least two blocks (at least one level)."""
+    blk = mbar_block_lengths(block, ns)
+    nb0 = -(-np.asarray(ns, dtype=np.int64) // np.minimum(blk, np.asarray(ns, dtype=np.int64)))
+    counts, l = [], 0
+    while l < 32:
+        c = (nb0 + (1 << l) - 1) >> l
+        if l > 0 and c.max() < 2:
+            break
+        counts.append(c)
+        l += 1
+    return 2 ** np.arange(len(counts), dtype=np.int64), np.asarray(counts, dtype=np.int64)
+
+
+def mbar_block_gamma(xs, us, alpha0, sol: MbarSolution, alphas, means, block, n_levels: int = 1) -> MbarBlockGamma:
+    """The Gram matrices behind the blocked (batch-means) MBAR error bars (txm_mbar_block_cov) with the sums the
+    coefficient vectors need, on the host.  Per 8 targets a txm_mbar_cov pass (b, B and, on the device, ln sum_n w_an),
+    then the block pass on the same stream, fed the first's lnw and ``means`` on the device: nothing waits on the host
+    between them.  ``block``: an int or one int per state; ``n_levels``: Gamma for blocks of block * 2**l, l < n_levels.
+    At most 255 columns."""
+    L = _L()
+    tab, keep, ns, C = _mbar_table(us, xs)
+    K = len(us)
+    a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(-1))
+    if a0.shape != (K,):
+        raise ValueError("need one alpha0 per state")
+    g, c = mbar_solution_g(ns, a0, sol)
+    g = np.ascontiguousarray(g)
+    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
+    if C > 255:
+        raise ValueError(f"the blocked MBAR error bars take at most 255 columns, got {C}")
+    n_levels = int(n_levels)
+    if not 1 <= n_levels <= 32:
+        raise ValueError(f"n_levels must be in [1, 32], got {n_levels}")
+    _check_f64_cuda(means, "means")
+    if means.shape != (len(al), C):
+        raise ValueError(f"means must be ({len(al)}, {C}), got {tuple(means.shape)}")
+    if sol.logD.shape != (int(ns.sum()),):
+        raise ValueError("sol.logD must hold one value per pooled sample")
+    blk = mbar_block_lengths(block, ns)
+    n64 = np.ascontiguousarray(ns, dtype=np.int64)
+    dp, ip = ct.POINTER(ct.c_double), ct.POINTER(ct.c_int64)
+    width = 1 + K + C * (1 + K)
+    outs, lnws, gammas = [], [], []
+    nblocks = torch.empty((n_levels, K), dtype=torch.int64, device="cuda")
+    for i0, chunk in _eight_per_pass(al):
+        na = len(chunk)
+        M = mbar_block_width(K, na, C)
+        mean = means[i0:i0 + na].contiguous()
+        out = torch.empty((na, width), dtype=F64, device="cuda")
+        lnw = torch.empty(na, dtype=F64, device="cuda")
+        gamma = torch.empty((n_levels, M, M), dtype=F64, device="cuda")
+        nbytes = L.txm_mbar_cov_ws_bytes(K, C, na)
+        ws = workspace(nbytes, tag="mbar_cov")
+        check(L.txm_mbar_cov(tab, K, C, float(sol.upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp), _ptr(sol.logD),
+                             chunk.ctypes.data_as(dp), na, _ptr(mean), _ptr(out), _ptr(lnw), _ptr(ws), nbytes,
+                             _stream()), "txm_mbar_cov")
+        plan = (ct.c_int64 * 7)()
+        check(L.txm_mbar_block_cov_plan(n64.ctypes.data_as(ip), blk.ctypes.data_as(ip), K, C, na, n_levels, _SIZE_MAX, plan),
+              "txm_mbar_block_cov_plan")
+        bbytes = int(plan[5])
+        wsb = workspace(bbytes, tag="mbar_block")
+        # (the plan's bytes, not the cached buffer's: the plan, and with it the bits, depend on nothing else)
+        check(L.txm_mbar_block_cov(tab, K, C, float(sol.upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp), _ptr(sol.logD),
+                                   chunk.ctypes.data_as(dp), na, _ptr(mean), _ptr(lnw), blk.ctypes.data_as(ip), n_levels,
+                                   _ptr(gamma), _ptr(nblocks), _ptr(wsb), bbytes, _stream()), "txm_mbar_block_cov")
+        outs.append(out)
+        lnws.append(lnw)
+        gammas.append(gamma)
+    v = torch.cat(outs, dim=0).cpu().numpy()
+    gam = [t.cpu().numpy() for t in gammas]
+    nbl = nblocks.cpu().numpy()
+    lnw = torch.cat(lnws).cpu().numpy() - al * sol.upiv + c
+    del keep
+    B = v[:, 1:1 + K].copy()
+    b = v[:, 1 + K:].reshape(len(al), C, 1 + K)[:, :, 1:].copy()
+    return MbarBlockGamma(gam, nbl, b, B, lnw)
 
 
 def bin_index(values, edges) -> torch.Tensor:

@@ -1848,28 +1848,92 @@ class MBARModel(StateCollection):
                                   "MBARModel predicts from the pooled samples, not from derivatives; its error bars are "
                                   "predict_with_error")
 
-    def predict_with_error(self, alpha, alpha_name=None):
+    # ---- blocked (batch-means) error bars for CORRELATED series kept whole ------------------------------
+    # Every influence of an MBAR estimate is linear in the row t_n of txm_mbar_block_cov; its block sums are centred per
+    # state (one stationary series per state, independent states) and var = l^T Gamma l.  First order; B beyond the
+    # correlation time (timeseries.block_lengths proposes one per state, blocking_curve shows whether the variance has
+    # levelled off); no nb / (nb - 1) factor; a state with a single block contributes exactly zero.  block=1 is the
+    # per-state-centred sandwich estimator: it agrees with the Theta form asymptotically, not to rounding.
+    def _block_gamma(self, avals, block, n_levels=1, first_column=False):
+        """(means on the device, engine.MbarBlockGamma, C) of the targets; ``first_column``: the first observable column
+        only (the free energies need no x)."""
+        us, xs, _, _ = self._samples()
+        sol = self._solution()
+        if first_column:
+            xs = [x[:, :1] for x in xs]
+        C = int(xs[0].shape[1])
+        if C > 255:
+            raise ValueError(f"the blocked MBAR error bars (block=...) take at most 255 observable columns, got {C}")
+        means = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
+        return means, engine.mbar_block_gamma(xs, us, self.alpha0, sol, avals, means, block, n_levels=n_levels), C
+
+    def _block_mean_variance(self, res, C):
+        """(n_levels, n_alpha, C): l^T Gamma l of every average, slab by slab."""
+        Gs, N, pinv = self._gram(), self._counts(), self._reduced_pinv()
+        out = []
+        for i, gam in enumerate(res.gamma):
+            L = engine.mbar_block_coef_mean(Gs, N, res.b[8 * i:8 * i + 8], pinv=pinv)
+            out.append(engine.mbar_block_variance(gam, L).reshape(gam.shape[0], -1, C))
+        return np.concatenate(out, axis=1)
+
+    def predict_with_error(self, alpha, alpha_name=None, block=None):
         """(mean, err): ``predict(alpha)`` bit for bit and its asymptotic standard deviation (pymbar's ``dA`` of
-        compute_expectations), both with ``predict``'s dims.  One more pass over the samples per 8 targets; no re-solve."""
+        compute_expectations), both with ``predict``'s dims.  One more pass over the samples per 8 targets; no re-solve.
+
+        ``block=None`` assumes INDEPENDENT samples (Shirts & Chodera's Theta).  ``block=B`` (an int, or one int per state
+        as ``timeseries.block_lengths`` returns them) is for CORRELATED series kept whole: every state is cut into
+        contiguous blocks of B records (a last short one is kept, blocks never straddle two states), the first-order
+        influences are summed per block, centred per state, and ``err^2 = sum_b (centred block sum)^2`` -- batch means,
+        B beyond the correlation time (``blocking_curve`` shows whether the variance has levelled off).  Assumptions:
+        first order, one stationary series per state, independent states, no nb / (nb - 1) factor; a state with a
+        single block contributes exactly zero.  ``block=1`` is the per-state-centred sandwich estimator: equal to the
+        Theta form asymptotically, not to rounding.  At most 255 observable columns with ``block``."""
         avals, alpha_name = self._alpha_values(alpha, alpha_name)
         us, xs, others, cshape = self._samples()
         sol = self._solution()
-        means = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
-        _, _, yy, b = engine.mbar_cov_sums(xs, us, self.alpha0, sol, avals, means)
-        var = engine.mbar_mean_variance(self._gram(), self._counts(), yy, b, pinv=self._reduced_pinv())
+        if block is None:
+            means = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
+            _, _, yy, b = engine.mbar_cov_sums(xs, us, self.alpha0, sol, avals, means)
+            var = engine.mbar_mean_variance(self._gram(), self._counts(), yy, b, pinv=self._reduced_pinv())
+        else:
+            means, res, C = self._block_gamma(avals, block)
+            var = self._block_mean_variance(res, C)[0]
         dims, coords = (alpha_name, *others), {alpha_name: avals}
         mean = DataArray(means.cpu().numpy().reshape(len(avals), *cshape), dims, coords=coords)
         err = DataArray(np.sqrt(np.clip(var, 0.0, None)).reshape(len(avals), *cshape), dims, coords=coords)
         return mean, err
 
-    def predict_with_covariance(self, alpha, alpha_name=None, cross_alpha=False):
+    def blocking_curve(self, alpha, block, alpha_name=None):
+        """The blocking curve of ``predict_with_error(alpha, block=...)``: ``(var, block_lengths, n_blocks)`` with
+        ``var[l] = predict_with_error(alpha, block=block * 2**l)[1] ** 2`` (dims ``(level, alpha, *val_dims)``),
+        ``block_lengths[l][s] = block[s] * 2**l`` and ``n_blocks[l][s]`` the blocks of state s at level l, for every
+        level at which some state still has at least two blocks.  ONE block pass per 8 targets: block sums are additive,
+        so each level merges the pairs of the level below within every state.  Where var stops growing the blocks are
+        longer than the correlation time; a state that is down to one block contributes zero from that level on, and the
+        last levels are noisy (relative standard deviation about ``sqrt(2 / (sum_s n_blocks - K))``)."""
+        avals, alpha_name = self._alpha_values(alpha, alpha_name)
+        us, _, others, cshape = self._samples()
+        ns = [int(u.shape[0]) for u in us]
+        blk = engine.mbar_block_lengths(block, ns)
+        factors, _ = engine.mbar_block_levels(ns, blk)
+        _, res, C = self._block_gamma(avals, blk, n_levels=len(factors))
+        var = self._block_mean_variance(res, C)
+        out = DataArray(var.reshape(len(factors), len(avals), *cshape), ("level", alpha_name, *others),
+                        coords={"level": factors.copy(), alpha_name: avals})
+        return out, factors[:, None] * np.minimum(blk, np.asarray(ns, dtype=np.int64))[None, :], res.nblocks
+
+    def predict_with_covariance(self, alpha, alpha_name=None, cross_alpha=False, block=None):
         """(mean, cov): ``predict(alpha)`` bit for bit and the asymptotic covariance of the averages across the
         observable columns -- what the error bar of a sum, an integral over bins or a ratio of columns needs.  ``cov`` has
         dims (alpha, *val_dims, *[d + "_2" for d in val_dims]); its diagonal is ``predict_with_error``'s err squared.
         With ``cross_alpha=True`` the covariance also runs across the targets (at most 8): dims (alpha, *val_dims,
         alpha + "_2", *[d + "_2" ...]), which the error bar of a difference between two targets needs.  At most 255
         columns.  The assumptions are ``predict_with_error``'s: independent samples (``timeseries.decorrelate`` first),
-        first order in the fluctuations.  Two more passes over the samples per 8 targets; no re-solve."""
+        first order in the fluctuations.  Two more passes over the samples per 8 targets; no re-solve.
+
+        ``block=B`` (an int or one int per state): the blocked form for correlated series kept whole, with the
+        assumptions of ``predict_with_error(block=...)``; the Gram matrix of the block sums carries all targets of a
+        call, so both forms of ``cross_alpha`` come from the same pass."""
         from types import SimpleNamespace
 
         avals, alpha_name = self._alpha_values(alpha, alpha_name)
@@ -1880,13 +1944,23 @@ class MBARModel(StateCollection):
         if cross_alpha and len(avals) > 8:
             raise ValueError(f"predict_with_covariance(cross_alpha=True) takes at most 8 targets, got {len(avals)}")
         sol = self._solution()
-        means = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
-        gram, b = engine.mbar_cross_cov_sums(xs, us, self.alpha0, sol, avals, means, cross_alpha=cross_alpha)
         na = len(avals)
-        if cross_alpha:
-            cov = engine.mbar_mean_covariance(self._gram(), self._counts(), gram.reshape(na * C, na * C),
-                                              b.reshape(na * C, -1), pinv=self._reduced_pinv())
+        if block is not None:
+            means, res, _ = self._block_gamma(avals, block)
+            Gs, N, pinv = self._gram(), self._counts(), self._reduced_pinv()
+            covs = []
+            for i, gam in enumerate(res.gamma):
+                L = engine.mbar_block_coef_mean(Gs, N, res.b[8 * i:8 * i + 8], pinv=pinv)
+                if cross_alpha:
+                    covs.append(engine.mbar_block_covariance(gam[0], L))
+                else:
+                    covs += [engine.mbar_block_covariance(gam[0], L[a * C:(a + 1) * C]) for a in range(L.shape[0] // C)]
+            cov = covs[0] if cross_alpha else np.stack(covs)
         else:
+            means = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
+            gram, b = engine.mbar_cross_cov_sums(xs, us, self.alpha0, sol, avals, means, cross_alpha=cross_alpha)
+            if cross_alpha:
+                gram, b = gram.reshape(na * C, na * C), b.reshape(na * C, -1)
             cov = engine.mbar_mean_covariance(self._gram(), self._counts(), gram, b, pinv=self._reduced_pinv())
         dims, coords = (alpha_name, *others), {alpha_name: avals}
         mean = DataArray(means.cpu().numpy().reshape(na, *cshape), dims, coords=coords)
@@ -1985,24 +2059,48 @@ class MBARModel(StateCollection):
         Q, B, _, _, lnw = engine.mbar_cov_sums(x1, us, self.alpha0, sol, avals, means, with_lnw=True)
         return Q, B, lnw
 
-    def free_energy_covariance(self) -> np.ndarray:
-        """The K x K matrix Theta of the sampled states: var(f_i - f_j) = Theta_ii + Theta_jj - 2 Theta_ij."""
+    def _block_sampled_covariance(self, block) -> np.ndarray:
+        """The blocked covariance of the sampled states' f_i - f_0, (K, K): one block pass at the target alpha0[0] over the
+        first observable column (only the K sampled columns of Gamma are used)."""
+        _, res, _ = self._block_gamma(np.asarray(self.alpha0, dtype=float)[:1], block, first_column=True)
+        gam = res.gamma[0][0]
+        L = engine.mbar_block_coef_sampled(self._gram(), self._counts(), gam.shape[0], pinv=self._reduced_pinv())
+        return engine.mbar_block_covariance(gam, L)
+
+    def free_energy_covariance(self, block=None) -> np.ndarray:
+        """The K x K matrix Theta of the sampled states: var(f_i - f_j) = Theta_ii + Theta_jj - 2 Theta_ij.  With
+        ``block=B`` (``predict_with_error``'s, for correlated series kept whole) the blocked covariance of f_i - f_0 and
+        f_j - f_0, for which the same identity holds; its row and column 0 are zero."""
+        if block is not None:
+            return self._block_sampled_covariance(block)
         if "mbar_theta" not in self._cache:
             self._cache["mbar_theta"] = engine.mbar_theta(self._gram(), self._counts())
         return self._cache["mbar_theta"].copy()
 
-    def free_energy(self, alpha=None, alpha_name=None):
+    def free_energy(self, alpha=None, alpha_name=None, block=None):
         """(f, df) relative to state 0 (pymbar's compute_free_energy_differences, row 0): of the sampled states
-        (``alpha=None``: the cached solution, df[0] = 0), or of the targets ``alpha``, f(a) = -ln sum_n e^{-a u_n - logD_n}."""
+        (``alpha=None``: the cached solution, df[0] = 0), or of the targets ``alpha``, f(a) = -ln sum_n e^{-a u_n - logD_n}.
+        ``block=B``: df by batch means for correlated series kept whole (``predict_with_error``'s ``block``)."""
         if alpha is None:
             name = self.alpha_name if alpha_name is None else alpha_name
-            th = self.free_energy_covariance()
-            var = np.diag(th) + th[0, 0] - 2.0 * th[0]
+            if block is None:
+                th = self.free_energy_covariance()
+                var = np.diag(th) + th[0, 0] - 2.0 * th[0]
+            else:
+                var = np.diag(self._block_sampled_covariance(block)).copy()
             var[0] = 0.0
             coords = {name: np.asarray(self.alpha0, dtype=float)}
             return (DataArray(np.array(self._solution().f, dtype=float), (name,), coords=coords),
                     DataArray(np.sqrt(np.clip(var, 0.0, None)), (name,), coords=coords))
         avals, alpha_name = self._alpha_values(alpha, alpha_name)
+        coords = {alpha_name: avals}
+        if block is not None:
+            _, res, C = self._block_gamma(avals, block, first_column=True)
+            Gs, N, pinv = self._gram(), self._counts(), self._reduced_pinv()
+            var = np.concatenate([engine.mbar_block_variance(gam[0], engine.mbar_block_coef_target(
+                Gs, N, res.B[8 * i:8 * i + 8], C, pinv=pinv)) for i, gam in enumerate(res.gamma)])
+            return (DataArray(-res.lnw - float(self._solution().f[0]), (alpha_name,), coords=coords),
+                    DataArray(np.sqrt(np.clip(var, 0.0, None)), (alpha_name,), coords=coords))
         Q, B, lnw = self._target_sums(avals)
         K, N, Gs = len(self.states), self._counts(), self._gram()
         G = np.zeros((K + 1, K + 1))
@@ -2013,7 +2111,6 @@ class MBARModel(StateCollection):
             G[K, K] = Q[i]
             th = engine.mbar_theta(G, np.append(N, 0.0))
             var[i] = th[K, K] + th[0, 0] - 2.0 * th[0, K]
-        coords = {alpha_name: avals}
         return (DataArray(-lnw - float(self._solution().f[0]), (alpha_name,), coords=coords),
                 DataArray(np.sqrt(np.clip(var, 0.0, None)), (alpha_name,), coords=coords))
 
