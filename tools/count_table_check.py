@@ -7,6 +7,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import numpy as np, torch
 import thermoextrap_amd as txa
 from thermoextrap_amd import engine, _lib
+from oracle.count_table_oracle import decode  # the one decoder (tests/test_count_table_*.py hold the table to it)
 
 txa.require_gpu(0)
 L = _lib.load()
@@ -19,24 +20,11 @@ def table(s, rep_begin, nreps):
     return t
 
 
-def expand(t, N, nreps):
-    """table -> [ceil(nreps/128)*128][N] counts (numpy), undoing the operand order and the slid last tile"""
-    ntiles = (N + 1023) // 1024
-    G = (nreps + 127) // 128
-    a = t.cpu().numpy().reshape(G, ntiles, 32, 4, 2, 32, 16)  # g t s q half n32 b
-    a = a.transpose(0, 3, 5, 1, 2, 4, 6).reshape(G * 128, ntiles, 1024)  # rep, tile, sample-in-window
-    out = np.zeros((G * 128, N), dtype=np.int64)
-    for tt in range(ntiles):
-        b0 = min(tt * 1024, N - 1024)
-        out[:, b0:b0 + 1024] += a[:, tt]
-    return out
-
-
 for (N, nrep, rep0, rb, nr) in [(4096, 130, 0, 0, 130), (5000, 200, 7, 0, 200), (5000, 200, 7, 128, 72), (1024 * 37 + 5, 64, 0, 0, 64),
                                 (300000, 300, 1000, 128, 172), (2048, 1, 0, 0, 1)]:
     s = engine.DeviceSampler(123, nrep, N, rep0=rep0)
     f = s.freq().cpu().numpy()
-    e = expand(table(s, rb, nr), N, nr)
+    e = decode(table(s, rb, nr).cpu().numpy(), N, nr)
     live = min(nrep - rb, e.shape[0])
     ok = np.array_equal(e[:live], f[rb:rb + live]) and not e[live:].any()
     print(f"N={N} nrep={nrep} rep0={rep0} slab=[{rb},{rb+nr}): {'OK' if ok else 'MISMATCH'}", flush=True)
