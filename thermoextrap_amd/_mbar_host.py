@@ -192,6 +192,17 @@ def mbar_newton_batched(evaluate, N, b, f0, *, tol: float = 1e-12, max_iter: int
                         f"{err[worst]:.3e} > tol {tol:.1e}")
 
 
+def mbar_unpack_h(packed, K: int) -> np.ndarray:
+    """The symmetric (..., K, K) Hessian term from the evaluation passes' packed upper triangle (..., K (K + 1) / 2),
+    row-major: every entry is stored into both places, none is added to."""
+    packed = np.asarray(packed, dtype=np.float64)
+    iu = np.triu_indices(K)
+    H = np.zeros((*packed.shape[:-1], K, K))
+    H[..., iu[0], iu[1]] = packed
+    H[..., iu[1], iu[0]] = packed
+    return H
+
+
 _MBAR_PINV_CUT = 1e-12   # eigenvalues of I - sqrt(N) G sqrt(N) below this fraction of the largest are its null space
 
 

@@ -32,12 +32,6 @@
 
 namespace txm {
 
-__device__ inline int64_t state_offset(const txm_mbar_state *tab, int s) {
-  int64_t off = 0;
-  for (int t = 0; t < s; ++t) off += tab[t].n;
-  return off;
-}
-
 __device__ inline double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -61,7 +55,7 @@ __global__ __launch_bounds__(MB_BLOCK) void mbar_eval_kernel(const txm_mbar_stat
   const int s = blockIdx.y;
   const double *__restrict__ u = tab[s].u;
   const int64_t n = tab[s].n;
-  const int64_t off = state_offset(tab, s);
+  const int64_t off = mb_state_offset(tab, s);
   double g[K], a0[K], S[K], H[NH], obj = 0.0;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -141,7 +135,7 @@ __global__ __launch_bounds__(MB_BLOCK) void mbar_eval_lds_kernel(const txm_mbar_
   const int s = blockIdx.y;
   const double *__restrict__ u = tab[s].u;
   const int64_t n = tab[s].n;
-  const int64_t off = state_offset(tab, s);
+  const int64_t off = mb_state_offset(tab, s);
   if (tid < K) {
     sg[tid] = gk[tid];
     sa[tid] = a0k[tid];
@@ -240,7 +234,7 @@ __global__ __launch_bounds__(MB_BLOCK) void mbar_max_kernel(const txm_mbar_state
   const int s = blockIdx.y;
   const double *__restrict__ u = tab[s].u;
   const int64_t n = tab[s].n;
-  const int64_t off = state_offset(tab, s);
+  const int64_t off = mb_state_offset(tab, s);
   double m[MB_MAXA];
 #pragma unroll
   for (int a = 0; a < MB_MAXA; ++a) m[a] = -INFINITY;
@@ -302,7 +296,7 @@ __global__ __launch_bounds__(MB_BLOCK) void mbar_predict_kernel(const txm_mbar_s
   const double *__restrict__ x = tab[s].x;
   const double *__restrict__ u = tab[s].u;
   const int64_t N = tab[s].n, ldx_s = tab[s].ldx_s;
-  const int64_t off = state_offset(tab, s);
+  const int64_t off = mb_state_offset(tab, s);
   const int64_t col0 = (int64_t)blockIdx.y * (LPR * VEC) + (int64_t)lir * VEC;
   const bool col_ok = col0 < C;
   double Ma[NA];
@@ -415,37 +409,11 @@ __global__ __launch_bounds__(MB_BLOCK) void mbar_predict_final_kernel(const doub
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-static int64_t mb_blocks_per_state(int64_t K) {
-  int64_t cap = (int64_t)num_cus() * 8 / K;  // at most num_cus * 8 blocks over all states
-  return cap < 1 ? 1 : cap;
-}
-
 static int64_t mb_cols_pad_bound(int64_t C) {  // as txm_perturb_ws_bytes
   int64_t cols_pad = 1;
   while (cols_pad < C) cols_pad <<= 1;
   if (cols_pad > 512) cols_pad = cdiv(C, 512) * 512;
   return cols_pad;
-}
-
-static int mb_check_states(const txm_mbar_state *states_host, int32_t K, bool need_x, int64_t C, const char *what,
-                           int64_t *ntot, int64_t *nmax) {
-  TXM_REQUIRE(states_host, "%s: null state table", what);
-  TXM_REQUIRE(K >= 1 && K <= MB_MAXK, "%s: K = %d states outside [1, %d]", what, (int)K, MB_MAXK);
-  *ntot = 0;
-  *nmax = 0;
-  for (int32_t s = 0; s < K; ++s) {
-    const txm_mbar_state &st = states_host[s];
-    TXM_REQUIRE(st.u, "%s: state %d has a null u", what, (int)s);
-    TXM_REQUIRE(st.n >= 1, "%s: state %d has n = %lld samples (need >= 1)", what, (int)s, (long long)st.n);
-    if (need_x) {
-      TXM_REQUIRE(st.x, "%s: state %d has a null x", what, (int)s);
-      TXM_REQUIRE(st.ldx_s >= C, "%s: state %d has row pitch ldx_s = %lld < C = %lld", what, (int)s,
-                  (long long)st.ldx_s, (long long)C);
-    }
-    *ntot += st.n;
-    *nmax = st.n > *nmax ? st.n : *nmax;
-  }
-  return TXM_OK;
 }
 
 }  // namespace txm
@@ -468,27 +436,19 @@ extern "C" int txm_mbar_eval(const txm_mbar_state *states_host, int32_t K, const
                              const double *g_host, double upiv, double *out, double *logD, void *ws, size_t ws_bytes,
                              txm_stream stream) {
   int64_t ntot = 0, nmax = 0;
-  const int rc = mb_check_states(states_host, K, false, 0, "mbar_eval", &ntot, &nmax);
-  if (rc != TXM_OK) return rc;
+  if (const int rc = mb_check_states(states_host, K, false, false, 0, "mbar_eval", &ntot, &nmax)) return rc;
   TXM_REQUIRE(alpha0_host && g_host && out && ws, "mbar_eval: null pointer");
-  for (int32_t k = 0; k < K; ++k)
-    TXM_REQUIRE(std::isfinite(alpha0_host[k]) && std::isfinite(g_host[k]), "mbar_eval: alpha0 / g of state %d not finite",
-                (int)k);
-  TXM_REQUIRE(std::isfinite(upiv), "mbar_eval: pivot not finite");
+  if (const int rc = mb_check_finite("mbar_eval", K, alpha0_host, g_host, 0, nullptr, upiv)) return rc;
   if (ws_bytes < txm_mbar_ws_bytes(K, 1, 1)) {
     set_error("mbar_eval: workspace too small");
     return TXM_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
   // one staging copy: state table, g, alpha0
-  unsigned char head[MB_TAB_BYTES] = {};
-  memcpy(head, states_host, (size_t)K * sizeof(txm_mbar_state));
-  memcpy(head + MB_MAXK * sizeof(txm_mbar_state), g_host, (size_t)K * sizeof(double));
-  memcpy(head + MB_MAXK * sizeof(txm_mbar_state) + MB_MAXK * sizeof(double), alpha0_host, (size_t)K * sizeof(double));
-  TXM_HIP(hipMemcpyAsync(ws, head, MB_TAB_BYTES, hipMemcpyHostToDevice, st));
-  const txm_mbar_state *tab = (const txm_mbar_state *)ws;
-  const double *gk = (const double *)((char *)ws + MB_MAXK * sizeof(txm_mbar_state));
-  const double *a0k = gk + MB_MAXK;
+  MbarHead h;
+  if (const int rc = mb_stage_head(ws, states_host, K, g_host, alpha0_host, MB_TAB_BYTES, nullptr, 0, st, &h)) return rc;
+  const txm_mbar_state *tab = h.tab;
+  const double *gk = h.gk, *a0k = h.a0k;
   double *partial = (double *)((char *)ws + MB_HEAD_BYTES);
   const int NV = K + K * (K + 1) / 2 + 1;
   int64_t gx;
@@ -526,31 +486,25 @@ extern "C" int txm_mbar_predict(const txm_mbar_state *states_host, int32_t K, in
                                 size_t ws_bytes, txm_stream stream) {
   TXM_REQUIRE(C >= 1 && C <= 65535, "mbar_predict: C = %lld outside [1, 65535]", (long long)C);
   int64_t ntot = 0, nmax = 0;
-  const int rc = mb_check_states(states_host, K, true, C, "mbar_predict", &ntot, &nmax);
-  if (rc != TXM_OK) return rc;
+  if (const int rc = mb_check_states(states_host, K, true, false, C, "mbar_predict", &ntot, &nmax)) return rc;
   TXM_REQUIRE(logD && alpha_host && out && ws, "mbar_predict: null pointer");
   TXM_REQUIRE(n_alpha >= 1 && n_alpha <= MB_MAXA, "mbar_predict: n_alpha = %d outside [1, %d]", (int)n_alpha, MB_MAXA);
-  TXM_REQUIRE(std::isfinite(upiv), "mbar_predict: pivot not finite");
+  if (const int rc = mb_check_finite("mbar_predict", K, nullptr, nullptr, 0, nullptr, upiv)) return rc;  // (targets: not looked at)
   if (ws_bytes < txm_mbar_ws_bytes(K, C, n_alpha)) {
     set_error("mbar_predict: workspace too small");
     return TXM_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
+  // only the K entries of the state table, straight from the caller
   TXM_HIP(hipMemcpyAsync(ws, states_host, (size_t)K * sizeof(txm_mbar_state), hipMemcpyHostToDevice, st));
-  const txm_mbar_state *tab = (const txm_mbar_state *)ws;
-  double *M = (double *)((char *)ws + MB_TAB_BYTES);
+  const MbarHead h = mb_head(ws);
+  const txm_mbar_state *tab = h.tab;
+  double *M = h.M;
   double *partial = (double *)((char *)ws + MB_HEAD_BYTES);
-  MbarTargets ta;
-  for (int a = 0; a < MB_MAXA; ++a) ta.a[a] = alpha_host[a < n_alpha ? a : n_alpha - 1];
+  const MbarTargets ta = mb_targets(alpha_host, n_alpha);
   // exact per-target maximum of the exponent
   const int64_t cap = mb_blocks_per_state(K);
-  int64_t gm = cdiv(nmax, (int64_t)MB_BLOCK * 8);
-  gm = gm > cap ? cap : (gm < 1 ? 1 : gm);
-  hipLaunchKernelGGL(mbar_max_kernel, dim3((unsigned)gm, (unsigned)K), dim3(MB_BLOCK), 0, st, tab, logD, upiv, ta,
-                     partial);
-  TXM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mbar_max_final_kernel, dim3(1), dim3(MB_BLOCK), 0, st, partial, (int)(gm * K), M);
-  TXM_LAUNCH_CHECK();
+  if (const int rc = mb_max_pass(tab, K, nmax, cap, logD, upiv, ta, partial, M, st)) return rc;
   // the contraction: txm_perturb's plan (a lane owns VEC columns, 2^l2 lanes span a row); VEC = 2 when every state allows it
   bool v2 = (C % 2 == 0);
   for (int32_t s = 0; s < K && v2; ++s)

@@ -59,12 +59,7 @@ struct MkState {
   int64_t choff, nch;          // first chunk, chunks
 };
 constexpr size_t MK_HEAD_BYTES = MB_HEAD_BYTES + MB_MAXK * sizeof(MkState);
-
-__device__ inline int64_t mk_state_offset(const txm_mbar_state *tab, int s) {
-  int64_t off = 0;
-  for (int t = 0; t < s; ++t) off += tab[t].n;
-  return off;
-}
+static_assert(MB_MAXK * sizeof(MkState) <= MB_EXTRA_BYTES, "txm_mbar.h: mb_stage_head's buffer holds the block table");
 
 // grid (unit workgroups, K)
 template <int NA>
@@ -82,7 +77,7 @@ __global__ __launch_bounds__(MB_BLOCK) void mbar_block_sums_kernel(const txm_mba
   const int tid = threadIdx.x, s = blockIdx.y;
   const double *__restrict__ x = tab[s].x;
   const double *__restrict__ u = tab[s].u;
-  const int64_t n = tab[s].n, ldx = tab[s].ldx_s, off = mk_state_offset(tab, s);
+  const int64_t n = tab[s].n, ldx = tab[s].ldx_s, off = mb_state_offset(tab, s);
   const MkState st = mk[s];
   if (tid < K) {
     sg[tid] = gk[tid];
@@ -301,8 +296,6 @@ struct MkPlan {
   MkState st[MB_MAXK];
 };
 
-static int mk_class(int32_t n_alpha) { return n_alpha == 1 ? 1 : (n_alpha == 2 ? 2 : (n_alpha <= 4 ? 4 : 8)); }
-
 static int mk_check_shape(const char *who, const int64_t *n_host, const int64_t *block_host, int32_t K, int64_t C,
                           int32_t n_alpha, int32_t n_levels) {
   TXM_REQUIRE(K >= 1 && K <= MB_MAXK, "%s: K = %d states outside [1, %d]", who, (int)K, MB_MAXK);
@@ -393,20 +386,10 @@ extern "C" int txm_mbar_block_cov(const txm_mbar_state *states_host, int32_t K, 
   int64_t n_host[MB_MAXK];
   for (int32_t s = 0; s < K; ++s) n_host[s] = states_host[s].n;
   if (const int rc = mk_check_shape("mbar_block_cov", n_host, block_host, K, C, n_alpha, n_levels)) return rc;
-  for (int32_t s = 0; s < K; ++s) {
-    const txm_mbar_state &st = states_host[s];
-    TXM_REQUIRE(st.u && st.x, "mbar_block_cov: state %d has a null u or x", (int)s);
-    TXM_REQUIRE(st.ldx_s >= C, "mbar_block_cov: state %d has row pitch ldx_s = %lld < C = %lld", (int)s,
-                (long long)st.ldx_s, (long long)C);
-  }
+  if (const int rc = mb_check_states(states_host, K, true, true, C, "mbar_block_cov", nullptr, nullptr)) return rc;
   TXM_REQUIRE(alpha0_host && g_host && logD && alpha_host && mean && lnw && gamma && nblocks && ws,
               "mbar_block_cov: null pointer");
-  for (int32_t k = 0; k < K; ++k)
-    TXM_REQUIRE(std::isfinite(alpha0_host[k]) && std::isfinite(g_host[k]),
-                "mbar_block_cov: alpha0 / g of state %d not finite", (int)k);
-  for (int32_t a = 0; a < n_alpha; ++a)
-    TXM_REQUIRE(std::isfinite(alpha_host[a]), "mbar_block_cov: target %d not finite", (int)a);
-  TXM_REQUIRE(std::isfinite(upiv), "mbar_block_cov: pivot not finite");
+  if (const int rc = mb_check_finite("mbar_block_cov", K, alpha0_host, g_host, n_alpha, alpha_host, upiv)) return rc;
   MkPlan p;
   if (mk_plan(n_host, block_host, K, C, n_alpha, n_levels, ws_bytes, &p) != TXM_OK) {
     set_error("mbar_block_cov: workspace too small (%zu bytes, the smallest plan needs %zu)", ws_bytes, p.bytes);
@@ -414,41 +397,31 @@ extern "C" int txm_mbar_block_cov(const txm_mbar_state *states_host, int32_t K, 
   }
   hipStream_t st = (hipStream_t)stream;
   // one staging copy: state table, g, alpha0 (the head of txm_mbar_eval), then the block table
-  std::vector<unsigned char> head(MK_HEAD_BYTES, 0);
-  memcpy(head.data(), states_host, (size_t)K * sizeof(txm_mbar_state));
-  memcpy(head.data() + MB_MAXK * sizeof(txm_mbar_state), g_host, (size_t)K * sizeof(double));
-  memcpy(head.data() + MB_MAXK * sizeof(txm_mbar_state) + MB_MAXK * sizeof(double), alpha0_host, (size_t)K * sizeof(double));
-  memcpy(head.data() + MB_HEAD_BYTES, p.st, (size_t)K * sizeof(MkState));
-  TXM_HIP(hipMemcpyAsync(ws, head.data(), MK_HEAD_BYTES, hipMemcpyHostToDevice, st));
+  MbarHead h;
+  if (const int rc = mb_stage_head(ws, states_host, K, g_host, alpha0_host, MK_HEAD_BYTES, p.st, (size_t)K * sizeof(MkState), st,
+                                   &h))
+    return rc;
   std::vector<int64_t> counts((size_t)n_levels * K);
   for (int l = 0; l < n_levels; ++l)
     for (int32_t s = 0; s < K; ++s) counts[(size_t)l * K + s] = mk_level_blocks(p.st[s].nb, l);
   TXM_HIP(hipMemcpyAsync(nblocks, counts.data(), counts.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  const txm_mbar_state *tab = (const txm_mbar_state *)ws;
-  const double *gk = (const double *)((char *)ws + MB_MAXK * sizeof(txm_mbar_state));
-  const double *a0k = gk + MB_MAXK;
+  const txm_mbar_state *tab = h.tab;
+  const double *gk = h.gk, *a0k = h.a0k;
   const MkState *mk = (const MkState *)((char *)ws + MB_HEAD_BYTES);
   double *base = (double *)((char *)ws + MK_HEAD_BYTES);
   double *T = base, *L1 = base + p.off_l1, *part = base + p.off_part, *csum = base + p.off_csum, *tot = base + p.off_tot;
   double *G = base + p.off_G, *partial = base + p.off_partial;
-  MbarTargets ta;
-  for (int a = 0; a < MB_MAXA; ++a) ta.a[a] = alpha_host[a < n_alpha ? a : n_alpha - 1];
+  const MbarTargets ta = mb_targets(alpha_host, n_alpha);
 
   int cp_log2 = 1;
   while ((1 << cp_log2) < C + 1) ++cp_log2;  // <= 8: C + 1 <= 256
-  int64_t cap = (int64_t)num_cus() * 8 / K;
-  cap = cap < 1 ? 1 : cap;
+  const int64_t cap = mb_blocks_per_state(K);
   const int64_t gx = p.max_units > cap ? cap : p.max_units;
   const dim3 block(MB_BLOCK);
 #define TXM_MK(NA_)                                                                                                        \
   hipLaunchKernelGGL((mbar_block_sums_kernel<NA_>), dim3((unsigned)gx, (unsigned)K), block, 0, st, tab, mk, (int)K, (int)C, \
                      cp_log2, gk, a0k, logD, upiv, ta, lnw, mean, (int)n_alpha, p.M, T, part)
-  switch (mk_class(n_alpha)) {
-    case 1: TXM_MK(1); break;
-    case 2: TXM_MK(2); break;
-    case 4: TXM_MK(4); break;
-    default: TXM_MK(8);
-  }
+  TXM_MB_NA_DISPATCH(n_alpha, TXM_MK)
 #undef TXM_MK
   TXM_LAUNCH_CHECK();
   const int64_t rows_cap = (int64_t)num_cus() * 16;

@@ -26,7 +26,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "txm_common.h"
+#include "txm_mbar.h"  // mb_check_state, mb_na_class
 #include "txm_sampler.h"
 
 namespace txm {
@@ -505,8 +505,6 @@ static int bt_lpr_log2(int64_t C) {
   return l2;
 }
 
-static int bt_na_pad(int32_t n_alpha) { return n_alpha <= 1 ? 1 : n_alpha <= 2 ? 2 : n_alpha <= 4 ? 4 : 8; }
-
 // checks the two host tables and fills the device table; TC = chunks over all states, maxch = most of one state
 static int bt_check(const txm_mbar_state *states, const txm_mbar_boot_state *samp, int32_t K, bool need_x, int64_t C,
                     const char *what, BootDev *dev, int64_t *ntot, int64_t *nrep, int64_t *TC, int *maxch) {
@@ -521,15 +519,9 @@ static int bt_check(const txm_mbar_state *states, const txm_mbar_boot_state *sam
   for (int32_t s = 0; s < K; ++s) {
     const txm_mbar_state &st = states[s];
     const txm_sampler_spec &sp = samp[s].spec;
-    TXM_REQUIRE(st.u, "%s: state %d has a null u", what, (int)s);
-    TXM_REQUIRE(st.n >= 1, "%s: state %d has n = %lld samples (need >= 1)", what, (int)s, (long long)st.n);
+    if (const int rc = mb_check_state(st, s, need_x, false, C, what)) return rc;
     TXM_REQUIRE(st.n <= ((int64_t)1 << 30), "%s: state %d has n = %lld samples (sampler limit 2^30)", what, (int)s,
                 (long long)st.n);
-    if (need_x) {
-      TXM_REQUIRE(st.x, "%s: state %d has a null x", what, (int)s);
-      TXM_REQUIRE(st.ldx_s >= C, "%s: state %d has row pitch ldx_s = %lld < C = %lld", what, (int)s,
-                  (long long)st.ldx_s, (long long)C);
-    }
     TXM_REQUIRE(samp[s].counts, "%s: state %d has null sampler counts", what, (int)s);
     TXM_REQUIRE(sp.ndat == st.n, "%s: state %d: sampler ndat = %lld but n = %lld", what, (int)s, (long long)sp.ndat,
                 (long long)st.n);
@@ -576,7 +568,7 @@ extern "C" size_t txm_mbar_boot_ws_bytes(int32_t K, int64_t C, int32_t n_alpha, 
   const int l2 = bt_lpr_log2(C);
   const size_t cpad = (size_t)cdiv(C, (int64_t)1 << l2) << l2;
   const size_t pe = (size_t)nrep * TC * nv;
-  const size_t pp = (size_t)nrep * TC * (size_t)bt_na_pad(n_alpha) * (cpad + 1);
+  const size_t pp = (size_t)nrep * TC * (size_t)mb_na_class(n_alpha) * (cpad + 1);
   return BT_HEAD_BYTES + BT_REFMAX_BYTES + (pe > pp ? pe : pp) * sizeof(double) + 256;
 }
 
@@ -690,21 +682,19 @@ extern "C" int txm_mbar_boot_predict(const txm_mbar_state *states_host, const tx
   TXM_LAUNCH_CHECK();
   hipLaunchKernelGGL(mbar_boot_refmax_final_kernel, dim3(1), dim3(256), 0, st, pmax, (int)(gm * K), Mref);
   TXM_LAUNCH_CHECK();
-  const int NA = bt_na_pad(n_alpha);
+  const int NA = mb_na_class(n_alpha);
   const dim3 grid((unsigned)blocks), block(BT_WAVES * 64);
-  switch (NA) {
 #define TXM_BT_PRED(NA_)                                                                                              \
-  case NA_:                                                                                                           \
+  do {                                                                                                                \
     if (l2 >= 3)                                                                                                      \
       hipLaunchKernelGGL((mbar_boot_predict_kernel<NA_, true>), grid, block, 0, st, tab, (int)K, C, l2, cpad, a0k, g, \
                          gref, Mref, ta, upiv, nrep, ngroups, maxch, TC, partial);                                    \
     else                                                                                                              \
       hipLaunchKernelGGL((mbar_boot_predict_kernel<NA_, false>), grid, block, 0, st, tab, (int)K, C, l2, cpad, a0k,   \
                          g, gref, Mref, ta, upiv, nrep, ngroups, maxch, TC, partial);                                 \
-    break;
-    TXM_BT_PRED(1) TXM_BT_PRED(2) TXM_BT_PRED(4) TXM_BT_PRED(8)
+  } while (0)
+  TXM_MB_NA_DISPATCH(n_alpha, TXM_BT_PRED)
 #undef TXM_BT_PRED
-  }
   TXM_LAUNCH_CHECK();
   hipLaunchKernelGGL(mbar_boot_predict_final_kernel, dim3((unsigned)cdiv(nrep * n_alpha * C, 256)), dim3(256), 0, st,
                      partial, nrep, TC, NA, (int)n_alpha, C, cpad, out);

@@ -36,12 +36,6 @@ constexpr int CV_LDP = 17;                // row pitch of P (16 rows + one pad d
 constexpr int CV_ROWS = 17;               // partial rows per target: 16 matrix rows, then yy
 constexpr int CV_PART = MB_MAXA * CV_ROWS * 16;  // doubles per workgroup
 
-__device__ inline int64_t cv_state_offset(const txm_mbar_state *tab, int s) {
-  int64_t off = 0;
-  for (int t = 0; t < s; ++t) off += tab[t].n;
-  return off;
-}
-
 // grid (sample blocks, column groups, K * RT); partial [state][gridDim.x][NCG][RT][MB_MAXA][CV_ROWS][16]
 template <int NA>
 __global__ __launch_bounds__(MB_BLOCK) void mbar_cov_kernel(const txm_mbar_state *__restrict__ tab, int K, int RT,
@@ -60,7 +54,7 @@ __global__ __launch_bounds__(MB_BLOCK) void mbar_cov_kernel(const txm_mbar_state
   const double *__restrict__ x = tab[s].x;
   const double *__restrict__ u = tab[s].u;
   const int64_t n = tab[s].n, ldx = tab[s].ldx_s;
-  const int64_t off = cv_state_offset(tab, s);
+  const int64_t off = mb_state_offset(tab, s);
   const int row0 = 16 * rt;  // logical rows row0 .. row0 + 15: k < K the states, K the row of ones, above it zeros
   if (tid < K) {
     sg[tid] = gk[tid];
@@ -223,7 +217,7 @@ extern "C" size_t txm_mbar_cov_ws_bytes(int32_t K, int64_t C, int32_t n_alpha) {
   int64_t ncg, rt, cap;
   cv_plan(K, C, &ncg, &rt, &cap);
   const size_t pcov = (size_t)K * cap * ncg * rt * CV_PART;
-  const size_t pmax = (size_t)K * (size_t)((int64_t)num_cus() * 8 / K < 1 ? 1 : (int64_t)num_cus() * 8 / K) * MB_MAXA;
+  const size_t pmax = (size_t)K * (size_t)mb_blocks_per_state(K) * MB_MAXA;
   return MB_HEAD_BYTES + (pcov > pmax ? pcov : pmax) * sizeof(double) + 256;
 }
 
@@ -235,50 +229,25 @@ extern "C" int txm_mbar_cov(const txm_mbar_state *states_host, int32_t K, int64_
   TXM_REQUIRE(states_host && K >= 1 && K <= MB_MAXK, "mbar_cov: K = %d states outside [1, %d] or a null state table",
               (int)K, MB_MAXK);
   int64_t nmax = 0;
-  for (int32_t s = 0; s < K; ++s) {
-    const txm_mbar_state &st = states_host[s];
-    TXM_REQUIRE(st.u && st.x, "mbar_cov: state %d has a null u or x", (int)s);
-    TXM_REQUIRE(st.n >= 1, "mbar_cov: state %d has n = %lld samples (need >= 1)", (int)s, (long long)st.n);
-    TXM_REQUIRE(st.ldx_s >= C, "mbar_cov: state %d has row pitch ldx_s = %lld < C = %lld", (int)s, (long long)st.ldx_s,
-                (long long)C);
-    nmax = st.n > nmax ? st.n : nmax;
-  }
+  if (const int rc = mb_check_states(states_host, K, true, true, C, "mbar_cov", nullptr, &nmax)) return rc;
   TXM_REQUIRE(alpha0_host && g_host && logD && alpha_host && mean && out && ws, "mbar_cov: null pointer");
   TXM_REQUIRE(n_alpha >= 1 && n_alpha <= MB_MAXA, "mbar_cov: n_alpha = %d outside [1, %d]", (int)n_alpha, MB_MAXA);
-  for (int32_t k = 0; k < K; ++k)
-    TXM_REQUIRE(std::isfinite(alpha0_host[k]) && std::isfinite(g_host[k]), "mbar_cov: alpha0 / g of state %d not finite",
-                (int)k);
-  for (int32_t a = 0; a < n_alpha; ++a)
-    TXM_REQUIRE(std::isfinite(alpha_host[a]), "mbar_cov: target %d not finite", (int)a);
-  TXM_REQUIRE(std::isfinite(upiv), "mbar_cov: pivot not finite");
+  if (const int rc = mb_check_finite("mbar_cov", K, alpha0_host, g_host, n_alpha, alpha_host, upiv)) return rc;
   if (ws_bytes < txm_mbar_cov_ws_bytes(K, C, n_alpha)) {
     set_error("mbar_cov: workspace too small");
     return TXM_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
   // one staging copy: state table, g, alpha0 (the head of txm_mbar_eval)
-  unsigned char head[MB_TAB_BYTES] = {};
-  memcpy(head, states_host, (size_t)K * sizeof(txm_mbar_state));
-  memcpy(head + MB_MAXK * sizeof(txm_mbar_state), g_host, (size_t)K * sizeof(double));
-  memcpy(head + MB_MAXK * sizeof(txm_mbar_state) + MB_MAXK * sizeof(double), alpha0_host, (size_t)K * sizeof(double));
-  TXM_HIP(hipMemcpyAsync(ws, head, MB_TAB_BYTES, hipMemcpyHostToDevice, st));
-  const txm_mbar_state *tab = (const txm_mbar_state *)ws;
-  const double *gk = (const double *)((char *)ws + MB_MAXK * sizeof(txm_mbar_state));
-  const double *a0k = gk + MB_MAXK;
-  double *M = (double *)((char *)ws + MB_TAB_BYTES);
+  MbarHead h;
+  if (const int rc = mb_stage_head(ws, states_host, K, g_host, alpha0_host, MB_TAB_BYTES, nullptr, 0, st, &h)) return rc;
+  const txm_mbar_state *tab = h.tab;
+  const double *gk = h.gk, *a0k = h.a0k;
+  double *M = h.M;
   double *partial = (double *)((char *)ws + MB_HEAD_BYTES);
-  MbarTargets ta;
-  for (int a = 0; a < MB_MAXA; ++a) ta.a[a] = alpha_host[a < n_alpha ? a : n_alpha - 1];
+  const MbarTargets ta = mb_targets(alpha_host, n_alpha);
   // exact per-target maximum of the exponent (predict's pass)
-  int64_t capm = (int64_t)num_cus() * 8 / K;
-  capm = capm < 1 ? 1 : capm;
-  int64_t gm = cdiv(nmax, (int64_t)MB_BLOCK * 8);
-  gm = gm > capm ? capm : (gm < 1 ? 1 : gm);
-  hipLaunchKernelGGL(mbar_max_kernel, dim3((unsigned)gm, (unsigned)K), dim3(MB_BLOCK), 0, st, tab, logD, upiv, ta,
-                     partial);
-  TXM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mbar_max_final_kernel, dim3(1), dim3(MB_BLOCK), 0, st, partial, (int)(gm * K), M);
-  TXM_LAUNCH_CHECK();
+  if (const int rc = mb_max_pass(tab, K, nmax, mb_blocks_per_state(K), logD, upiv, ta, partial, M, st)) return rc;
   int64_t ncg, rt, cap;
   cv_plan(K, C, &ncg, &rt, &cap);
   int64_t gx = cdiv(nmax, (int64_t)CV_TILE * 4);
@@ -287,10 +256,7 @@ extern "C" int txm_mbar_cov(const txm_mbar_state *states_host, int32_t K, int64_
 #define TXM_CV(NA_)                                                                                                 \
   hipLaunchKernelGGL((mbar_cov_kernel<NA_>), grid, block, 0, st, tab, (int)K, (int)rt, C, gk, a0k, logD, upiv, ta, M, \
                      mean, (int)n_alpha, partial)
-  if (n_alpha == 1) TXM_CV(1);
-  else if (n_alpha == 2) TXM_CV(2);
-  else if (n_alpha <= 4) TXM_CV(4);
-  else TXM_CV(8);
+  TXM_MB_NA_DISPATCH(n_alpha, TXM_CV)
 #undef TXM_CV
   TXM_LAUNCH_CHECK();
   hipLaunchKernelGGL(mbar_cov_final_kernel, dim3((unsigned)(1 + K + C * (1 + K)), (unsigned)n_alpha), dim3(MB_BLOCK), 0,

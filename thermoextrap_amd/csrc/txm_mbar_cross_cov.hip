@@ -227,10 +227,7 @@ static int xc_launch(const XcPlan &p, const txm_mbar_state *tab, int K, int C, c
 #define TXM_XC(NA_)                                                                                                    \
   hipLaunchKernelGGL((mbar_cross_cov_kernel<NA_, CROSS>), grid, block, 0, st, tab, K, C, (int)p.T, logD, upiv, ta, lnw, \
                      mean, n_alpha, partial)
-  if (n_alpha == 1) TXM_XC(1);
-  else if (n_alpha == 2) TXM_XC(2);
-  else if (n_alpha <= 4) TXM_XC(4);
-  else TXM_XC(8);
+  TXM_MB_NA_DISPATCH(n_alpha, TXM_XC)
 #undef TXM_XC
   TXM_LAUNCH_CHECK();
   const int64_t M = CROSS ? (int64_t)n_alpha * C : (int64_t)C;
@@ -264,20 +261,10 @@ extern "C" int txm_mbar_cross_cov(const txm_mbar_state *states_host, int32_t K, 
                                   const double *alpha_host, int32_t n_alpha, const double *mean, const double *lnw,
                                   int32_t cross_alpha, double *out, void *ws, size_t ws_bytes, txm_stream stream) {
   if (const int rc = xc_check_shape("mbar_cross_cov", K, C, n_alpha, cross_alpha)) return rc;
-  TXM_REQUIRE(states_host, "mbar_cross_cov: null state table");
   int64_t nmax = 0;
-  for (int32_t s = 0; s < K; ++s) {
-    const txm_mbar_state &st = states_host[s];
-    TXM_REQUIRE(st.u && st.x, "mbar_cross_cov: state %d has a null u or x", (int)s);
-    TXM_REQUIRE(st.n >= 1, "mbar_cross_cov: state %d has n = %lld samples (need >= 1)", (int)s, (long long)st.n);
-    TXM_REQUIRE(st.ldx_s >= C, "mbar_cross_cov: state %d has row pitch ldx_s = %lld < C = %lld", (int)s,
-                (long long)st.ldx_s, (long long)C);
-    nmax = st.n > nmax ? st.n : nmax;
-  }
+  if (const int rc = mb_check_states(states_host, K, true, true, C, "mbar_cross_cov", nullptr, &nmax)) return rc;
   TXM_REQUIRE(logD && alpha_host && mean && lnw && out && ws, "mbar_cross_cov: null pointer");
-  for (int32_t a = 0; a < n_alpha; ++a)
-    TXM_REQUIRE(std::isfinite(alpha_host[a]), "mbar_cross_cov: target %d not finite", (int)a);
-  TXM_REQUIRE(std::isfinite(upiv), "mbar_cross_cov: pivot not finite");
+  if (const int rc = mb_check_finite("mbar_cross_cov", K, nullptr, nullptr, n_alpha, alpha_host, upiv)) return rc;
   XcPlan p;
   if (xc_plan(C, n_alpha, cross_alpha, nmax, ws_bytes, &p) != TXM_OK) {
     set_error("mbar_cross_cov: workspace too small (%zu bytes, the smallest plan needs %zu)", ws_bytes, p.bytes);
@@ -285,13 +272,12 @@ extern "C" int txm_mbar_cross_cov(const txm_mbar_state *states_host, int32_t K, 
   }
   hipStream_t st = (hipStream_t)stream;
   // the state table at the head of the workspace, where txm_mbar_cov keeps it
-  unsigned char head[MB_MAXK * sizeof(txm_mbar_state)] = {};
-  memcpy(head, states_host, (size_t)K * sizeof(txm_mbar_state));
-  TXM_HIP(hipMemcpyAsync(ws, head, sizeof(head), hipMemcpyHostToDevice, st));
-  const txm_mbar_state *tab = (const txm_mbar_state *)ws;
+  MbarHead h;
+  if (const int rc = mb_stage_head(ws, states_host, K, nullptr, nullptr, MB_MAXK * sizeof(txm_mbar_state), nullptr, 0, st, &h))
+    return rc;
+  const txm_mbar_state *tab = h.tab;
   double *partial = (double *)((char *)ws + MB_HEAD_BYTES);
-  MbarTargets ta;
-  for (int a = 0; a < MB_MAXA; ++a) ta.a[a] = alpha_host[a < n_alpha ? a : n_alpha - 1];
+  const MbarTargets ta = mb_targets(alpha_host, n_alpha);
   if (cross_alpha)
     return xc_launch<true>(p, tab, (int)K, (int)C, logD, upiv, ta, lnw, mean, (int)n_alpha, partial, out, st);
   return xc_launch<false>(p, tab, (int)K, (int)C, logD, upiv, ta, lnw, mean, (int)n_alpha, partial, out, st);

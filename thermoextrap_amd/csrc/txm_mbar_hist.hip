@@ -47,6 +47,7 @@ constexpr int HH_ACC = 32;      // accumulator tiles per wave: targets (1, 2, 4 
 constexpr int HH_MAXBINS = 1023;  // nbins + 1 columns: at most 64 bin tiles
 // the workspace head of the MBAR entry points (state table, g, alpha0, M), then the K device pointers of the bin indices
 constexpr size_t HH_HEAD_BYTES = MB_HEAD_BYTES + MB_MAXK * sizeof(void *);
+static_assert(MB_MAXK * sizeof(void *) <= MB_EXTRA_BYTES, "txm_mbar.h: mb_stage_head's buffer holds the bin pointers");
 
 // partial [gridDim.x][gridDim.y][gridDim.z][n_alpha][bt][256]
 template <int NA, int BT>
@@ -229,14 +230,12 @@ struct HhPlan {
   size_t bytes;
 };
 
-static int hh_class(int32_t n_alpha) { return n_alpha == 1 ? 1 : (n_alpha == 2 ? 2 : (n_alpha <= 4 ? 4 : 8)); }
-
 // The launch plan from the bytes the caller has: HH_ACC accumulator tiles per wave split between the
 // targets and the bin tiles of a group; as many sample workgroups as records fit, at most one per HH_SHARE samples of the
 // longest state and about four workgroups per CU in all.  TXM_OK or TXM_ERR_WORKSPACE.
 static int hh_plan(int32_t K, int32_t nbins, int32_t n_alpha, int64_t n_max, size_t ws_bytes, HhPlan *p) {
   const int64_t NT = nbins / 16 + 1;  // the bins and the outside class
-  const int64_t room = HH_ACC / hh_class(n_alpha);
+  const int64_t room = HH_ACC / mb_na_class(n_alpha);
   p->bt = NT < room ? NT : room;
   p->groups = cdiv(NT, p->bt);
   p->rt = cdiv((int64_t)K + 2, 16);
@@ -286,23 +285,12 @@ extern "C" int txm_mbar_hist(const txm_mbar_state *states_host, const int32_t *c
                              const double *alpha_host, int32_t n_alpha, double *out, double *lnw, void *ws,
                              size_t ws_bytes, txm_stream stream) {
   if (const int rc = hh_check_shape("mbar_hist", K, nbins, n_alpha)) return rc;
-  TXM_REQUIRE(states_host, "mbar_hist: null state table");
-  TXM_REQUIRE(bin_host, "mbar_hist: null table of bin indices");
   int64_t nmax = 0;
-  for (int32_t s = 0; s < K; ++s) {
-    const txm_mbar_state &st = states_host[s];
-    TXM_REQUIRE(st.u, "mbar_hist: state %d has a null u", (int)s);
-    TXM_REQUIRE(bin_host[s], "mbar_hist: state %d has null bin indices", (int)s);
-    TXM_REQUIRE(st.n >= 1, "mbar_hist: state %d has n = %lld samples (need >= 1)", (int)s, (long long)st.n);
-    nmax = st.n > nmax ? st.n : nmax;
-  }
+  if (const int rc = mb_check_states(states_host, K, false, false, 0, "mbar_hist", nullptr, &nmax)) return rc;
+  TXM_REQUIRE(bin_host, "mbar_hist: null table of bin indices");
+  for (int32_t s = 0; s < K; ++s) TXM_REQUIRE(bin_host[s], "mbar_hist: state %d has null bin indices", (int)s);
   TXM_REQUIRE(alpha0_host && g_host && logD && alpha_host && out && ws, "mbar_hist: null pointer");
-  for (int32_t k = 0; k < K; ++k)
-    TXM_REQUIRE(std::isfinite(alpha0_host[k]) && std::isfinite(g_host[k]), "mbar_hist: alpha0 / g of state %d not finite",
-                (int)k);
-  for (int32_t a = 0; a < n_alpha; ++a)
-    TXM_REQUIRE(std::isfinite(alpha_host[a]), "mbar_hist: target %d not finite", (int)a);
-  TXM_REQUIRE(std::isfinite(upiv), "mbar_hist: pivot not finite");
+  if (const int rc = mb_check_finite("mbar_hist", K, alpha0_host, g_host, n_alpha, alpha_host, upiv)) return rc;
   HhPlan p;
   if (hh_plan(K, nbins, n_alpha, nmax, ws_bytes, &p) != TXM_OK) {
     set_error("mbar_hist: workspace too small (%zu bytes, the smallest plan needs %zu)", ws_bytes, p.bytes);
@@ -310,44 +298,28 @@ extern "C" int txm_mbar_hist(const txm_mbar_state *states_host, const int32_t *c
   }
   hipStream_t st = (hipStream_t)stream;
   // one staging copy: state table, g, alpha0 (the head of txm_mbar_eval), the slot of M, the bin pointers
-  unsigned char head[HH_HEAD_BYTES] = {};
-  memcpy(head, states_host, (size_t)K * sizeof(txm_mbar_state));
-  memcpy(head + MB_MAXK * sizeof(txm_mbar_state), g_host, (size_t)K * sizeof(double));
-  memcpy(head + MB_MAXK * sizeof(txm_mbar_state) + MB_MAXK * sizeof(double), alpha0_host, (size_t)K * sizeof(double));
-  memcpy(head + MB_HEAD_BYTES, bin_host, (size_t)K * sizeof(void *));
-  TXM_HIP(hipMemcpyAsync(ws, head, HH_HEAD_BYTES, hipMemcpyHostToDevice, st));
-  const txm_mbar_state *tab = (const txm_mbar_state *)ws;
-  const double *gk = (const double *)((char *)ws + MB_MAXK * sizeof(txm_mbar_state));
-  const double *a0k = gk + MB_MAXK;
-  double *M = (double *)((char *)ws + MB_TAB_BYTES);
+  MbarHead h;
+  if (const int rc = mb_stage_head(ws, states_host, K, g_host, alpha0_host, HH_HEAD_BYTES, bin_host, (size_t)K * sizeof(void *), st,
+                                   &h))
+    return rc;
+  const txm_mbar_state *tab = h.tab;
+  const double *gk = h.gk, *a0k = h.a0k;
+  double *M = h.M;
   const int32_t *const *bins = (const int32_t *const *)((char *)ws + MB_HEAD_BYTES);
   double *partial = (double *)((char *)ws + HH_HEAD_BYTES);
-  MbarTargets ta;
-  for (int a = 0; a < MB_MAXA; ++a) ta.a[a] = alpha_host[a < n_alpha ? a : n_alpha - 1];
+  const MbarTargets ta = mb_targets(alpha_host, n_alpha);
   // exact per-target maximum of the exponent (predict's pass); its per-block maxima lie where the records will, so the
   // blocks are also capped by the bytes of the plan (a maximum is exact in any order: M does not depend on the cap)
-  int64_t capm = (int64_t)num_cus() * 8 / K;
   const int64_t fit = (int64_t)((p.bytes - HH_HEAD_BYTES) / ((size_t)K * MB_MAXA * sizeof(double)));
+  int64_t capm = mb_blocks_per_state(K);
   capm = capm > fit ? fit : capm;
-  capm = capm < 1 ? 1 : capm;
-  int64_t gm = cdiv(nmax, (int64_t)MB_BLOCK * 8);
-  gm = gm > capm ? capm : (gm < 1 ? 1 : gm);
-  hipLaunchKernelGGL(mbar_max_kernel, dim3((unsigned)gm, (unsigned)K), dim3(MB_BLOCK), 0, st, tab, logD, upiv, ta,
-                     partial);
-  TXM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mbar_max_final_kernel, dim3(1), dim3(MB_BLOCK), 0, st, partial, (int)(gm * K), M);
-  TXM_LAUNCH_CHECK();
+  if (const int rc = mb_max_pass(tab, K, nmax, capm < 1 ? 1 : capm, logD, upiv, ta, partial, M, st)) return rc;
   const int NT = nbins / 16 + 1;
   const dim3 grid((unsigned)p.gx, (unsigned)p.groups, (unsigned)p.rt), block(MB_BLOCK);
 #define TXM_HH(NA_)                                                                                                     \
   hipLaunchKernelGGL((mbar_hist_kernel<NA_, HH_ACC / NA_>), grid, block, 0, st, tab, bins, (int)K, (int)nbins, NT,      \
                      (int)p.bt, gk, a0k, logD, upiv, ta, M, (int)n_alpha, partial)
-  switch (hh_class(n_alpha)) {
-    case 1: TXM_HH(1); break;
-    case 2: TXM_HH(2); break;
-    case 4: TXM_HH(4); break;
-    default: TXM_HH(8);
-  }
+  TXM_MB_NA_DISPATCH(n_alpha, TXM_HH)
 #undef TXM_HH
   TXM_LAUNCH_CHECK();
   const int64_t total = (int64_t)n_alpha * (K + 2) * (nbins + 1);

@@ -20,7 +20,7 @@ from ._lib import ResampleOpts, SamplerSpec, check
 from ._mbar_host import (_MBAR_MAX_STEP, _MBAR_PINV_CUT, _sym_pinv, mbar_block_coef_mean, mbar_block_coef_sampled,  # noqa: F401
                          mbar_block_coef_target, mbar_block_covariance, mbar_block_variance, mbar_block_width, mbar_hist_covariance, mbar_hist_terms,
                          mbar_hist_variance, mbar_mean_covariance, mbar_mean_variance, mbar_newton, mbar_newton_batched,
-                         mbar_overlap, mbar_reduced_pinv, mbar_solution_g, mbar_theta)
+                         mbar_overlap, mbar_reduced_pinv, mbar_solution_g, mbar_theta, mbar_unpack_h)
 from ._operands import either_layout, resample_pitch_ok, rowmajor_layout  # noqa: F401
 
 F64 = torch.float64
@@ -1184,6 +1184,95 @@ def _mbar_table(us, xs=None):
     return tab, (u2, x2), np.asarray(ns, dtype=np.float64), C
 
 
+def _mbar_alpha0(alpha0, K):
+    """alpha0 as a contiguous float64 (K,)."""
+    a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(-1))
+    if a0.shape != (K,):
+        raise ValueError("need one alpha0 per state")
+    return a0
+
+
+def _mbar_b(us, alpha0, upiv):
+    """(ns, a0, b): the states' sample counts, alpha0 as (K,) and b = ln N - alpha0 upiv, the log-weights at f = 0."""
+    a0 = _mbar_alpha0(alpha0, len(us))
+    ns = np.array([u.shape[0] for u in us], dtype=np.float64)
+    return ns, a0, np.log(ns) - a0 * upiv
+
+
+MBAR_CROSS_MAX_TARGETS = 8    # txm_mbar_cross_cov with cross_alpha: one call, MB_MAXA targets
+MBAR_CROSS_MAX_COLUMNS = 255  # txm_mbar_cross_cov, txm_mbar_block_cov: C + 1 logical columns in at most 16 tiles a side
+
+
+class _MbarTargetCall(NamedTuple):
+    """What a pass over the targets at a solution starts from (``_mbar_target_call``)."""
+
+    tab: object        # the host table of txm_mbar_state entries
+    keep: object       # the tensors it points into: alive until the results are on the host
+    K: int
+    C: int
+    ns: np.ndarray     # samples per state
+    a0: np.ndarray     # (K,), contiguous
+    g: np.ndarray      # (K,), contiguous: the solution's shifted log-weights (mbar_solution_g)
+    c: float           # their shift: sol.logD is the true log-denominator + c
+    al: np.ndarray     # the targets, flat
+
+
+def _mbar_target_call(us, xs, alpha0, sol, alphas, means=None, *, wide=None, many=None) -> _MbarTargetCall:
+    """The checked operands of mbar_cov_sums, mbar_cross_cov_sums, mbar_block_gamma and mbar_hist_sums (``xs=None``).
+    ``means``: checked to be (n_alpha, C) float64 CUDA.  ``wide`` / ``many``: the caller's refusal of more than 255
+    columns / more than 8 targets (a text with one ``{}``); None: no limit."""
+    tab, keep, ns, C = _mbar_table(us, xs)
+    K = len(us)
+    a0 = _mbar_alpha0(alpha0, K)
+    g, c = mbar_solution_g(ns, a0, sol)
+    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
+    if wide is not None and C > MBAR_CROSS_MAX_COLUMNS:
+        raise ValueError(wide.format(C))
+    if many is not None and len(al) > MBAR_CROSS_MAX_TARGETS:
+        raise ValueError(many.format(len(al)))
+    if means is not None:
+        _check_f64_cuda(means, "means")
+        if means.shape != (len(al), C):
+            raise ValueError(f"means must be ({len(al)}, {C}), got {tuple(means.shape)}")
+    if sol.logD.shape != (int(ns.sum()),):
+        raise ValueError("sol.logD must hold one value per pooled sample")
+    return _MbarTargetCall(tab, keep, K, C, ns, a0, np.ascontiguousarray(g), c, al)
+
+
+def _mbar_cov_passes(t: _MbarTargetCall, sol, means):
+    """txm_mbar_cov per 8 targets, launched: yields (chunk, mean, out, lnw, ws, nbytes) of each pass -- the targets, their
+    rows of ``means``, the pass's device output [n][1 + K + C (1 + K)] and ln sum_n w_an, its workspace (tag "mbar_cov")
+    and the bytes of the size query.  A second pass of the caller's goes onto the same stream inside the loop, fed lnw on
+    the device: nothing waits on the host in between."""
+    L = _L()
+    dp = ct.POINTER(ct.c_double)
+    K, C = t.K, t.C
+    for i0, chunk in _eight_per_pass(t.al):
+        na = len(chunk)
+        mean = means[i0:i0 + na].contiguous()
+        out = torch.empty((na, 1 + K + C * (1 + K)), dtype=F64, device="cuda")
+        lnw = torch.empty(na, dtype=F64, device="cuda")
+        nbytes = L.txm_mbar_cov_ws_bytes(K, C, na)
+        ws = workspace(nbytes, tag="mbar_cov")
+        check(L.txm_mbar_cov(t.tab, K, C, float(sol.upiv), t.a0.ctypes.data_as(dp), t.g.ctypes.data_as(dp), _ptr(sol.logD),
+                             chunk.ctypes.data_as(dp), na, _ptr(mean), _ptr(out), _ptr(lnw), _ptr(ws), nbytes,
+                             _stream()), "txm_mbar_cov")
+        yield chunk, mean, out, lnw, ws, nbytes
+
+
+def _mbar_cov_rows(t: _MbarTargetCall, outs):
+    """(Q, B, yy, b) on the host from the passes' ``out`` rows: per target Q, B_k, then (yy_c, b_kc) per column."""
+    v = torch.cat(outs, dim=0).cpu().numpy()
+    rest = v[:, 1 + t.K:].reshape(len(t.al), t.C, 1 + t.K)
+    return v[:, 0].copy(), v[:, 1:1 + t.K].copy(), rest[:, :, 0].copy(), rest[:, :, 1:].copy()
+
+
+def _mbar_true_lnw(t: _MbarTargetCall, sol, lnws) -> np.ndarray:
+    """ln sum_n e^{-alpha u_n - logD_n} with the true log-denominators from the kernels' lnw: their exponents are
+    -alpha (u - upiv) - (logD + c), so the sum is e^{-alpha upiv + c} times theirs."""
+    return torch.cat(lnws).cpu().numpy() - t.al * sol.upiv + t.c
+
+
 def mbar_pivot(us) -> float:
     """The pivot the MBAR kernels subtract from u: the pooled mean (torch's sum, a deterministic reduction)."""
     tot = sum(float(u.sum()) for u in us)
@@ -1212,10 +1301,7 @@ def mbar_eval(us, alpha0, g, upiv: float, logD: torch.Tensor | None = None):
                           ws.numel(), _stream()), "txm_mbar_eval")
     v = out.cpu().numpy()
     del keep
-    H = np.zeros((K, K))
-    H[np.triu_indices(K)] = v[K:K + nh]
-    H = H + np.triu(H, 1).T
-    return v[:K].copy(), H, float(v[K + nh])
+    return v[:K].copy(), mbar_unpack_h(v[K:K + nh], K), float(v[K + nh])
 
 
 def mbar_initial_f(us, alpha0) -> np.ndarray:
@@ -1236,14 +1322,9 @@ def mbar_solve(us, alpha0, *, tol: float = 1e-12, max_iter: int = 100) -> MbarSo
     (u: one float64 CUDA tensor per state, any lengths).  Damped Newton (``mbar_newton``), one device evaluation pass
     (``mbar_eval``) per step: the host waits for each pass -- acceptable because a model solves once and caches the
     result.  Every pass also stores the pooled log-denominators, so the buffer returned is the solution's."""
-    K = len(us)
-    a0 = np.asarray(alpha0, dtype=np.float64).reshape(-1)
-    if a0.shape != (K,):
-        raise ValueError("need one alpha0 per state")
-    ns = np.array([u.shape[0] for u in us], dtype=np.float64)
     upiv = mbar_pivot(us)
+    ns, a0, b = _mbar_b(us, alpha0, upiv)
     logD = torch.empty(int(ns.sum()), dtype=F64, device="cuda")
-    b = np.log(ns) - a0 * upiv
 
     def evaluate(g):
         return mbar_eval(us, a0, g, upiv, logD)
@@ -1263,7 +1344,7 @@ def mbar_predict(xs, us, alpha0, f, logD, alphas, *, upiv: float | None = None) 
         upiv = mbar_pivot(us)
     if logD is None:
         a0 = np.asarray(alpha0, dtype=np.float64).reshape(-1)
-        g = np.log(ns) + np.asarray(f, dtype=np.float64) - a0 * upiv
+        g = np.log(ns) + np.asarray(f, dtype=np.float64) - a0 * upiv      # (summed in this order: not _mbar_b's b + f)
         logD = torch.empty(int(ns.sum()), dtype=F64, device="cuda")
         mbar_eval(us, a0, g - g.max(), upiv, logD)
     _check_f64_cuda(logD, "logD")
@@ -1304,44 +1385,13 @@ def mbar_cov_sums(xs, us, alpha0, sol: MbarSolution, alphas, means, *, with_lnw:
     b (n_alpha, C, K) = sum_n W_nk W_na (x_nc - mean_ac).  ``means``: (n_alpha, C) float64 CUDA, ``mbar_predict``'s output
     for the same targets.  ``with_lnw``: also ln sum_n e^{-alpha u_n - logD_n} (n_alpha,) with the true log-denominators
     (the solve's pivot and shift taken out): minus the target's free energy in the gauge of ``sol.f``."""
-    L = _L()
-    tab, keep, ns, C = _mbar_table(us, xs)
-    K = len(us)
-    a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(-1))
-    if a0.shape != (K,):
-        raise ValueError("need one alpha0 per state")
-    g, c = mbar_solution_g(ns, a0, sol)
-    g = np.ascontiguousarray(g)
-    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
-    _check_f64_cuda(means, "means")
-    if means.shape != (len(al), C):
-        raise ValueError(f"means must be ({len(al)}, {C}), got {tuple(means.shape)}")
-    if sol.logD.shape != (int(ns.sum()),):
-        raise ValueError("sol.logD must hold one value per pooled sample")
-    dp = ct.POINTER(ct.c_double)
-    width = 1 + K + C * (1 + K)
+    t = _mbar_target_call(us, xs, alpha0, sol, alphas, means)
     outs, lnws = [], []
-    for i0, chunk in _eight_per_pass(al):
-        na = len(chunk)
-        mean = means[i0:i0 + na].contiguous()
-        out = torch.empty((na, width), dtype=F64, device="cuda")
-        lnw = torch.empty(na, dtype=F64, device="cuda")
-        ws = workspace(L.txm_mbar_cov_ws_bytes(K, C, na), tag="mbar_cov")
-        check(L.txm_mbar_cov(tab, K, C, float(sol.upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp), _ptr(sol.logD),
-                             chunk.ctypes.data_as(dp), na, _ptr(mean), _ptr(out), _ptr(lnw), _ptr(ws), ws.numel(),
-                             _stream()), "txm_mbar_cov")
+    for _, _, out, lnw, _, _ in _mbar_cov_passes(t, sol, means):
         outs.append(out)
         lnws.append(lnw)
-    v = torch.cat(outs, dim=0).cpu().numpy()
-    del keep
-    Q = v[:, 0].copy()
-    B = v[:, 1:1 + K].copy()
-    rest = v[:, 1 + K:].reshape(len(al), C, 1 + K)
-    yy, b = rest[:, :, 0].copy(), rest[:, :, 1:].copy()
-    if not with_lnw:
-        return Q, B, yy, b
-    # the kernel's exponents are -alpha (u - upiv) - (logD + c): sum_n e^{-alpha u_n - logD_n} = e^{-alpha upiv + c} x its sum
-    return Q, B, yy, b, torch.cat(lnws).cpu().numpy() - al * sol.upiv + c
+    sums = _mbar_cov_rows(t, outs)
+    return (*sums, _mbar_true_lnw(t, sol, lnws)) if with_lnw else sums
 
 
 def mbar_cross_cov_sums(xs, us, alpha0, sol: MbarSolution, alphas, means, *, cross_alpha: bool = False):
@@ -1351,48 +1401,23 @@ def mbar_cross_cov_sums(xs, us, alpha0, sol: MbarSolution, alphas, means, *, cro
     txm_mbar_cov pass, then the Gram pass in the same workspace on the same stream, fed the first's ln sum_n w_an on the
     device: nothing waits on the host between them.  At most 255 columns."""
     L = _L()
-    tab, keep, ns, C = _mbar_table(us, xs)
-    K = len(us)
-    a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(-1))
-    if a0.shape != (K,):
-        raise ValueError("need one alpha0 per state")
-    g, _ = mbar_solution_g(ns, a0, sol)
-    g = np.ascontiguousarray(g)
-    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
-    if C > 255:
-        raise ValueError(f"the covariance across columns takes at most 255 columns, got {C}")
-    if cross_alpha and len(al) > 8:
-        raise ValueError(f"the covariance across targets takes at most 8 targets, got {len(al)}")
-    _check_f64_cuda(means, "means")
-    if means.shape != (len(al), C):
-        raise ValueError(f"means must be ({len(al)}, {C}), got {tuple(means.shape)}")
-    if sol.logD.shape != (int(ns.sum()),):
-        raise ValueError("sol.logD must hold one value per pooled sample")
-    dp = ct.POINTER(ct.c_double)
-    width = 1 + K + C * (1 + K)
+    t = _mbar_target_call(us, xs, alpha0, sol, alphas, means,
+                          wide="the covariance across columns takes at most 255 columns, got {}",
+                          many="the covariance across targets takes at most 8 targets, got {}" if cross_alpha else None)
+    K, C, n = t.K, t.C, len(t.al)
     outs, grams = [], []
-    for i0, chunk in _eight_per_pass(al):
+    for chunk, mean, out, lnw, ws, nbytes in _mbar_cov_passes(t, sol, means):
         na = len(chunk)
-        mean = means[i0:i0 + na].contiguous()
-        out = torch.empty((na, width), dtype=F64, device="cuda")
-        lnw = torch.empty(na, dtype=F64, device="cuda")
         gram = torch.empty((na * C, na * C) if cross_alpha else (na, C, C), dtype=F64, device="cuda")
-        nbytes = L.txm_mbar_cov_ws_bytes(K, C, na)
-        ws = workspace(nbytes, tag="mbar_cov")
-        check(L.txm_mbar_cov(tab, K, C, float(sol.upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp), _ptr(sol.logD),
-                             chunk.ctypes.data_as(dp), na, _ptr(mean), _ptr(out), _ptr(lnw), _ptr(ws), nbytes,
-                             _stream()), "txm_mbar_cov")
         # (the query's bytes, not the cached buffer's: the plan, and with it the bits, depend on nothing else)
-        check(L.txm_mbar_cross_cov(tab, K, C, float(sol.upiv), _ptr(sol.logD), chunk.ctypes.data_as(dp), na, _ptr(mean),
-                                   _ptr(lnw), int(bool(cross_alpha)), _ptr(gram), _ptr(ws), nbytes, _stream()),
+        check(L.txm_mbar_cross_cov(t.tab, K, C, float(sol.upiv), _ptr(sol.logD), chunk.ctypes.data_as(ct.POINTER(ct.c_double)),
+                                   na, _ptr(mean), _ptr(lnw), int(bool(cross_alpha)), _ptr(gram), _ptr(ws), nbytes, _stream()),
               "txm_mbar_cross_cov")
         outs.append(out)
         grams.append(gram)
-    v = torch.cat(outs, dim=0).cpu().numpy()
+    b = _mbar_cov_rows(t, outs)[3]
     G = torch.cat(grams, dim=0).cpu().numpy()
-    del keep
-    b = v[:, 1 + K:].reshape(len(al), C, 1 + K)[:, :, 1:].copy()
-    return (G.reshape(len(al), C, len(al), C) if cross_alpha else G), b
+    return (G.reshape(n, C, n, C) if cross_alpha else G), b
 
 
 HIST_MAX_BINS = 1023    # txm_mbar_hist: nbins + 1 columns in at most 64 tiles of 16
@@ -1408,6 +1433,12 @@ class MbarBlockGamma(NamedTuple):
     b: np.ndarray          # (n_alpha, C, K): mbar_cov_sums' b
     B: np.ndarray          # (n_alpha, K): mbar_cov_sums' B
     lnw: np.ndarray        # (n_alpha,): mbar_cov_sums' lnw (with_lnw=True)
+
+    def slabs(self):
+        """(gamma, b, B) of every slab: its Gram matrices and its targets' rows of ``b`` and ``B`` (the slab width is
+        ``_eight_per_pass``'s)."""
+        for gamma, (i0, chunk) in zip(self.gamma, _eight_per_pass(self.lnw)):
+            yield gamma, self.b[i0:i0 + len(chunk)], self.B[i0:i0 + len(chunk)]
 
 
 def mbar_block_lengths(block, ns) -> np.ndarray:
@@ -1450,62 +1481,35 @@ def mbar_block_gamma(xs, us, alpha0, sol: MbarSolution, alphas, means, block, n_
     between them.  ``block``: an int or one int per state; ``n_levels``: Gamma for blocks of block * 2**l, l < n_levels.
     At most 255 columns."""
     L = _L()
-    tab, keep, ns, C = _mbar_table(us, xs)
-    K = len(us)
-    a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(-1))
-    if a0.shape != (K,):
-        raise ValueError("need one alpha0 per state")
-    g, c = mbar_solution_g(ns, a0, sol)
-    g = np.ascontiguousarray(g)
-    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
-    if C > 255:
-        raise ValueError(f"the blocked MBAR error bars take at most 255 columns, got {C}")
     n_levels = int(n_levels)
     if not 1 <= n_levels <= 32:
         raise ValueError(f"n_levels must be in [1, 32], got {n_levels}")
-    _check_f64_cuda(means, "means")
-    if means.shape != (len(al), C):
-        raise ValueError(f"means must be ({len(al)}, {C}), got {tuple(means.shape)}")
-    if sol.logD.shape != (int(ns.sum()),):
-        raise ValueError("sol.logD must hold one value per pooled sample")
-    blk = mbar_block_lengths(block, ns)
-    n64 = np.ascontiguousarray(ns, dtype=np.int64)
+    t = _mbar_target_call(us, xs, alpha0, sol, alphas, means, wide="the blocked MBAR error bars take at most 255 columns, got {}")
+    K, C = t.K, t.C
+    blk = mbar_block_lengths(block, t.ns)
+    n64 = np.ascontiguousarray(t.ns, dtype=np.int64)
     dp, ip = ct.POINTER(ct.c_double), ct.POINTER(ct.c_int64)
-    width = 1 + K + C * (1 + K)
     outs, lnws, gammas = [], [], []
     nblocks = torch.empty((n_levels, K), dtype=torch.int64, device="cuda")
-    for i0, chunk in _eight_per_pass(al):
+    for chunk, mean, out, lnw, _, _ in _mbar_cov_passes(t, sol, means):
         na = len(chunk)
         M = mbar_block_width(K, na, C)
-        mean = means[i0:i0 + na].contiguous()
-        out = torch.empty((na, width), dtype=F64, device="cuda")
-        lnw = torch.empty(na, dtype=F64, device="cuda")
         gamma = torch.empty((n_levels, M, M), dtype=F64, device="cuda")
-        nbytes = L.txm_mbar_cov_ws_bytes(K, C, na)
-        ws = workspace(nbytes, tag="mbar_cov")
-        check(L.txm_mbar_cov(tab, K, C, float(sol.upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp), _ptr(sol.logD),
-                             chunk.ctypes.data_as(dp), na, _ptr(mean), _ptr(out), _ptr(lnw), _ptr(ws), nbytes,
-                             _stream()), "txm_mbar_cov")
         plan = (ct.c_int64 * 7)()
         check(L.txm_mbar_block_cov_plan(n64.ctypes.data_as(ip), blk.ctypes.data_as(ip), K, C, na, n_levels, _SIZE_MAX, plan),
               "txm_mbar_block_cov_plan")
         bbytes = int(plan[5])
         wsb = workspace(bbytes, tag="mbar_block")
         # (the plan's bytes, not the cached buffer's: the plan, and with it the bits, depend on nothing else)
-        check(L.txm_mbar_block_cov(tab, K, C, float(sol.upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp), _ptr(sol.logD),
+        check(L.txm_mbar_block_cov(t.tab, K, C, float(sol.upiv), t.a0.ctypes.data_as(dp), t.g.ctypes.data_as(dp), _ptr(sol.logD),
                                    chunk.ctypes.data_as(dp), na, _ptr(mean), _ptr(lnw), blk.ctypes.data_as(ip), n_levels,
                                    _ptr(gamma), _ptr(nblocks), _ptr(wsb), bbytes, _stream()), "txm_mbar_block_cov")
         outs.append(out)
         lnws.append(lnw)
         gammas.append(gamma)
-    v = torch.cat(outs, dim=0).cpu().numpy()
-    gam = [t.cpu().numpy() for t in gammas]
-    nbl = nblocks.cpu().numpy()
-    lnw = torch.cat(lnws).cpu().numpy() - al * sol.upiv + c
-    del keep
-    B = v[:, 1:1 + K].copy()
-    b = v[:, 1 + K:].reshape(len(al), C, 1 + K)[:, :, 1:].copy()
-    return MbarBlockGamma(gam, nbl, b, B, lnw)
+    _, B, _, b = _mbar_cov_rows(t, outs)
+    gam = [g.cpu().numpy() for g in gammas]
+    return MbarBlockGamma(gam, nblocks.cpu().numpy(), b, B, _mbar_true_lnw(t, sol, lnws))
 
 
 def bin_index(values, edges) -> torch.Tensor:
@@ -1532,11 +1536,11 @@ def mbar_hist_sums(bins, us, alpha0, sol: MbarSolution, alphas, nbins: int):
     T (n_alpha, K, nbins + 1) = sum_n W_nk W_na 1_b, Q (n_alpha,) = sum_b S_ab, B (n_alpha, K) = sum_b T_kab and
     lnw (n_alpha,) = ln sum_n e^{-alpha u_n - logD_n} as ``mbar_cov_sums`` gives it."""
     L = _L()
-    tab, keep, ns, _ = _mbar_table(us)
-    K = len(us)
     nbins = int(nbins)
     if not 1 <= nbins <= HIST_MAX_BINS:
         raise ValueError(f"a histogram takes 1 <= nbins <= {HIST_MAX_BINS} bins, got {nbins}")
+    t = _mbar_target_call(us, None, alpha0, sol, alphas)
+    K, ns = t.K, t.ns
     if len(bins) != K:
         raise ValueError("need one tensor of bin indices per state")
     b2 = []
@@ -1547,17 +1551,9 @@ def mbar_hist_sums(bins, us, alpha0, sol: MbarSolution, alphas, nbins: int):
             raise ValueError(f"bins of state {s} must be ({int(ns[s])},), got {tuple(b.shape)}")
         b2.append(b.contiguous())
     btab = (ct.c_void_p * K)(*[b.data_ptr() for b in b2])
-    a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(-1))
-    if a0.shape != (K,):
-        raise ValueError("need one alpha0 per state")
-    g, c = mbar_solution_g(ns, a0, sol)
-    g = np.ascontiguousarray(g)
-    al = np.atleast_1d(np.asarray(alphas, dtype=np.float64)).reshape(-1)
-    if sol.logD.shape != (int(ns.sum()),):
-        raise ValueError("sol.logD must hold one value per pooled sample")
     dp = ct.POINTER(ct.c_double)
     outs, lnws = [], []
-    for _, chunk in _eight_per_pass(al):
+    for _, chunk in _eight_per_pass(t.al):
         na = len(chunk)
         plan = (ct.c_int64 * 4)()
         check(L.txm_mbar_hist_plan(K, nbins, na, int(ns.max()), _SIZE_MAX, plan), "txm_mbar_hist_plan")
@@ -1566,14 +1562,14 @@ def mbar_hist_sums(bins, us, alpha0, sol: MbarSolution, alphas, nbins: int):
         lnw = torch.empty(na, dtype=F64, device="cuda")
         ws = workspace(nbytes, tag="mbar_hist")
         # (the plan's bytes, not the cached buffer's: the plan, and with it the bits, depend on nothing else)
-        check(L.txm_mbar_hist(tab, btab, K, nbins, float(sol.upiv), a0.ctypes.data_as(dp), g.ctypes.data_as(dp),
+        check(L.txm_mbar_hist(t.tab, btab, K, nbins, float(sol.upiv), t.a0.ctypes.data_as(dp), t.g.ctypes.data_as(dp),
                               _ptr(sol.logD), chunk.ctypes.data_as(dp), na, _ptr(out), _ptr(lnw), _ptr(ws), nbytes,
                               _stream()), "txm_mbar_hist")
         outs.append(out)
         lnws.append(lnw)
     v = torch.cat(outs, dim=0).cpu().numpy()
-    lnw = torch.cat(lnws).cpu().numpy() - al * sol.upiv + c
-    del keep, b2
+    lnw = _mbar_true_lnw(t, sol, lnws)
+    del b2
     T, H, S = v[:, :K, :].copy(), v[:, K, :].copy(), v[:, K + 1, :].copy()
     return H, S, T, S.sum(axis=-1), T.sum(axis=-1), lnw
 
@@ -1638,11 +1634,7 @@ def mbar_boot_eval(us, alpha0, samplers, g, upiv: float, active=None):
                                float(upiv), _ptr(out), _ptr(ws), ws.numel(), _stream()), "txm_mbar_boot_eval")
     v = out.cpu().numpy()[rows]
     del keep
-    iu = np.triu_indices(K)
-    H = np.zeros((len(rows), K, K))
-    H[:, iu[0], iu[1]] = v[:, K:K + nh]
-    H[:, iu[1], iu[0]] = v[:, K:K + nh]
-    return v[:, :K].copy(), H, v[:, K + nh].copy()
+    return v[:, :K].copy(), mbar_unpack_h(v[:, K:K + nh], K), v[:, K + nh].copy()
 
 
 def mbar_bootstrap_solve(us, alpha0, samplers, sol0: MbarSolution, *, tol: float = 1e-12, max_iter: int = 100) -> np.ndarray:
@@ -1651,15 +1643,11 @@ def mbar_bootstrap_solve(us, alpha0, samplers, sol0: MbarSolution, *, tol: float
     solution ``sol0`` (``mbar_solve`` of the same states; its pivot is reused).  Replicates go in slabs whose
     workspace fits ``workspace_budget()``; a slab's rows are the rows of the unslabbed call bit for bit."""
     K = len(us)
-    a0 = np.asarray(alpha0, dtype=np.float64).reshape(-1)
-    if a0.shape != (K,):
-        raise ValueError("need one alpha0 per state")
+    upiv = float(sol0.upiv)
+    ns, a0, b = _mbar_b(us, alpha0, upiv)
     if len(samplers) != K:
         raise ValueError("need one sampler per state")
-    ns = np.array([u.shape[0] for u in us], dtype=np.float64)
     nrep = int(samplers[0].nrep)
-    upiv = float(sol0.upiv)
-    b = np.log(ns) - a0 * upiv
     f0 = np.asarray(sol0.f, dtype=np.float64)
     slab = _mbar_boot_slab(K, 1, 1, int(ns.sum()), nrep)
     out = np.empty((nrep, K))

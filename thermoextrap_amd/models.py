@@ -1664,6 +1664,17 @@ class InterpModelPiecewise(StateCollection, PiecewiseMixin):
         return pred, _delta.per_alpha_pairs(self, alpha, alpha_name, method, cov_of)
 
 
+def _std(var):
+    """The standard deviation of a variance that rounding may have left slightly negative."""
+    return np.sqrt(np.clip(var, 0.0, None))
+
+
+def _along_alpha(value, error, name, avals):
+    """(value, error) as two DataArrays along the alpha dim ``name``."""
+    coords = {name: avals}
+    return DataArray(value, (name,), coords=coords), DataArray(error, (name,), coords=coords)
+
+
 class MBAROverlap(NamedTuple):
     """What ``MBARModel.overlap`` returns: the K x K overlap ``matrix``, its ``eigenvalues`` (descending) and the
     ``scalar`` 1 - the second largest eigenvalue."""
@@ -1720,7 +1731,7 @@ class MBARHistogram:
                 v = np.einsum("abb->ab", c)
                 pr, vr, cbr = p[rows, r][:, None], v[rows, r][:, None], c[rows, :, r]
                 var = v / (p * p) + vr / (pr * pr) - 2.0 * cbr / (p * pr)
-                dF = np.where((p > 0) & (pr > 0), np.sqrt(np.clip(var, 0.0, None)), np.nan)
+                dF = np.where((p > 0) & (pr > 0), _std(var), np.nan)
                 dF[rows, r] = np.where(pr[:, 0] > 0, 0.0, np.nan)
                 F = F - F[rows, r][:, None]
         return (DataArray(F, self.p.dims, coords=self.p.coords), DataArray(dF, self.p.dims, coords=self.p.coords))
@@ -1795,17 +1806,19 @@ class MBARModel(StateCollection):
     def predict(self, alpha, alpha_name=None):
         """<x> at every alpha: dims (alpha_name, *the non-record dims of xv); a scalar alpha keeps a length-1 alpha dim
         (the reference's expand_dims, models.py:1085-1086)."""
-        if alpha_name is None:
-            alpha_name = self.alpha_name
-        alpha = xrwrap_alpha(alpha, name=alpha_name)
-        avals = np.atleast_1d(np.asarray(alpha.values, dtype=float))
-        if avals.ndim != 1:
-            raise ValueError("alpha must be a scalar or 1-D")
-        us, xs, others, cshape = self._samples()
-        sol = self._solution()
-        out = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
-        vals = out.cpu().numpy().reshape(len(avals), *cshape)
+        avals, alpha_name = self._alpha_values(alpha, alpha_name)
+        _, _, others, cshape = self._samples()
+        vals = self._means(avals)[1].cpu().numpy().reshape(len(avals), *cshape)
         return DataArray(vals, (alpha_name, *others), coords={alpha_name: avals})
+
+    def _means(self, avals, first_column=False):
+        """(xs, means): ``engine.mbar_predict`` at the cached solution, on the device, and the observables it averaged;
+        ``first_column``: the first observable column only (the free energies need no x)."""
+        us, xs, _, _ = self._samples()
+        sol = self._solution()
+        if first_column:
+            xs = [x[:, :1] for x in xs]
+        return xs, engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
 
     # ---- the estimator's asymptotic covariance (Shirts & Chodera 2008, eq. 8 and appendix D) --------------------------
     # It assumes independent samples: decorrelate first (timeseries.statistical_inefficiencies).
@@ -1826,6 +1839,7 @@ class MBARModel(StateCollection):
         return self._cache["mbar_pinv"]
 
     def _alpha_values(self, alpha, alpha_name):
+        """(values, name) of the targets: a float 1-D array (a scalar alpha becomes length 1) and the alpha dim."""
         if alpha_name is None:
             alpha_name = self.alpha_name
         alpha = xrwrap_alpha(alpha, name=alpha_name)
@@ -1858,21 +1872,18 @@ class MBARModel(StateCollection):
         """(means on the device, engine.MbarBlockGamma, C) of the targets; ``first_column``: the first observable column
         only (the free energies need no x)."""
         us, xs, _, _ = self._samples()
-        sol = self._solution()
-        if first_column:
-            xs = [x[:, :1] for x in xs]
-        C = int(xs[0].shape[1])
-        if C > 255:
+        C = 1 if first_column else int(xs[0].shape[1])
+        if C > engine.MBAR_CROSS_MAX_COLUMNS:
             raise ValueError(f"the blocked MBAR error bars (block=...) take at most 255 observable columns, got {C}")
-        means = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
-        return means, engine.mbar_block_gamma(xs, us, self.alpha0, sol, avals, means, block, n_levels=n_levels), C
+        xs, means = self._means(avals, first_column)
+        return means, engine.mbar_block_gamma(xs, us, self.alpha0, self._solution(), avals, means, block, n_levels=n_levels), C
 
     def _block_mean_variance(self, res, C):
         """(n_levels, n_alpha, C): l^T Gamma l of every average, slab by slab."""
         Gs, N, pinv = self._gram(), self._counts(), self._reduced_pinv()
         out = []
-        for i, gam in enumerate(res.gamma):
-            L = engine.mbar_block_coef_mean(Gs, N, res.b[8 * i:8 * i + 8], pinv=pinv)
+        for gam, b, _ in res.slabs():
+            L = engine.mbar_block_coef_mean(Gs, N, b, pinv=pinv)
             out.append(engine.mbar_block_variance(gam, L).reshape(gam.shape[0], -1, C))
         return np.concatenate(out, axis=1)
 
@@ -1892,7 +1903,7 @@ class MBARModel(StateCollection):
         us, xs, others, cshape = self._samples()
         sol = self._solution()
         if block is None:
-            means = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
+            _, means = self._means(avals)
             _, _, yy, b = engine.mbar_cov_sums(xs, us, self.alpha0, sol, avals, means)
             var = engine.mbar_mean_variance(self._gram(), self._counts(), yy, b, pinv=self._reduced_pinv())
         else:
@@ -1900,7 +1911,7 @@ class MBARModel(StateCollection):
             var = self._block_mean_variance(res, C)[0]
         dims, coords = (alpha_name, *others), {alpha_name: avals}
         mean = DataArray(means.cpu().numpy().reshape(len(avals), *cshape), dims, coords=coords)
-        err = DataArray(np.sqrt(np.clip(var, 0.0, None)).reshape(len(avals), *cshape), dims, coords=coords)
+        err = DataArray(_std(var).reshape(len(avals), *cshape), dims, coords=coords)
         return mean, err
 
     def blocking_curve(self, alpha, block, alpha_name=None):
@@ -1939,25 +1950,26 @@ class MBARModel(StateCollection):
         avals, alpha_name = self._alpha_values(alpha, alpha_name)
         us, xs, others, cshape = self._samples()
         C = int(np.prod(cshape, dtype=np.int64))
-        if C > 255:
+        if C > engine.MBAR_CROSS_MAX_COLUMNS:
             raise ValueError(f"predict_with_covariance takes at most 255 observable columns, got {C}")
-        if cross_alpha and len(avals) > 8:
-            raise ValueError(f"predict_with_covariance(cross_alpha=True) takes at most 8 targets, got {len(avals)}")
+        if cross_alpha and len(avals) > engine.MBAR_CROSS_MAX_TARGETS:
+            raise ValueError(f"predict_with_covariance(cross_alpha=True) takes at most {engine.MBAR_CROSS_MAX_TARGETS} targets, "
+                             f"got {len(avals)}")
         sol = self._solution()
         na = len(avals)
         if block is not None:
             means, res, _ = self._block_gamma(avals, block)
             Gs, N, pinv = self._gram(), self._counts(), self._reduced_pinv()
             covs = []
-            for i, gam in enumerate(res.gamma):
-                L = engine.mbar_block_coef_mean(Gs, N, res.b[8 * i:8 * i + 8], pinv=pinv)
+            for gam, b, _ in res.slabs():
+                L = engine.mbar_block_coef_mean(Gs, N, b, pinv=pinv)
                 if cross_alpha:
                     covs.append(engine.mbar_block_covariance(gam[0], L))
                 else:
                     covs += [engine.mbar_block_covariance(gam[0], L[a * C:(a + 1) * C]) for a in range(L.shape[0] // C)]
             cov = covs[0] if cross_alpha else np.stack(covs)
         else:
-            means = engine.mbar_predict(xs, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
+            _, means = self._means(avals)
             gram, b = engine.mbar_cross_cov_sums(xs, us, self.alpha0, sol, avals, means, cross_alpha=cross_alpha)
             if cross_alpha:
                 gram, b = gram.reshape(na * C, na * C), b.reshape(na * C, -1)
@@ -2047,16 +2059,14 @@ class MBARModel(StateCollection):
         Gs, N, pinv = self._gram(), self._counts(), self._reduced_pinv()
         var = engine.mbar_hist_variance(Gs, N, H, S, T, pinv=pinv)
         covar = engine.mbar_hist_covariance(Gs, N, H, S, T, pinv=pinv) if cov else None
-        return MBARHistogram(H[:, :nb].copy(), np.sqrt(np.clip(var, 0.0, None)), covar, H[:, nb].copy(), edges, 1.0 / Q,
+        return MBARHistogram(H[:, :nb].copy(), _std(var), covar, H[:, nb].copy(), edges, 1.0 / Q,
                              avals, alpha_name)
 
     def _target_sums(self, avals):
         """(Q, B, ln sum_n w_an) of the targets: the covariance pass over the first observable column only."""
-        us, xs, _, _ = self._samples()
-        sol = self._solution()
-        x1 = [x[:, :1] for x in xs]
-        means = engine.mbar_predict(x1, us, self.alpha0, sol.f, sol.logD, avals, upiv=sol.upiv)
-        Q, B, _, _, lnw = engine.mbar_cov_sums(x1, us, self.alpha0, sol, avals, means, with_lnw=True)
+        us, _, _, _ = self._samples()
+        x1, means = self._means(avals, first_column=True)
+        Q, B, _, _, lnw = engine.mbar_cov_sums(x1, us, self.alpha0, self._solution(), avals, means, with_lnw=True)
         return Q, B, lnw
 
     def _block_sampled_covariance(self, block) -> np.ndarray:
@@ -2089,18 +2099,14 @@ class MBARModel(StateCollection):
             else:
                 var = np.diag(self._block_sampled_covariance(block)).copy()
             var[0] = 0.0
-            coords = {name: np.asarray(self.alpha0, dtype=float)}
-            return (DataArray(np.array(self._solution().f, dtype=float), (name,), coords=coords),
-                    DataArray(np.sqrt(np.clip(var, 0.0, None)), (name,), coords=coords))
+            return _along_alpha(np.array(self._solution().f, dtype=float), _std(var), name, np.asarray(self.alpha0, dtype=float))
         avals, alpha_name = self._alpha_values(alpha, alpha_name)
-        coords = {alpha_name: avals}
         if block is not None:
             _, res, C = self._block_gamma(avals, block, first_column=True)
             Gs, N, pinv = self._gram(), self._counts(), self._reduced_pinv()
-            var = np.concatenate([engine.mbar_block_variance(gam[0], engine.mbar_block_coef_target(
-                Gs, N, res.B[8 * i:8 * i + 8], C, pinv=pinv)) for i, gam in enumerate(res.gamma)])
-            return (DataArray(-res.lnw - float(self._solution().f[0]), (alpha_name,), coords=coords),
-                    DataArray(np.sqrt(np.clip(var, 0.0, None)), (alpha_name,), coords=coords))
+            var = np.concatenate([engine.mbar_block_variance(gam[0], engine.mbar_block_coef_target(Gs, N, B, C, pinv=pinv))
+                                  for gam, _, B in res.slabs()])
+            return _along_alpha(-res.lnw - float(self._solution().f[0]), _std(var), alpha_name, avals)
         Q, B, lnw = self._target_sums(avals)
         K, N, Gs = len(self.states), self._counts(), self._gram()
         G = np.zeros((K + 1, K + 1))
@@ -2111,8 +2117,7 @@ class MBARModel(StateCollection):
             G[K, K] = Q[i]
             th = engine.mbar_theta(G, np.append(N, 0.0))
             var[i] = th[K, K] + th[0, 0] - 2.0 * th[0, K]
-        return (DataArray(-lnw - float(self._solution().f[0]), (alpha_name,), coords=coords),
-                DataArray(np.sqrt(np.clip(var, 0.0, None)), (alpha_name,), coords=coords))
+        return _along_alpha(-lnw - float(self._solution().f[0]), _std(var), alpha_name, avals)
 
     def overlap(self) -> "MBAROverlap":
         """The overlap matrix O = G diag(N_k) of the sampled states (rows sum to 1; O_jk: the share of state k's samples
@@ -2182,12 +2187,7 @@ class MBARBootstrap:
         """<x> of every replicate at every alpha: dims (alpha_name, rep_dim, *the non-record dims of xv) --
         PerturbModel's resampled layout; a scalar alpha keeps a length-1 alpha dim, as ``MBARModel.predict``."""
         p = self.parent
-        if alpha_name is None:
-            alpha_name = p.alpha_name
-        alpha = xrwrap_alpha(alpha, name=alpha_name)
-        avals = np.atleast_1d(np.asarray(alpha.values, dtype=float))
-        if avals.ndim != 1:
-            raise ValueError("alpha must be a scalar or 1-D")
+        avals, alpha_name = p._alpha_values(alpha, alpha_name)
         us, xs, others, cshape = p._samples()
         out = engine.mbar_bootstrap_predict(xs, us, p.alpha0, self.samplers, self.f, p._solution(), avals)
         vals = np.moveaxis(out.cpu().numpy(), 0, 1).reshape(len(avals), self.nrep, *cshape)
